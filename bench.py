@@ -1,8 +1,20 @@
 #!/usr/bin/env python3
 """Benchmark: device-resident tile pack + transpose + unpack (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline figure needs and nothing else: build the workload, one first
+call (plan), W untimed blocking steps and W untimed stream-ordered ones, the K timed steps, the
+outputs if --dump-outputs is given, a correctness check of C, the JSON line (metric, value,
+unit, ms_per_step, ...).  Everything else
+described below -- the extra configurations, the blocking and phase-event passes with the
+roofline and copy ceiling, the planner comparison, the end-to-end legs, the call overhead and the
+CPU baselines -- runs only with --full, which adds those fields to the same line.
+--dump-outputs DIR: right after the K timed steps every rank saves what they left in its local C
+as DIR/C.npy (DIR/C_rank<r>.npy at N > 1), float64 (complex as (re, im) pairs): all of C when it
+fits in 32 MiB over the ranks, else the elements at a fixed, seeded set of sorted positions
+(dump_positions).  The inputs are hashes of positions, so equal arguments give equal files.
 
 Workload (one "step" = one costa::transform over all local tiles, data already in HBM):
   N = 1   BASELINE configs[1]: pxtran fp64 16384 x 16384, 256 x 256 blocks, op 'T',
@@ -318,6 +330,35 @@ def count_mismatch(got, exp) -> int:
     g = got.contiguous().view(iv[got.element_size()])
     e = exp.contiguous().view(iv[exp.element_size()])
     return int((g != e).sum().item())
+
+
+DUMP_BYTES = 32 << 20  # --dump-outputs: bytes of float64 written over all ranks
+DUMP_SEED = 0xD0C5
+
+
+def dump_positions(numel: int, max_elems: int, rank: int = 0):
+    """--dump-outputs: the elements of a rank's local C that are saved -> None (all of them) when
+    numel <= max_elems, else max_elems positions drawn with replacement from a numpy PCG64
+    stream seeded by (DUMP_SEED, rank), sorted: the same positions in every run and every build"""
+    import numpy as np
+    if numel <= max_elems:
+        return None
+    return np.sort(np.random.default_rng([DUMP_SEED, rank]).integers(0, numel, max_elems))
+
+
+def dump_outputs(dirname: str, Cm, rank: int, world: int) -> str:
+    """--dump-outputs: save this rank's local C (see dump_positions) -> the file written"""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    per_elem = 16 if torch.is_complex(Cm) else 8  # as float64
+    pos = dump_positions(Cm.numel(), max(1, DUMP_BYTES // per_elem // world), rank)
+    x = Cm if pos is None else Cm[torch.from_numpy(pos).to(Cm.device)]
+    if torch.is_complex(x):
+        x = torch.view_as_real(x)
+    path = os.path.join(dirname, "C.npy" if world == 1 else f"C_rank{rank}.npy")
+    np.save(path, x.to(torch.float64).cpu().numpy())
+    return path
 
 
 def measured_traffic(alg_bytes: int):
@@ -803,8 +844,8 @@ def kernels_ran(st: dict, steps: int, tname: str) -> dict:
 
 
 def extra_keys(world: int, args):
-    """BASELINE's other configurations, measured after the headline in the same processes: at
-    the GPU counts they are quoted on (cfg 3 at 4 GPUs, cfg 4 and cfg 5 at 8), and at one GPU
+    """BASELINE's other configurations, measured (with --full) after the headline in the same
+    processes: at the GPU counts they are quoted on (cfg 3 at 4 GPUs, cfg 4 and cfg 5 at 8), and at one GPU
     their single-GPU slices, each beside the reference's own CPU rate.
     -> [(entry key, config, edge / op)]"""
     extra_plan = {1: [("cfg3", None), ("cfg4", 32768), ("cfg5", "N"), ("cfg5", "T")],
@@ -815,7 +856,7 @@ def extra_keys(world: int, args):
         for item in args.extra.split(","):
             k, _, e = item.partition(":")
             plan_x.append((k, (int(e) if e.isdigit() else e) if e else None))
-    if args.workload != "pxtran" or args.no_extra:
+    if args.workload != "pxtran" or args.no_extra or not args.full:
         plan_x = []
     keys_x = []
     for kind, edge in plan_x:
@@ -825,15 +866,15 @@ def extra_keys(world: int, args):
 
 
 def spawn_ranks(cmd, args, runner=None) -> int:
-    """The parent of `bench.py --gpus N` (N > 1, no launcher): the reference's multi-rank CPU
-    baselines first (cpu_baseline_multirank, before any rank touches the GPU; their results reach
+    """The parent of `bench.py --gpus N` (N > 1, no launcher): with --full the reference's multi-rank
+    CPU baselines first (cpu_baseline_multirank, before any rank touches the GPU; their results reach
     rank 0 through a file named by COSTA_BENCH_CPU_MR), then the N ranks (run_ranks, or `runner`
     in the tests) -> the ranks' exit code"""
     import tempfile
     runner = runner or run_ranks
     budget = float(os.environ.get("COSTA_BENCH_BUDGET_S", RUN_BUDGET_S))
     path = None
-    if not args.no_cpu_baseline and args.workload == "pxtran":
+    if args.full and not args.no_cpu_baseline and args.workload == "pxtran":
         mr = cpu_baseline_multirank(args.gpus, extra_keys(args.gpus, args))
         fd, path = tempfile.mkstemp(prefix="costa_cpu_mr_", suffix=".json")
         with os.fdopen(fd, "w") as f:
@@ -870,7 +911,18 @@ def main():
     ap.add_argument("--extra", default=None,
                     help="run these extra configs instead of the GPU count's own, e.g. "
                          "'cfg3,cfg4:32768,cfg5:N' (rehearsal of the multi-GPU entries)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the extra configs, blocking and phase-event passes "
+                         "(roofline, copy ceiling), planner comparison, end-to-end legs, call "
+                         "overhead and CPU baselines (--no-cpu-baseline / --no-e2e / --no-extra / "
+                         "--extra select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps save what they left in each rank's local C as "
+                         "DIR/C.npy (DIR/C_rank<r>.npy at N > 1), float64; a fixed seeded sample "
+                         "of positions when C is larger than 32 MiB over the ranks")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # `bench.py --gpus N` with N > 1 and no launcher around it: start the N ranks as a child
     # torch.distributed.run (before anything here touches the GPU), relay rank 0's line
@@ -886,7 +938,9 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "pxtran"
+    full = args.full
+    want_cpu = (full and rank == 0 and world == 1 and not args.no_cpu_baseline
+                and args.workload == "pxtran")
     keys_x = extra_keys(world, args)
     # the reference's own CPU path, as child processes before anything touches the GPU
     if want_cpu:
@@ -897,7 +951,7 @@ def main():
     # (COSTA_BENCH_CPU_MR names its file) or, under an outside launcher, here by rank 0 -- in
     # both cases before this process touches the GPU
     cpu_mr = {}
-    if rank == 0 and world > 1 and not args.no_cpu_baseline and args.workload == "pxtran":
+    if full and rank == 0 and world > 1 and not args.no_cpu_baseline and args.workload == "pxtran":
         path = os.environ.get(CPU_MR_ENV)
         if path and os.path.exists(path):
             cpu_mr = json.load(open(path))
@@ -1069,7 +1123,10 @@ def main():
                       if world == 1 else sampled)
         return w
 
-    def measure(w, steps, warmup, planning_modes=False):
+    def measure(w, steps, warmup, planning_modes=False, full=True, after_value=None):
+        """first call, warm-up, the `steps` timed steps (r["el"], the `value` pass), then
+        after_value() (the outputs of the timed steps are in C) and the correctness check; with
+        `full` also the blocking pass before and the phase-event pass after the value pass"""
         LA, LC, op, al, be = w["LA"], w["LC"], w["op"], w["al"], w["be"]
 
         def step_blocking():
@@ -1126,17 +1183,22 @@ def main():
         r["planning"] = planning
         for _ in range(warmup):
             step_blocking()
-        if w["check"] and w["repeatable"]:  # correctness of what we time
-            verified.append(w["check"]())
-        r["el_block"], _ = timed(step_blocking, profile=False)
+        if full:
+            if w["check"] and w["repeatable"]:  # correctness of what we time
+                verified.append(w["check"]())
+            r["el_block"], _ = timed(step_blocking, profile=False)
         for _ in range(warmup):
             step_async()
         # value: the product as shipped (phase-timing events off: recording them costs ~11 us per
-        # step on cfg 2, tools/step_gap_probe.py); then the same steps again with the events on,
-        # for the kernel durations (roofline.avg_launch_ms, phase_ms_per_step)
+        # step on cfg 2, tools/step_gap_probe.py); with `full` the same steps again with the
+        # events on, for the kernel durations (roofline.avg_launch_ms, phase_ms_per_step)
         r["el"], st_val = timed(step_async, profile=False)
-        r["el_ev"], st = timed(step_async)
-        assert all(st_val[k] == st[k] for k in ("local_bytes", "pack_bytes", "unpack_bytes"))
+        if after_value:
+            after_value()
+        st = st_val
+        if full:
+            r["el_ev"], st = timed(step_async)
+            assert all(st_val[k] == st[k] for k in ("local_bytes", "pack_bytes", "unpack_bytes"))
         if w["check"] and w["repeatable"]:
             verified.append(w["check"]())
         r["verified"] = all(verified) if verified else None
@@ -1151,6 +1213,8 @@ def main():
             total = t.item()
         r["total_bytes"] = total
         r["value"] = total / r["el"] / 1e9
+        if not full:
+            return r
         # SURVEY §8(d) node figure: kernel time only (pack + local + unpack), summed bytes / max t
         kern_ms = (st["local_ms"] + st["pack_ms"] + st["unpack_ms"]) / steps
         r["kern_ms_max"] = max_over_ranks(kern_ms)
@@ -1188,14 +1252,61 @@ def main():
     wmain = build(args.workload)
     phase(rank, f"measure workload {args.workload} (first call, warmup, {args.steps} timed steps)")
     torch.cuda.synchronize()
-    res = measure(wmain, args.steps, args.warmup, planning_modes=world == 1)
-    el, el_block, el_ev, st = res["el"], res["el_block"], res["el_ev"], res["st"]
-    total_bytes, value, kernel_node = res["total_bytes"], res["value"], res["kernel_node"]
+    def dump():  # --dump-outputs: C as the timed steps left it, before any later pass touches it
+        if args.dump_outputs:
+            phase(rank, "dump outputs: " + dump_outputs(args.dump_outputs, wmain["C"], rank, world))
+
+    res = measure(wmain, args.steps, args.warmup, planning_modes=full and world == 1, full=full,
+                  after_value=dump)
+    el, st = res["el"], res["st"]
+    total_bytes, value = res["total_bytes"], res["value"]
     op, al, be, wl = wmain["op"], wmain["al"], wmain["be"], wmain["wl"]
     A, Cm = wmain["A"], wmain["C"]
     n, b = args.edge, args.block
     pm, pn = grid_for(world)
     M, N = wmain.get("m", 0), wmain.get("n", 0)
+
+    def headline():
+        """the head of rank 0's JSON line: what a plain run reports, and --full adds to"""
+        def js(x):  # complex scalars as [re, im]
+            return [x.real, x.imag] if isinstance(x, complex) else x
+        cfg = {"workload": wl, "op": op, "alpha": js(al), "beta": js(be),
+               "parallelism": f"{world} rank(s), one per GPU, RCCL send/recv exchange",
+               "bytes_per_step": int(total_bytes / args.steps)}
+        if args.workload in ("pxtran", "cfg3", "cfg4"):
+            cfg.update({"m": M, "n": N, "block": wmain.get("block", b), "grid": f"{pm}x{pn}"})
+        return {
+            "metric": METRIC,
+            "value": round(value, 2),
+            "unit": "GB/s",
+            "pct_hbm_peak": round(100 * value / (HBM_PEAK_GBPS * world), 2),
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(el / args.steps * 1e3, 4),
+            "higher_is_better": True,
+            "scaling": "strong" if args.workload == "cfg5" else "weak",
+            "vs_baseline": None,
+            "dtype": {"pxtran": "f64", "cfg3": "f64", "cfg4": "c128", "cfg5": "f32"}[args.workload],
+            "data": ("synthetic, device-resident: every element a hash of its global (row, col), "
+                     "uniform on +-[1, 2); checks sample positions bit for bit"),
+            "config": cfg,
+        }
+
+    value_mode = ("costa_hip_transform_async steps, stream-ordered, one sync at the end; "
+                  "phase-timing events off (the shipped default)")
+    if not full:  # a plain run ends here
+        if rank == 0:
+            line = headline()
+            line.update({"verified": res["verified"],
+                         "first_call_ms": round(res["first_call_ms"], 2),  # plan-cache miss
+                         "planning": res["planning"], "value_mode": value_mode, "full": False})
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    el_block, el_ev, kernel_node = res["el_block"], res["el_ev"], res["kernel_node"]
 
     if rank == 0:  # what the watchdog reports should a later phase hang
         _partial_line.update({
@@ -1375,29 +1486,8 @@ def main():
         cpu = cpu_mr["headline"]
 
     if rank == 0:
-        def js(x):  # complex scalars as [re, im]
-            return [x.real, x.imag] if isinstance(x, complex) else x
-        cfg = {"workload": wl, "op": op, "alpha": js(al), "beta": js(be),
-               "parallelism": f"{world} rank(s), one per GPU, RCCL send/recv exchange",
-               "bytes_per_step": int(total_bytes / args.steps)}
-        if args.workload in ("pxtran", "cfg3", "cfg4"):
-            cfg.update({"m": M, "n": N, "block": wmain.get("block", b), "grid": f"{pm}x{pn}"})
-        line = {
-            "metric": METRIC,
-            "value": round(value, 2),
-            "unit": "GB/s",
-            "pct_hbm_peak": round(100 * value / (HBM_PEAK_GBPS * world), 2),
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(el / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "strong" if args.workload == "cfg5" else "weak",
-            "vs_baseline": None,
-            "dtype": {"pxtran": "f64", "cfg3": "f64", "cfg4": "c128", "cfg5": "f32"}[args.workload],
-            "data": ("synthetic, device-resident: every element a hash of its global (row, col), "
-                     "uniform on +-[1, 2); checks sample positions bit for bit"),
-            "config": cfg,
+        line = headline()
+        line.update({
             "roofline": roof,
             "cpu_baseline": cpu,
             "e2e_host": e2e,
@@ -1408,8 +1498,7 @@ def main():
             "blocking": {"ms_per_step": round(el_block / args.steps * 1e3, 4),
                          "GBps": round(total_bytes / el_block / 1e9, 2),
                          "note": "costa_hip_transform (reference semantics: host waits for C)"},
-            "value_mode": ("costa_hip_transform_async steps, stream-ordered, one sync at the end; "
-                           "phase-timing events off (the shipped default)"),
+            "value_mode": value_mode,
             "with_phase_events": {"ms_per_step": round(el_ev / args.steps * 1e3, 4),
                                   "GBps": round(total_bytes / el_ev / 1e9, 2),
                                   "note": "second pass of the same K steps with a HIP event "
@@ -1419,7 +1508,8 @@ def main():
             "rank_kernel_frac_min_max": res["rank_frac"],
             "phase_ms_per_step": {k: round(st[k + "_ms"] / args.steps, 4)
                                   for k in ("pack", "local", "unpack", "exchange")},
-        }
+            "full": True,
+        })
         if extra:
             line["baseline_configs"] = extra
         print(json.dumps(line), flush=True)

@@ -379,7 +379,7 @@ REF_HARNESS = os.path.join(ROOT, "oracle", "_ref", "ref_harness")
                     reason="oracle/_ref/ref_harness (built where /root/reference exists) or MPICH absent")
 @pytest.mark.parametrize("n", [2, 4])
 def test_multirank_cpu_baseline_in_the_parent(n, monkeypatch):
-    """`bench.py --gpus N` (N > 1) runs the reference's multi-rank path
+    """`bench.py --gpus N --full` (N > 1) runs the reference's multi-rank path
     (ref_harness bench_mr under mpiexec -n N) in the spawning parent before the ranks start, and
     hands rank 0 numeric reference baselines: the headline's and each extra config's (cfg 3 at
     N = 4).  The rank launch is stubbed; the samples are shortened to 1 s."""
@@ -387,7 +387,7 @@ def test_multirank_cpu_baseline_in_the_parent(n, monkeypatch):
     import functools
     import json
     args = argparse.Namespace(gpus=n, no_cpu_baseline=False, workload="pxtran", extra=None,
-                              no_extra=False)
+                              no_extra=False, full=True)
     monkeypatch.setattr(bench, "cpu_baseline_multirank",
                         functools.partial(bench.cpu_baseline_multirank, target_s=1.0))
     monkeypatch.setattr(bench, "host_cpus", lambda: (n, {"cpus_usable": n}))
@@ -436,3 +436,53 @@ def test_entries_name_the_kernels_that_ran():
     names = [f for f, _ in costa_amd.Stats._fields_]
     assert names[-6:] == ["tile_items", "skew_items", "cblock_items", "tiny_items", "device_lists",
                           "fused_pieces"]
+
+
+def test_plain_run_skips_what_full_adds():
+    """without --full no extra configuration is planned and the N-rank parent starts no CPU
+    baseline; with it both are as before"""
+    import argparse
+    for world, want in ((1, ["cfg3", "cfg4", "cfg5", "cfg5_T"]), (4, ["cfg3"]), (8, ["cfg4", "cfg5"])):
+        args = argparse.Namespace(workload="pxtran", extra=None, no_extra=False, full=True)
+        assert [k for k, _, _ in bench.extra_keys(world, args)] == want
+        args.full = False
+        assert bench.extra_keys(world, args) == []
+        args.extra = "cfg3,cfg5:N"  # an explicit list is part of --full too
+        assert bench.extra_keys(world, args) == []
+    args = argparse.Namespace(gpus=2, no_cpu_baseline=False, workload="pxtran", extra=None,
+                              no_extra=False, full=False)
+    assert bench.spawn_ranks(["ranks"], args, runner=lambda cmd, budget, gpus: 7) == 7
+    assert bench.CPU_MR_ENV not in os.environ
+
+
+def test_dump_positions_fixed_and_bounded():
+    """--dump-outputs: a C that fits is saved whole; a larger one at the same sorted positions in
+    every run, its own per rank"""
+    assert bench.dump_positions(1000, 1000) is None
+    p = bench.dump_positions(1 << 28, 4096)
+    assert p.dtype == np.int64 and p.shape == (4096,)
+    assert bool((np.diff(p) >= 0).all()) and 0 <= p[0] and p[-1] < 1 << 28
+    assert np.array_equal(p, bench.dump_positions(1 << 28, 4096))
+    assert not np.array_equal(p, bench.dump_positions(1 << 28, 4096, rank=1))
+    # the headline's C (16384^2 fp64) stays within the byte budget
+    assert (bench.DUMP_BYTES // 8) * 8 <= 64 << 20
+
+
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32, torch.complex128])
+def test_dump_outputs_writes_float64(tmp_path, dtype, monkeypatch):
+    t = bench.pos_values(torch.arange(300)[:, None], torch.arange(70)[None, :], bench.SEED_A,
+                         {torch.float64: "f64", torch.float32: "f32",
+                          torch.complex128: "c128"}[dtype]).reshape(-1)
+    path = bench.dump_outputs(str(tmp_path / "d"), t, 0, 1)
+    assert path == str(tmp_path / "d" / "C.npy")
+    got = np.load(path)
+    assert got.dtype == np.float64
+    want = torch.view_as_real(t).numpy() if t.is_complex() else t.numpy()
+    assert got.shape == want.shape and np.array_equal(got, want.astype(np.float64))
+    # a C over the budget: the sampled positions, one file per rank at N > 1
+    monkeypatch.setattr(bench, "DUMP_BYTES", 16 * 1000)
+    path = bench.dump_outputs(str(tmp_path / "d"), t, 1, 2)
+    assert path.endswith("C_rank1.npy")
+    per = 16 if t.is_complex() else 8
+    pos = bench.dump_positions(t.numel(), 16 * 1000 // per // 2, 1)
+    assert np.array_equal(np.load(path), want[pos].astype(np.float64))

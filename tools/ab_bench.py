@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B of bench.py lines under several environment settings, alternating, each in a fresh process
+"""A/B of `bench.py --full` lines (the roofline fields come with --full) under several environment settings, alternating, each in a fresh process
 (one process = one placement of the buffers; see DESIGN §5 on process-to-process spread).
 
     python3 tools/ab_bench.py OUT REPS 'label:ENV=V,ENV=V' ... -- <bench.py args>
@@ -29,7 +29,7 @@ def main():
     for r in range(reps):
         for label, env in settings:
             e = dict(os.environ, **env)
-            p = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.join(root, "bench.py"),
+            p = subprocess.run(["timeout", "-k", "10", "300", sys.executable, os.path.join(root, "bench.py"), "--full",
                                 *bench_args], capture_output=True, text=True, env=e)
             with open(os.path.join(out, f"{label}_{r}.err"), "w") as f:
                 f.write(p.stderr[-20000:])

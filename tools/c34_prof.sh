@@ -11,9 +11,9 @@ export TMPDIR=/tmp
 run() {  # name alg-bytes bench-args...
   local n=$1 alg=$2
   shift 2
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_$n -o trace --output-format csv -- python3 bench.py "$@" --steps 5 --warmup 2 --no-cpu-baseline --no-e2e --no-extra > $O/prof_$n.log 2>&1 || exit 1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_$n -o trace --output-format csv -- python3 bench.py --full "$@" --steps 5 --warmup 2 --no-cpu-baseline --no-e2e --no-extra > $O/prof_$n.log 2>&1 || exit 1
   for c in FETCH_SIZE WRITE_SIZE; do
-    timeout -s KILL 200 rocprofv3 --pmc $c -d $O/pmc_${n}_$c -o p --output-format csv -- python3 bench.py "$@" --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --no-extra > $O/pmc_${n}_$c.log 2>&1 || exit 1
+    timeout -s KILL 200 rocprofv3 --pmc $c -d $O/pmc_${n}_$c -o p --output-format csv -- python3 bench.py --full "$@" --steps 2 --warmup 1 --no-cpu-baseline --no-e2e --no-extra > $O/pmc_${n}_$c.log 2>&1 || exit 1
     python3 tools/pmc_brief.py $O/pmc_${n}_$c $alg >> $O/summary_$n.txt 2>&1
   done
 }
