@@ -29,7 +29,8 @@ import numpy as np
 __all__ = [
     "CostaError", "lib", "FLOAT", "DOUBLE", "CFLOAT", "CDOUBLE", "INT32", "dtype_code",
     "np_dtype", "Layout", "block_cyclic_layout", "custom_layout", "Comm", "transform",
-    "transform_batch", "transform_async", "transform_batch_async", "synchronize", "transformer", "copy_and_transform", "execute_tiles", "TileOp",
+    "transform_batch", "transform_async", "transform_batch_async", "synchronize", "transformer", "copy_and_transform", "execute_tiles", "execute_tiles_mixed",
+    "convert_subtile", "TileOp",
     "plan_export", "set_profiling", "get_stats", "release_caches", "TILE_OP_DTYPE",
 ]
 
@@ -103,7 +104,19 @@ class Stats(C.Structure):
                 ("fused_pieces", C.c_int64)]
 
     def as_dict(self) -> dict:
-        return {k: getattr(self, k) for k, _ in self._fields_}
+        # (a ctypes subclass lists only the fields it appends: walk the bases first)
+        out = {}
+        for cls in reversed(type(self).__mro__):
+            for k, _ in cls.__dict__.get("_fields_", ()):
+                out[k] = getattr(self, k)
+        return out
+
+
+class FullStats(Stats):
+    """costa_stats_t as the library fills it: ``Stats`` is its prefix, counters added since are
+    appended here in the order of include/costa_hip.h (convert_items: sub-tiles run by the
+    converting kernels of mixed-precision transforms)."""
+    _fields_ = [("convert_items", C.c_int64)]
 
 
 # COSTA_LIB: another build of the library (A/B runs against a tuning build of the sources)
@@ -156,10 +169,12 @@ def lib():
         "costa_hip_rccl_version": (i, [C.POINTER(i)]),
         "costa_hip_copy_and_transform": (i, [i, i, i, vp, i, i, vp, i, i, i, i, vp, vp]),
         "costa_hip_execute_tiles": (i, [i, C.POINTER(TileOp), i64, vp, vp, vp, i, i]),
+        "costa_hip_execute_tiles_mixed": (i, [i, i, C.POINTER(TileOp), i64, vp, vp, vp, i, i]),
+        "costa_hip_convert_subtile": (i, [i, i, C.POINTER(i), C.POINTER(i)]),
         "costa_hip_plan_export": (i, [i, C.POINTER(vp), C.POINTER(vp), C.c_char_p, vp, vp, i, i,
                                       C.POINTER(PlanInfo), vp, vp, vp, vp, vp, vp, vp, vp]),
         "costa_hip_set_profiling": (i, [i]),
-        "costa_hip_get_stats": (i, [C.POINTER(Stats), i]),
+        "costa_hip_get_stats": (i, [C.POINTER(FullStats), i]),
         "costa_hip_release_caches": (i, []),
         "costa_hip_set_host_staging": (i, [i]),
         "costa_hip_set_planner": (i, [i]),
@@ -353,7 +368,11 @@ class Comm:
 
 # ------------------------------------------------------------------ transforms
 def transform(A: Layout, Cl: Layout, comm: Comm, trans: str = "N", alpha=1, beta=0):
-    """sub(C) = beta*sub(C) + alpha*op(sub(A)) (reference transform.hpp:13-27)."""
+    """sub(C) = beta*sub(C) + alpha*op(sub(A)) (reference transform.hpp:13-27).
+
+    A and C may differ in dtype (FLOAT <-> DOUBLE, CFLOAT <-> CDOUBLE; device-resident layouts):
+    sub(A) is converted to C's type inside the tile kernels, and alpha / beta are of C's type
+    (costa_hip.h, "Mixed precision")."""
     transform_batch([A], [Cl], comm, [trans], [alpha], [beta])
 
 
@@ -362,7 +381,7 @@ def transform_batch(As: Sequence[Layout], Cs: Sequence[Layout], comm: Comm,
     """Several layout pairs in one exchange (reference transform.hpp:38-43)."""
     n = len(As)
     assert n == len(Cs) and n > 0
-    code = As[0].dtype
+    code = Cs[0].dtype  # alpha / beta are elements of C's type
     trans = list(trans) if trans is not None else ["N"] * n
     alpha = list(alpha) if alpha is not None else [1] * n
     beta = list(beta) if beta is not None else [0] * n
@@ -382,7 +401,7 @@ def transform_async(A: Layout, Cl: Layout, comm: Comm, trans: str = "N", alpha=1
 
 def transform_batch_async(As, Cs, comm: Comm, trans=None, alpha=None, beta=None, stream=None):
     n = len(As)
-    code = As[0].dtype
+    code = Cs[0].dtype  # alpha / beta are elements of C's type
     trans = list(trans) if trans is not None else ["N"] * n
     alpha = list(alpha) if alpha is not None else [1] * n
     beta = list(beta) if beta is not None else [0] * n
@@ -450,6 +469,30 @@ def execute_tiles(dtype, ops: np.ndarray, scalars: np.ndarray, src_base=0, dst_b
                                          sc.ctypes.data, sc.size // 2, device))
 
 
+def execute_tiles_mixed(src_dtype, dst_dtype, ops: np.ndarray, scalars: np.ndarray, src_base=0,
+                        dst_base=0, device: int = 0):
+    """Run a list of converting tile ops (sources of ``src_dtype``, destinations of ``dst_dtype``:
+    FLOAT <-> DOUBLE or CFLOAT <-> CDOUBLE) in one batched launch; ``scalars`` are of
+    ``dst_dtype`` (costa_hip_execute_tiles_mixed)."""
+    sc_, dc_ = dtype_code(src_dtype), dtype_code(dst_dtype)
+    ops = np.ascontiguousarray(ops, dtype=TILE_OP_DTYPE)
+    sc = np.ascontiguousarray(scalars, dtype=_NP[dc_]).reshape(-1)
+    assert sc.size % 2 == 0
+    _check(lib().costa_hip_execute_tiles_mixed(sc_, dc_, ops.ctypes.data_as(C.POINTER(TileOp)),
+                                               ops.size, C.c_void_p(_ptr(src_base)),
+                                               C.c_void_p(_ptr(dst_base)), sc.ctypes.data,
+                                               sc.size // 2, device))
+
+
+def convert_subtile(src_dtype, dst_dtype) -> tuple:
+    """(BF, BS): the sub-tile of the converting kernels for a mixed pair, in elements along the
+    source's fast and slow dimension (one workgroup each)."""
+    bf, bs = C.c_int(0), C.c_int(0)
+    _check(lib().costa_hip_convert_subtile(dtype_code(src_dtype), dtype_code(dst_dtype),
+                                           C.byref(bf), C.byref(bs)))
+    return bf.value, bs.value
+
+
 @dataclass
 class Plan:
     local_ops: np.ndarray
@@ -470,7 +513,7 @@ def plan_export(As: Sequence[Layout], Cs: Sequence[Layout], rank: int, nranks: i
     """Tile-op lists of `rank`: by the host planner (never touches a GPU), or with ``device``
     set by the GPU planner of that device (costa_hip_plan_export_device)."""
     n = len(As)
-    code = As[0].dtype
+    code = Cs[0].dtype  # alpha / beta are elements of C's type
     trans = list(trans) if trans is not None else ["N"] * n
     alpha = list(alpha) if alpha is not None else [1] * n
     beta = list(beta) if beta is not None else [0] * n
@@ -505,7 +548,7 @@ def set_profiling(on: bool = True):
 
 
 def get_stats(reset: bool = False) -> dict:
-    s = Stats()
+    s = FullStats()
     _check(lib().costa_hip_get_stats(C.byref(s), int(reset)))
     return s.as_dict()
 

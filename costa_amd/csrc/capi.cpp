@@ -96,7 +96,7 @@ void check_handles(int n, const costa_layout_t* A, const costa_layout_t* C) {
 std::vector<job> make_jobs(int n, const costa_layout_t* A, const costa_layout_t* C,
                            const char* trans, const void* alpha, const void* beta) {
     check_handles(n, A, C);
-    const costa_dtype_t t = A[0]->e.dtype;
+    const costa_dtype_t t = C[0]->e.dtype;  // alpha / beta are elements of C's type
     const size_t E = dtype_size(t);
     std::vector<job> jobs(static_cast<size_t>(n));
     for (int i = 0; i < n; ++i) {
@@ -352,6 +352,24 @@ int costa_hip_execute_tiles(costa_dtype_t dtype, const costa_tile_op_t* ops, int
     });
 }
 
+int costa_hip_execute_tiles_mixed(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
+                                  const costa_tile_op_t* ops, int64_t n, const void* src_base,
+                                  void* dst_base, const void* scalars, int n_slots, int device) {
+    return gpu_guarded([&] {
+        if (n < 0 || (n > 0 && (!ops || !scalars)))
+            throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::execute_tiles_mixed(src_dtype, dst_dtype, ops, n, src_base, dst_base, scalars,
+                                           n_slots, device);
+    });
+}
+
+int costa_hip_convert_subtile(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, int* bf, int* bs) {
+    return guarded([&] {
+        if (!bf || !bs) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::convert_subtile(src_dtype, dst_dtype, bf, bs);
+    });
+}
+
 int costa_hip_plan_export(int n, const costa_layout_t* A, const costa_layout_t* C,
                           const char* trans, const void* alpha, const void* beta, int rank,
                           int nranks, costa_plan_info_t* info, costa_tile_op_t* local_ops,
@@ -511,6 +529,43 @@ void transform(std::vector<layout_ref<T>>& from, std::vector<layout_ref<T>>& to,
                const T* alpha, const T* beta, costa_comm_t comm) {
     run<T>(from, to, trans, alpha, beta, comm);
 }
+
+// mixed precision: one (A, C) pair, scalars of C's type
+template <typename Ta, typename Tc>
+void run_mixed(grid_layout<Ta>& A, grid_layout<Tc>& C, char trans, Tc alpha, Tc beta,
+               costa_comm_t comm) {
+    raise(gpu_guarded([&] {
+        if (!comm) throw engine::error(COSTA_ERR_ARG, "costa::transform: null communicator");
+        engine::elayout a = engine::erase(A), c = engine::erase(C);
+        engine::job jb;
+        jb.A = &a;
+        jb.C = &c;
+        jb.trans = trans;
+        jb.s = scal_of(alpha, beta);
+        engine::transform({jb}, comm->c);
+    }));
+}
+
+template <typename Ta, typename Tc>
+typename std::enable_if<!std::is_same<Ta, Tc>::value>::type
+transform(grid_layout<Ta>& A, grid_layout<Tc>& C, costa_comm_t comm) {
+    run_mixed<Ta, Tc>(A, C, 'N', Tc{1}, Tc{0}, comm);
+}
+
+template <typename Ta, typename Tc>
+typename std::enable_if<!std::is_same<Ta, Tc>::value>::type
+transform(grid_layout<Ta>& A, grid_layout<Tc>& C, char trans, Tc alpha, Tc beta, costa_comm_t comm) {
+    run_mixed<Ta, Tc>(A, C, trans, alpha, beta, comm);
+}
+
+#define COSTA_INSTANTIATE_MIXED(Ta, Tc)                                                         \
+    template void transform<Ta, Tc>(grid_layout<Ta>&, grid_layout<Tc>&, costa_comm_t);          \
+    template void transform<Ta, Tc>(grid_layout<Ta>&, grid_layout<Tc>&, char, Tc, Tc, costa_comm_t);
+
+COSTA_INSTANTIATE_MIXED(double, float)
+COSTA_INSTANTIATE_MIXED(float, double)
+COSTA_INSTANTIATE_MIXED(std::complex<double>, std::complex<float>)
+COSTA_INSTANTIATE_MIXED(std::complex<float>, std::complex<double>)
 
 #define COSTA_INSTANTIATE_TRANSFORM(T)                                                          \
     template void transform<T>(grid_layout<T>&, grid_layout<T>&, costa_comm_t);                 \

@@ -314,8 +314,11 @@ std::unique_ptr<plan> make_plan_device(const std::vector<job>& jobs, int rank, i
                    std::chrono::steady_clock::now().time_since_epoch()).count();
     };
     const double t0 = now();
+    // mixed-precision pairs are planned on the host (whose checks also report unsupported pairs)
+    if (any_mixed(jobs)) return nullptr;
     auto p = std::make_unique<plan>();
     const std::vector<job_params> prm = check_jobs(jobs, n_ranks, p->dtype);
+    p->src_dtype = p->pkg_dtype = p->dtype;
     const uint64_t E = dtype_size(p->dtype);
 
     // ---- host: merged grids and tables, O(split points + blocks) ----

@@ -287,7 +287,7 @@ size_t peer_of(const std::vector<int64_t>& displs, int64_t o) {
 
 void exchange_round_of_ops(const plan& p, int rounds, std::vector<int>& pack_round,
                            std::vector<int>& unpack_round) {
-    const size_t E = dtype_size(p.dtype);
+    const size_t E = dtype_size(p.pkg_dtype);  // package offsets are in package elements
     pack_round.clear();
     unpack_round.clear();
     for (const auto& op : p.pack_ops) {
@@ -1748,10 +1748,14 @@ struct cached_plan {
     dbuf d_local, w_local, d_scal;
     work_split l_local;                     // how the work list splits over the kernel shapes
     bool tr_local = true, ax_local = true;  // any op of the list transposes / reads C
+    // converting lists of a mixed-precision plan (convert_kernels.hip) have a convert_list instead
+    // of a work_split: LOCAL; PACK of a narrowing pair; UNPACK of a widening pair
+    convert_list c_local;
     struct xround {  // one exchange round: its pack ops (by their first element) and unpack
                      // ops (by their last element)
         dbuf d_pack, w_pack, d_unpack, w_unpack;
         work_split l_pack, l_unpack;
+        convert_list c_pack, c_unpack;
         bool tr_unpack = false, ax_unpack = false;
     };
     std::vector<std::unique_ptr<xround>> rounds;
@@ -1934,7 +1938,7 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
         uint64_t w = uint64_t(uint8_t(std::toupper(static_cast<unsigned char>(j.trans))));
         // the scale kinds (not the values) are baked into the ops
         for (bool cm : {true, false})
-            w = w << 8 | scale_kind(j.A->dtype, j.s, cm, std::toupper(j.trans) == 'C');
+            w = w << 8 | scale_kind(j.C->dtype, j.s, cm, std::toupper(j.trans) == 'C');
         key.push_back(w);
     }
     hasher h;
@@ -1956,6 +1960,11 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
     const double t0 = now();
     double t_resid = 0, t_plan = 0, t_work = 0;
 
+    const bool mixed = any_mixed(jobs);
+    if (mixed) {  // an unsupported pair is reported as such, whatever the residency
+        costa_dtype_t a, b;
+        check_jobs(jobs, c->size, a, b);
+    }
     auto cp = std::make_unique<cached_plan>();
     cp->device = c->device;
     // residency: all device, or stage the host-resident layouts
@@ -1972,6 +1981,10 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
     std::vector<job> pj = jobs;
     std::vector<hrange> staged_ranges;
     std::vector<uint8_t> range_flags;
+    if (!all_dev && mixed)
+        throw error(COSTA_ERR_ARG,
+                    "costa: mixed-precision transforms (A and C of different element types) need "
+                    "device-resident layouts");
     if (!all_dev) {
         cp->staged = true;
         std::vector<const elayout*> As, Cs;
@@ -2107,7 +2120,14 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
         return d;
     };
     device_section sec_l = section();
-    cp->l_local = build_work(p.dtype, p.local_ops, ord_l, w_l, list_local, &sec_l);
+    // (a mixed plan's LOCAL list converts; its package holds the narrower type, so PACK converts
+    // for narrowing pairs and UNPACK for widening ones, the other being a same-type list)
+    const bool cv_pack = p.mixed() && p.pkg_dtype != p.src_dtype;
+    const bool cv_unpack = p.mixed() && p.pkg_dtype != p.dtype;
+    if (p.mixed())
+        cp->c_local = build_convert_work(p.src_dtype, p.dtype, p.local_ops, 0, 0, ord_l, w_l);
+    else
+        cp->l_local = build_work(p.dtype, p.local_ops, ord_l, w_l, list_local, &sec_l);
     // exchange rounds: pack ops go to the round of their first element (every element a round
     // sends is packed by then), unpack ops to the round of their last (every element they read
     // has arrived)
@@ -2126,9 +2146,18 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
         auto x = std::make_unique<cached_plan::xround>();
         x->tr_unpack = any_transpose(up[size_t(r)]);
         x->ax_unpack = any_axpby(up[size_t(r)]);
-        x->l_pack = build_work(p.dtype, pk[size_t(r)], ord_p[size_t(r)], w_p[size_t(r)], list_pack);
-        x->l_unpack = build_work(p.dtype, up[size_t(r)], ord_u[size_t(r)], w_u[size_t(r)], list_unpack,
-                                 &sec_u[size_t(r)]);
+        // (package offsets are relative to the 256-byte aligned send / receive buffers)
+        if (cv_pack)
+            x->c_pack = build_convert_work(p.src_dtype, p.pkg_dtype, pk[size_t(r)], 0, 0, ord_p[size_t(r)],
+                                           w_p[size_t(r)]);
+        else
+            x->l_pack = build_work(p.pkg_dtype, pk[size_t(r)], ord_p[size_t(r)], w_p[size_t(r)], list_pack);
+        if (cv_unpack)
+            x->c_unpack = build_convert_work(p.pkg_dtype, p.dtype, up[size_t(r)], 0, 0, ord_u[size_t(r)],
+                                             w_u[size_t(r)]);
+        else
+            x->l_unpack = build_work(p.dtype, up[size_t(r)], ord_u[size_t(r)], w_u[size_t(r)], list_unpack,
+                                     &sec_u[size_t(r)]);
         cp->rounds.push_back(std::move(x));
     }
     t_work = now() - t0 - t_resid - t_plan;
@@ -2267,7 +2296,7 @@ namespace {
 // Round `round` of `rounds` (exchange_rounds(); rounds = 1: everything at once).
 void issue_exchange(comm* c, const plan& p, char* sb, char* rb, hipStream_t s, int round = 0,
                     int rounds = 1) {
-    const size_t E = dtype_size(p.dtype);
+    const size_t E = dtype_size(p.pkg_dtype);
     const size_t piece = max_message_bytes();
     NCCL_CHECK(ncclGroupStart());
     for (int q = 0; q < c->size; ++q) {
@@ -2292,7 +2321,7 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
     device_ctx& dc = ctx(c->device);
     cached_plan& cp = *get_plan(jobs, c, dc);
     const plan& p = *cp.p;
-    const size_t E = dtype_size(p.dtype);
+    const size_t E = dtype_size(p.pkg_dtype);  // of the send / receive packages
     if (async && (cp.staged || cp.pipe))
         throw error(COSTA_ERR_ARG,
                     "costa: asynchronous transforms need device-resident layouts (host data is "
@@ -2345,6 +2374,13 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
         HIP_CHECK(hipEventRecord(dc.ev_ready, dc.main));
         HIP_CHECK(hipStreamWaitEvent(dc.aux, dc.ev_ready, 0));
     }
+    if (cp.c_local.n_items) {
+        tm.start(PH_LOCAL, ls);
+        launch_convert(p.src_dtype, p.dtype, static_cast<const costa_tile_op_t*>(cp.d_local.p),
+                       static_cast<const uint64_t*>(cp.w_local.p), cp.c_local, nullptr, nullptr,
+                       cp.d_scal.p, ls);
+        tm.stop();
+    }
     if (cp.l_local.n_items()) {
         tm.start(PH_LOCAL, ls);
         launch_tiles(p.dtype,
@@ -2365,9 +2401,16 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
         dc.round_events(size_t(R));
         for (int r = 0; r < R; ++r) {
             const auto& x = *cp.rounds[size_t(r)];
+            if (x.c_pack.n_items) {
+                tm.start(PH_PACK, dc.main);
+                launch_convert(p.src_dtype, p.pkg_dtype, static_cast<const costa_tile_op_t*>(x.d_pack.p),
+                               static_cast<const uint64_t*>(x.w_pack.p), x.c_pack, nullptr, sb,
+                               cp.d_scal.p, dc.main);
+                tm.stop();
+            }
             if (x.l_pack.n_items()) {
                 tm.start(PH_PACK, dc.main);
-                launch_tiles(p.dtype,
+                launch_tiles(p.pkg_dtype,
                              make_launch(x.l_pack, x.d_pack.p, x.w_pack.p, nullptr, sb, cp.d_scal.p,
                                          false, false),
                              dc.main);
@@ -2382,6 +2425,14 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
         }
         for (int r = 0; r < R; ++r) {
             const auto& x = *cp.rounds[size_t(r)];
+            if (x.c_unpack.n_items) {
+                HIP_CHECK(hipStreamWaitEvent(dc.aux, dc.ev_moved[size_t(r)], 0));
+                tm.start(PH_UNPACK, dc.aux);
+                launch_convert(p.pkg_dtype, p.dtype, static_cast<const costa_tile_op_t*>(x.d_unpack.p),
+                               static_cast<const uint64_t*>(x.w_unpack.p), x.c_unpack, rb, nullptr,
+                               cp.d_scal.p, dc.aux);
+                tm.stop();
+            }
             if (!x.l_unpack.n_items()) continue;
             HIP_CHECK(hipStreamWaitEvent(dc.aux, dc.ev_moved[size_t(r)], 0));
             tm.start(PH_UNPACK, dc.aux);
@@ -2416,17 +2467,19 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
         if (!dtype_is_complex(p.dtype) && pieces_in_group_launch(w.n_cblock, w.n_tiny))
             g_stats.fused_pieces += w.n_tiny;
     };
-    if (cp.l_local.n_items()) {
+    if (cp.l_local.n_items() || cp.c_local.n_items) {
         g_stats.local_launches++;
         g_stats.local_bytes += p.local_bytes;
         count_items(cp.l_local);
+        g_stats.convert_items += cp.c_local.n_items;
     }
     if (exchange) {
         for (const auto& x : cp.rounds) {
-            g_stats.pack_launches += x->l_pack.n_items() ? 1 : 0;
-            g_stats.unpack_launches += x->l_unpack.n_items() ? 1 : 0;
+            g_stats.pack_launches += x->l_pack.n_items() || x->c_pack.n_items ? 1 : 0;
+            g_stats.unpack_launches += x->l_unpack.n_items() || x->c_unpack.n_items ? 1 : 0;
             count_items(x->l_pack);
             count_items(x->l_unpack);
+            g_stats.convert_items += x->c_pack.n_items + x->c_unpack.n_items;
         }
         g_stats.pack_bytes += p.pack_bytes;
         g_stats.unpack_bytes += p.unpack_bytes;
@@ -2470,6 +2523,37 @@ void execute_tiles(costa_dtype_t dtype, const costa_tile_op_t* ops, int64_t n,
                              any_axpby(v)),
                  dc.main);
     HIP_CHECK(hipStreamSynchronize(dc.main));
+}
+
+void execute_tiles_mixed(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_tile_op_t* ops,
+                         int64_t n, const void* src_base, void* dst_base, const void* scalars,
+                         int n_slots, int device) {
+    std::lock_guard<std::recursive_mutex> lk(g_mutex);
+    if (!convertible(src_dtype, dst_dtype))
+        throw error(COSTA_ERR_ARG, std::string("costa_hip_execute_tiles_mixed: cannot convert ") +
+                                       dtype_name(src_dtype) + " to " + dtype_name(dst_dtype) +
+                                       " (FLOAT <-> DOUBLE and CFLOAT <-> CDOUBLE only)");
+    device_ctx& dc = ctx(device);
+    std::vector<costa_tile_op_t> v(ops, ops + n);
+    for (const auto& op : v)
+        if ((op.flags >> COSTA_SLOT_SHIFT) >= uint32_t(std::max(n_slots, 0)))
+            throw error(COSTA_ERR_ARG, "costa_hip_execute_tiles_mixed: scalar slot out of range");
+    std::vector<costa_tile_op_t> ord;
+    std::vector<uint64_t> w;
+    const convert_list l = build_convert_work(src_dtype, dst_dtype, v, reinterpret_cast<uintptr_t>(src_base),
+                                              reinterpret_cast<uintptr_t>(dst_base), ord, w);
+    dbuf d_ops, d_work, d_scal;
+    d_ops.upload(ord, dc.main);
+    d_work.upload(w, dc.main);
+    const size_t E = dtype_size(dst_dtype);
+    std::vector<unsigned char> sc(static_cast<const unsigned char*>(scalars),
+                                  static_cast<const unsigned char*>(scalars) + size_t(n_slots) * 2 * E);
+    d_scal.upload(sc, dc.main);
+    launch_convert(src_dtype, dst_dtype, static_cast<const costa_tile_op_t*>(d_ops.p),
+                   static_cast<const uint64_t*>(d_work.p), l, static_cast<const char*>(src_base),
+                   static_cast<char*>(dst_base), d_scal.p, dc.main);
+    HIP_CHECK(hipStreamSynchronize(dc.main));
+    g_stats.convert_items += l.n_items;
 }
 
 void copy_and_transform(costa_dtype_t dtype, int n_rows, int n_cols, const void* src,

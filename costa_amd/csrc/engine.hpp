@@ -70,7 +70,14 @@ struct job {
 // The three tile-op lists of one rank plus the exchange geometry.  Addresses of pack
 // destinations and unpack sources are byte offsets into the send / receive buffers.
 struct plan {
-    costa_dtype_t dtype = COSTA_DOUBLE;
+    costa_dtype_t dtype = COSTA_DOUBLE;      // C's element type: the scalars and all arithmetic
+    // Mixed-precision plans (A's type differs from C's): local ops read src_dtype and write dtype;
+    // the package holds pkg_dtype, the narrower of the two, so the converting list is PACK
+    // (src_dtype -> pkg_dtype) for narrowing pairs and UNPACK (pkg_dtype -> dtype) for widening
+    // ones, and the other list is a same-type list.  Same-type plans: all three equal.
+    costa_dtype_t src_dtype = COSTA_DOUBLE;  // A's element type
+    costa_dtype_t pkg_dtype = COSTA_DOUBLE;  // element type of the send / receive packages
+    bool mixed() const { return src_dtype != dtype; }
     int rank = 0, n_ranks = 1;
     std::vector<costa_tile_op_t> local_ops, pack_ops, unpack_ops;
     std::vector<int64_t> send_counts, send_displs, recv_counts, recv_displs;  // elements
@@ -86,6 +93,14 @@ struct job_params {
     uint32_t kind_copy, kind_tr;  // scale kind of ops that copy / transpose
 };
 std::vector<job_params> check_jobs(const std::vector<job>& jobs, int n_ranks, costa_dtype_t& dtype);
+// the same for batches whose A and C may differ in element type: every job shares one
+// (A dtype, C dtype) pair, equal or one of FLOAT <-> DOUBLE, CFLOAT <-> CDOUBLE; the scale kinds
+// are evaluated in C's type
+std::vector<job_params> check_jobs(const std::vector<job>& jobs, int n_ranks,
+                                   costa_dtype_t& src_dtype, costa_dtype_t& dst_dtype);
+const char* dtype_name(costa_dtype_t t);
+// whether some job of the batch converts (A's element type differs from C's)
+bool any_mixed(const std::vector<job>& jobs);
 
 // Build the plan of `rank` (of `n_ranks`) for a batch of jobs (host only).  `loopback` (test
 // mode, see loopback_exchange()): 1 = the rank's own tiles all go through pack -> exchange with
@@ -129,6 +144,10 @@ int exchange_rounds();
 costa_tile_op_t make_tile_op(int n_rows, int n_cols, uint64_t src, int src_stride, bool src_cm,
                              uint64_t dst, int dst_stride, bool dst_cm, bool transpose, bool conj,
                              uint32_t scale_kind, uint32_t slot, size_t elem);
+// ... of a converting op (source and destination element sizes differ)
+costa_tile_op_t make_tile_op(int n_rows, int n_cols, uint64_t src, int src_stride, bool src_cm,
+                             uint64_t dst, int dst_stride, bool dst_cm, bool transpose, bool conj,
+                             uint32_t scale_kind, uint32_t slot, size_t src_elem, size_t dst_elem);
 
 // scale kind of (alpha, beta) for `dtype` with the reference's branch rules
 uint32_t scale_kind(costa_dtype_t dtype, const scal& s, bool copy_mode, bool conj);
@@ -158,6 +177,31 @@ void copy_and_transform(costa_dtype_t dtype, int n_rows, int n_cols, const void*
 void execute_tiles(costa_dtype_t dtype, const costa_tile_op_t* ops, int64_t n,
                    const void* src_base, void* dst_base, const void* scalars, int n_slots,
                    int device);
+// a list of converting ops (src_dtype != dst_dtype, a supported pair); scalars in dst_dtype
+void execute_tiles_mixed(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_tile_op_t* ops,
+                         int64_t n, const void* src_base, void* dst_base, const void* scalars,
+                         int n_slots, int device);
+
+// ---- converting lists (convert_kernels.hip): dst = g(static_cast<dst type>(src)) ----
+// One kernel family, one workgroup per sub-tile of one op; the work items are
+// (op index << 32) | sub-tile, as for tile_kernel, in list order.  Scale kind BITCOPY of a
+// converting op means "convert only".
+// the sub-tile of a pair: elements along the source's fast (*bf) and slow (*bs) dimension
+void convert_subtile(costa_dtype_t src, costa_dtype_t dst, int* bf, int* bs);
+struct convert_list {
+    int64_t n_items = 0;
+    bool any_transpose = false;
+};
+bool convertible(costa_dtype_t src, costa_dtype_t dst);  // FLOAT <-> DOUBLE, CFLOAT <-> CDOUBLE
+// the work list of a converting list: `ordered` = the ops with each side's VEC flag set from its
+// actual address (base + offset) and element size, `work` = every sub-tile of every op
+convert_list build_convert_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
+                                const std::vector<costa_tile_op_t>& ops, uint64_t src_base,
+                                uint64_t dst_base, std::vector<costa_tile_op_t>& ordered,
+                                std::vector<uint64_t>& work);
+void launch_convert(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_tile_op_t* d_ops,
+                    const uint64_t* d_work, const convert_list& l, const char* src_base,
+                    char* dst_base, const void* d_scalars, void* stream /* hipStream_t */);
 
 // kernel launcher (tile_kernels.hip); `work` and `ops` are device arrays
 // ops small enough for one wavefront each (tiny path): copy mode up to kTinyCopyBytes of

@@ -22,6 +22,7 @@
 #include <complex>
 #include <cstring>
 #include <exception>
+#include <string>
 #include <thread>
 
 namespace costa {
@@ -39,6 +40,23 @@ size_t dtype_size(costa_dtype_t t) {
 }
 
 bool dtype_is_complex(costa_dtype_t t) { return t == COSTA_CFLOAT || t == COSTA_CDOUBLE; }
+
+const char* dtype_name(costa_dtype_t t) {
+    switch (t) {
+    case COSTA_FLOAT: return "FLOAT";
+    case COSTA_DOUBLE: return "DOUBLE";
+    case COSTA_CFLOAT: return "CFLOAT";
+    case COSTA_CDOUBLE: return "CDOUBLE";
+    case COSTA_INT32: return "INT32";
+    }
+    return "unknown";
+}
+
+bool any_mixed(const std::vector<job>& jobs) {
+    for (const job& jb : jobs)
+        if (jb.A && jb.C && jb.A->dtype != jb.C->dtype) return true;
+    return false;
+}
 
 template <> costa_dtype_t dtype_of<float>() { return COSTA_FLOAT; }
 template <> costa_dtype_t dtype_of<double>() { return COSTA_DOUBLE; }
@@ -130,8 +148,9 @@ struct view {
 
 // decompose every local block of `src` (seen through `sv`) by the grid of `dst` (seen
 // through `dv`) and append the tiles (utils.hpp:26-115)
-void decompose(const view& sv, const view& dv, int tag, size_t elem, std::vector<side_tile>& out) {
+void decompose(const view& sv, const view& dv, int tag, std::vector<side_tile>& out) {
     out.reserve(out.size() + sv.L->blocks.size() * 4);
+    const size_t elem = dtype_size(sv.L->dtype);  // of the layout being decomposed
     const auto& drs = dv.rsplit();
     const auto& dcs = dv.csplit();
     if (sv.rsplit().back() != drs.back() || sv.csplit().back() != dcs.back())
@@ -200,15 +219,48 @@ costa_tile_op_t make_tile_op(int n_rows, int n_cols, uint64_t src, int src_strid
                    kind, slot, elem);
 }
 
+costa_tile_op_t make_tile_op(int n_rows, int n_cols, uint64_t src, int src_stride, bool src_cm,
+                             uint64_t dst, int dst_stride, bool dst_cm, bool transpose, bool conj,
+                             uint32_t kind, uint32_t slot, size_t src_elem, size_t dst_elem) {
+    return tile_op(n_rows, n_cols, src, src_stride, src_cm, dst, dst_stride, dst_cm, transpose, conj,
+                   kind, slot, src_elem, dst_elem);
+}
+
 std::vector<job_params> check_jobs(const std::vector<job>& jobs, int n_ranks, costa_dtype_t& dtype) {
+    costa_dtype_t src;
+    auto out = check_jobs(jobs, n_ranks, src, dtype);
+    if (src != dtype)
+        throw error(COSTA_ERR_ARG, "costa::transform: all layouts must share one element type");
+    return out;
+}
+
+std::vector<job_params> check_jobs(const std::vector<job>& jobs, int n_ranks, costa_dtype_t& src_dtype,
+                                   costa_dtype_t& dtype) {
     if (jobs.empty()) throw error(COSTA_ERR_ARG, "costa::transform: nothing scheduled");
     if (jobs.size() > 0xFFFF) throw error(COSTA_ERR_ARG, "costa::transform: too many layout pairs");
-    dtype = jobs[0].A->dtype;
+    src_dtype = jobs[0].A->dtype;
+    dtype = jobs[0].C->dtype;
+    // mixed precision: convert(A) in C's type; only the 2:1 pairs of one kind convert
+    const bool pair_ok =
+        src_dtype == dtype ||
+        (src_dtype == COSTA_FLOAT && dtype == COSTA_DOUBLE) || (src_dtype == COSTA_DOUBLE && dtype == COSTA_FLOAT) ||
+        (src_dtype == COSTA_CFLOAT && dtype == COSTA_CDOUBLE) || (src_dtype == COSTA_CDOUBLE && dtype == COSTA_CFLOAT);
+    if (!pair_ok)
+        throw error(COSTA_ERR_ARG, std::string("costa::transform: cannot convert ") + dtype_name(src_dtype) +
+                                       " (A) to " + dtype_name(dtype) +
+                                       " (C): mixed transforms are FLOAT <-> DOUBLE and CFLOAT <-> CDOUBLE");
     const bool cplx = dtype_is_complex(dtype);
     std::vector<job_params> out;
     for (const job& jb : jobs) {
-        if (jb.A->dtype != dtype || jb.C->dtype != dtype)
-            throw error(COSTA_ERR_ARG, "costa::transform: all layouts must share one element type");
+        if (jb.A->dtype != src_dtype || jb.C->dtype != dtype) {
+            if (src_dtype == dtype && jb.A->dtype == jb.C->dtype)
+                throw error(COSTA_ERR_ARG, "costa::transform: all layouts must share one element type");
+            throw error(COSTA_ERR_ARG,
+                        std::string("costa::transform: all layout pairs of a batch must share one (A, C) "
+                                    "element-type pair: ") +
+                            dtype_name(src_dtype) + " -> " + dtype_name(dtype) + " and " +
+                            dtype_name(jb.A->dtype) + " -> " + dtype_name(jb.C->dtype));
+        }
         for (const elayout* L : {jb.A, jb.C})
             for (int o : L->owners)
                 if (o < 0 || o >= n_ranks)
@@ -238,8 +290,12 @@ std::unique_ptr<plan> make_plan(const std::vector<job>& jobs, int rank, int n_ra
     p->rank = rank;
     p->n_ranks = n_ranks;
     using tag_info = job_params;
-    const std::vector<tag_info> tags = check_jobs(jobs, n_ranks, p->dtype);
-    const size_t E = dtype_size(p->dtype);
+    const std::vector<tag_info> tags = check_jobs(jobs, n_ranks, p->src_dtype, p->dtype);
+    // element sizes of A, of C and of the package (the narrower type crosses the exchange:
+    // narrowing pairs convert in PACK, widening pairs in UNPACK); all equal for same-type plans
+    const size_t EA = dtype_size(p->src_dtype), EC = dtype_size(p->dtype);
+    p->pkg_dtype = EA < EC ? p->src_dtype : p->dtype;
+    const size_t EP = std::min(EA, EC);
     std::vector<side_tile> send, recv;
     for (const job& jb : jobs) p->slots.push_back(jb.s);
     // prepare_to_send and prepare_to_recv are independent: the receive side runs on a second
@@ -249,9 +305,9 @@ std::unique_ptr<plan> make_plan(const std::vector<job>& jobs, int rank, int n_ra
             const job& jb = jobs[t];
             const bool tr = tags[t].transpose;
             if (send_side)
-                decompose(view{jb.A, tr}, view{jb.C, false}, int(t), E, out);  // prepare_to_send
+                decompose(view{jb.A, tr}, view{jb.C, false}, int(t), out);  // prepare_to_send
             else
-                decompose(view{jb.C, false}, view{jb.A, tr}, int(t), E, out);  // prepare_to_recv
+                decompose(view{jb.C, false}, view{jb.A, tr}, int(t), out);  // prepare_to_recv
         }
         std::sort(out.begin(), out.end(), key_less);
     };
@@ -290,7 +346,6 @@ std::unique_ptr<plan> make_plan(const std::vector<job>& jobs, int rank, int n_ra
     auto will_tr = [](const tag_info& ti, bool src_cm, bool dst_cm) {
         return (ti.transpose && src_cm == dst_cm) || (!ti.transpose && src_cm != dst_cm);
     };
-    auto op_bytes = [&](const costa_tile_op_t& op) { return op_alg_bytes(op, E); };
 
     // target coordinates of every op, for the locality hint (costa_tile_op_t::order)
     std::vector<const side_tile*> at_pack, at_unpack, at_local;
@@ -307,8 +362,8 @@ std::unique_ptr<plan> make_plan(const std::vector<job>& jobs, int rank, int n_ra
         const int64_t n = int64_t(m.n_rows) * m.n_cols;
         // copy_to_buffer: stored shape and ordering, dense, no transform (cpp:191-217)
         p->pack_ops.push_back(make_tile_op(m.n_rows, m.n_cols, uint64_t(m.ptr), m.ld, ti.a_cm,
-                                           uint64_t(off) * E, 0, ti.a_cm, false, false,
-                                           COSTA_SCALE_BITCOPY, 0, E));
+                                           uint64_t(off) * EP, 0, ti.a_cm, false, false,
+                                           COSTA_SCALE_BITCOPY, 0, EA, EP));
         at_pack.push_back(&m);
         p->send_counts[size_t(m.peer)] += n;
         off += n;
@@ -330,9 +385,9 @@ std::unique_ptr<plan> make_plan(const std::vector<job>& jobs, int rank, int n_ra
         const int nr = ti.transpose ? m.n_cols : m.n_rows;
         const int nc = ti.transpose ? m.n_rows : m.n_cols;
         const bool wt = will_tr(ti, ti.a_cm, ti.c_cm);
-        p->unpack_ops.push_back(make_tile_op(nr, nc, uint64_t(off) * E, 0, ti.a_cm, uint64_t(m.ptr),
+        p->unpack_ops.push_back(make_tile_op(nr, nc, uint64_t(off) * EP, 0, ti.a_cm, uint64_t(m.ptr),
                                              m.ld, ti.c_cm, ti.transpose, ti.conj,
-                                             kind_of(ti, wt), uint32_t(m.tag), E));
+                                             kind_of(ti, wt), uint32_t(m.tag), EP, EC));
         at_unpack.push_back(&m);
         p->recv_counts[size_t(m.peer)] += n;
         off += n;
@@ -351,7 +406,7 @@ std::unique_ptr<plan> make_plan(const std::vector<job>& jobs, int rank, int n_ra
         const bool wt = will_tr(ti, ti.a_cm, ti.c_cm);
         p->local_ops.push_back(make_tile_op(s.n_rows, s.n_cols, uint64_t(s.ptr), s.ld, ti.a_cm,
                                             uint64_t(d.ptr), d.ld, ti.c_cm, ti.transpose, ti.conj,
-                                            kind_of(ti, wt), uint32_t(s.tag), E));
+                                            kind_of(ti, wt), uint32_t(s.tag), EA, EC));
         at_local.push_back(&d);
         p->local_elems += int64_t(s.n_rows) * s.n_cols;
     }
@@ -363,9 +418,10 @@ std::unique_ptr<plan> make_plan(const std::vector<job>& jobs, int rank, int n_ra
     set_order(p->pack_ops, at_pack);
     set_order(p->unpack_ops, at_unpack);
     set_order(p->local_ops, at_local);
-    for (auto& op : p->local_ops) p->local_bytes += op_bytes(op);
-    for (auto& op : p->pack_ops) p->pack_bytes += op_bytes(op);
-    for (auto& op : p->unpack_ops) p->unpack_bytes += op_bytes(op);
+    // algorithmic bytes: each side of an op at its own element size
+    for (auto& op : p->local_ops) p->local_bytes += op_alg_bytes(op, EA, EC);
+    for (auto& op : p->pack_ops) p->pack_bytes += op_alg_bytes(op, EA, EP);
+    for (auto& op : p->unpack_ops) p->unpack_bytes += op_alg_bytes(op, EP, EC);
     return p;
 }
 

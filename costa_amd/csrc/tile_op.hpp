@@ -38,10 +38,12 @@ COSTA_HD inline tile_side sub_tile(uint64_t data, int ld, int block_row0, int bl
 // copy_and_transform (memory_utils.hpp:339-412) as one op: an ordering mismatch is itself a
 // transpose and cancels an explicit one (:353-367); stride 0 means the default stride
 // (:330-337, 370-381); a transposing op never takes the memcpy branch.
+// Converting ops (mixed-precision transforms) have a source element of `src_elem` bytes and a
+// destination element of `dst_elem`: each side's VEC flag follows its own byte alignment.
 COSTA_HD inline costa_tile_op_t tile_op(int n_rows, int n_cols, uint64_t src, int src_stride,
                                         bool src_cm, uint64_t dst, int dst_stride, bool dst_cm,
                                         bool transpose, bool conj, uint32_t kind, uint32_t slot,
-                                        uint64_t elem) {
+                                        uint64_t src_elem, uint64_t dst_elem) {
     const bool will_transpose = (transpose && src_cm == dst_cm) || (!transpose && src_cm != dst_cm);
     if (dst_stride == 0) {
         const int r = will_transpose ? n_cols : n_rows, c = will_transpose ? n_rows : n_cols;
@@ -58,9 +60,17 @@ COSTA_HD inline costa_tile_op_t tile_op(int n_rows, int n_cols, uint64_t src, in
     if (will_transpose && kind == COSTA_SCALE_BITCOPY) kind = COSTA_SCALE_ALPHA;  // never memcpy
     op.flags = (will_transpose ? COSTA_TILE_TRANSPOSE : 0u) | (conj ? COSTA_TILE_CONJ : 0u) |
                (kind << COSTA_SCALE_SHIFT) | (slot << COSTA_SLOT_SHIFT);
-    if (src % 16 == 0 && (uint64_t(src_stride) * elem) % 16 == 0) op.flags |= COSTA_TILE_VEC_SRC;
-    if (dst % 16 == 0 && (uint64_t(dst_stride) * elem) % 16 == 0) op.flags |= COSTA_TILE_VEC_DST;
+    if (src % 16 == 0 && (uint64_t(src_stride) * src_elem) % 16 == 0) op.flags |= COSTA_TILE_VEC_SRC;
+    if (dst % 16 == 0 && (uint64_t(dst_stride) * dst_elem) % 16 == 0) op.flags |= COSTA_TILE_VEC_DST;
     return op;
+}
+
+COSTA_HD inline costa_tile_op_t tile_op(int n_rows, int n_cols, uint64_t src, int src_stride,
+                                        bool src_cm, uint64_t dst, int dst_stride, bool dst_cm,
+                                        bool transpose, bool conj, uint32_t kind, uint32_t slot,
+                                        uint64_t elem) {
+    return tile_op(n_rows, n_cols, src, src_stride, src_cm, dst, dst_stride, dst_cm, transpose, conj,
+                   kind, slot, elem, elem);
 }
 
 // algorithmic HBM bytes of one op: read + write (+ read of the target when beta != 0)
@@ -68,6 +78,13 @@ COSTA_HD inline int64_t op_alg_bytes(const costa_tile_op_t& op, uint64_t elem) {
     const uint32_t k = (op.flags & COSTA_SCALE_MASK) >> COSTA_SCALE_SHIFT;
     const int64_t n = int64_t(op.nf) * op.ns;
     return int64_t(elem) * n * (1 + (k != COSTA_SCALE_ZERO) + (k == COSTA_SCALE_AXPBY));
+}
+// ... of a converting op: each side at its own element size
+COSTA_HD inline int64_t op_alg_bytes(const costa_tile_op_t& op, uint64_t src_elem, uint64_t dst_elem) {
+    const uint32_t k = (op.flags & COSTA_SCALE_MASK) >> COSTA_SCALE_SHIFT;
+    const int64_t n = int64_t(op.nf) * op.ns;
+    return int64_t(src_elem) * n * (k != COSTA_SCALE_ZERO) +
+           int64_t(dst_elem) * n * (1 + (k == COSTA_SCALE_AXPBY));
 }
 
 }  // namespace engine

@@ -17,6 +17,7 @@
 
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 namespace costa {
@@ -42,6 +43,22 @@ template <typename T>
 void transform(std::vector<layout_ref<T>>& initial_layouts,
                std::vector<layout_ref<T>>& final_layouts, const char* trans, const T* alpha,
                const T* beta, costa_comm_t comm);
+
+// Mixed precision (MI355X-native; the reference's transform<T> takes one T):
+//   sub(C) = beta*sub(C) + alpha*op(convert(sub(A))),  convert = static_cast<Tc> per element.
+// (Ta, Tc) is float <-> double or complex<float> <-> complex<double>; alpha and beta are of C's
+// type and everything after the conversion runs in it, so the result equals, bit for bit, the
+// same-type transform of an A that was converted first.  The conversion is fused into the tile
+// kernels (no temporary); the narrower type crosses the exchange.  Device-resident layouts only.
+// Same-type calls keep picking the overloads above.
+template <typename Ta, typename Tc>
+typename std::enable_if<!std::is_same<Ta, Tc>::value>::type
+transform(grid_layout<Ta>& initial_layout, grid_layout<Tc>& final_layout, costa_comm_t comm);
+
+template <typename Ta, typename Tc>
+typename std::enable_if<!std::is_same<Ta, Tc>::value>::type
+transform(grid_layout<Ta>& initial_layout, grid_layout<Tc>& final_layout, char trans, Tc alpha,
+          Tc beta, costa_comm_t comm);
 
 // Elements each rank pair exchanges when g_init is transformed into g_final with op `trans`
 // (reference transform.hpp:44-48 / transform.cpp:9-44): every block of g_init (transposed view

@@ -158,7 +158,21 @@ void costa_hip_comm_destroy(costa_comm_t comm);
 
 /* ---- transforms: sub(C) = beta*sub(C) + alpha*op(sub(A)), op in {'N','T','C'} ----
  * alpha/beta point to ONE element of the layouts' dtype (complex: two reals).
- * Collective over `comm`; blocking (returns after C is complete). */
+ * Collective over `comm`; blocking (returns after C is complete).
+ *
+ * Mixed precision (MI355X-native; the reference's transform<T> takes one T): A and C may differ
+ * in dtype, COSTA_FLOAT <-> COSTA_DOUBLE or COSTA_CFLOAT <-> COSTA_CDOUBLE, and then
+ *   sub(C) = beta*sub(C) + alpha*op(convert(sub(A))),
+ * convert being the C++ static_cast from A's element type to C's (round to nearest even,
+ * overflow to +-inf, fp32 subnormals kept, widening exact, complex per component).  alpha/beta
+ * are ONE element of C's dtype and everything after the conversion runs in C's type with the
+ * same-type code: the result equals, bit for bit, the same-type transform of an A converted
+ * first.  The conversion runs inside the tile kernels (no temporary); the packages of the
+ * exchange hold the narrower of the two types (narrowing pairs convert while packing, widening
+ * pairs while unpacking).  Every pair of a batch must share one (A dtype, C dtype); any other
+ * unequal pair (COSTA_INT32 with anything, real with complex) is COSTA_ERR_ARG with a message
+ * naming both types.  Mixed transforms need device-resident layouts (blocking and _async entry
+ * points, any communicator size): on host-resident layouts they return COSTA_ERR_ARG. */
 int costa_hip_transform(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
                         const void* beta, costa_comm_t comm);
 /* several layout pairs in one exchange; trans/alpha/beta are arrays of n entries
@@ -188,11 +202,28 @@ int costa_hip_copy_and_transform(costa_dtype_t dtype, int n_rows, int n_cols, co
 int costa_hip_execute_tiles(costa_dtype_t dtype, const costa_tile_op_t* ops, int64_t n,
                             const void* src_base, void* dst_base, const void* scalars,
                             int n_slots, int device);
+/* the same for converting ops: sources hold src_dtype, destinations dst_dtype (a mixed pair as
+ * above), dst = g(convert(src)); offsets and leading dimensions of each side count in that side's
+ * elements / bytes as in costa_tile_op_t; `scalars` = n_slots (alpha, beta) pairs of dst_dtype.
+ * COSTA_SCALE_BITCOPY means "convert only" here (never a byte copy).  The VEC flags are recomputed
+ * from each side's actual address: the side of the wider type takes 16-byte vector accesses when
+ * 16-byte aligned, the other side 8-byte ones when 8-byte aligned. */
+int costa_hip_execute_tiles_mixed(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
+                                  const costa_tile_op_t* ops, int64_t n, const void* src_base,
+                                  void* dst_base, const void* scalars, int n_slots, int device);
+/* the sub-tile one workgroup of the converting kernels runs for a mixed pair: elements along the
+ * source's fast (*bf) and slow (*bs) dimension */
+int costa_hip_convert_subtile(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, int* bf, int* bs);
 
 /* ---- plan inspection (host only, never touches a GPU) ----
  * Plans the transform for rank `rank` of `nranks` and copies the three descriptor
  * lists out.  Offsets of pack destinations / unpack sources are byte offsets into the
  * send / receive buffer; all other addresses are the layouts' own pointers.
+ * The package element size is that of the layouts' dtype; for a mixed pair (A and C of different
+ * dtypes) it is the smaller of the two: pack ops then read A's type and write the package type,
+ * unpack ops read the package type and write C's, local ops read A's and write C's, and each
+ * side's byte offsets and VEC flag follow its own element size.  Counts and displacements are in
+ * elements; `scalars` are of C's dtype.
  * Call once with NULL arrays to get the sizes in *info, then again with arrays of
  * at least those sizes. */
 typedef struct {
@@ -239,6 +270,8 @@ typedef struct {
                              (costa_hip_set_list_builder) */
     int64_t fused_pieces; /* of tiny_items: wavefront pieces run as workgroups at the end of the
                              destination-block group launch (no tiny_kernel launch of their own) */
+    int64_t convert_items; /* sub-tiles run by convert_kernel (the converting lists of mixed
+                              transforms, costa_hip_execute_tiles_mixed) */
 } costa_stats_t;
 int costa_hip_set_profiling(int on);
 int costa_hip_get_stats(costa_stats_t* out, int reset);

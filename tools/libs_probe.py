@@ -25,7 +25,8 @@ class Stats(C.Structure):  # costa_stats_t (include/costa_hip.h)
                [(k, C.c_int64) for k in ("pack_launches", "local_launches", "unpack_launches", "pack_bytes",
                                          "local_bytes", "unpack_bytes", "transforms", "plan_hits", "plan_misses",
                                          "host_groups", "device_plans")] + \
-               [("plan_ms", C.c_double), ("host_direct", C.c_int64), ("host_direct_groups", C.c_int64)]
+               [("plan_ms", C.c_double), ("host_direct", C.c_int64), ("host_direct_groups", C.c_int64),
+                ("later", C.c_int64 * 16)]  # room for the counters appended since (tile_items ...)
 
 
 class Lib:
