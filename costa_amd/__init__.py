@@ -30,7 +30,8 @@ __all__ = [
     "CostaError", "lib", "FLOAT", "DOUBLE", "CFLOAT", "CDOUBLE", "INT32", "dtype_code",
     "np_dtype", "Layout", "block_cyclic_layout", "custom_layout", "Comm", "transform",
     "transform_batch", "transform_async", "transform_batch_async", "synchronize", "transformer", "copy_and_transform", "execute_tiles", "execute_tiles_mixed",
-    "convert_subtile", "TileOp",
+    "convert_subtile", "TileOp", "TriOp", "TRI_OP_DTYPE", "transform_tri", "transform_tri_async",
+    "execute_tiles_tri", "plan_export_tri", "tri_cut", "tri_subtile", "tri_phase_ms",
     "plan_export", "set_profiling", "get_stats", "release_caches", "TILE_OP_DTYPE",
 ]
 
@@ -45,6 +46,11 @@ SCALE_BITCOPY, SCALE_ZERO, SCALE_ALPHA, SCALE_AXPBY = 0, 1, 2, 3
 TILE_OP_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("nf", "<i4"), ("ns", "<i4"),
                           ("lds", "<i4"), ("ldd", "<i4"), ("flags", "<u4"),
                           ("order", "<u4")])
+
+
+# numpy view of costa_tri_op_t (48 bytes): the tile op's fields, then the diagonal
+TRI_LE = 0x40
+TRI_OP_DTYPE = np.dtype(TILE_OP_DTYPE.descr + [("diag", "<i4"), ("pad", "<i4")])
 
 
 class CostaError(RuntimeError):
@@ -84,10 +90,20 @@ class TileOp(C.Structure):
                 ("order", C.c_uint32)]
 
 
+class TriOp(C.Structure):
+    """costa_tri_op_t: element (f, s) of the op is kept when s - f >= diag, or s - f <= diag with
+    flag TRI_LE."""
+    _fields_ = [("op", TileOp), ("diag", C.c_int32), ("pad", C.c_int32)]
+
+
 class PlanInfo(C.Structure):
     _fields_ = [("n_local", C.c_int64), ("n_pack", C.c_int64), ("n_unpack", C.c_int64),
                 ("send_elems", C.c_int64), ("recv_elems", C.c_int64),
                 ("local_elems", C.c_int64), ("n_ranks", C.c_int32), ("n_slots", C.c_int32)]
+
+
+class TriPlanInfo(C.Structure):
+    _fields_ = [("base", PlanInfo), ("n_local_tri", C.c_int64), ("n_unpack_tri", C.c_int64)]
 
 
 class Stats(C.Structure):
@@ -115,8 +131,9 @@ class Stats(C.Structure):
 class FullStats(Stats):
     """costa_stats_t as the library fills it: ``Stats`` is its prefix, counters added since are
     appended here in the order of include/costa_hip.h (convert_items: sub-tiles run by the
-    converting kernels of mixed-precision transforms)."""
-    _fields_ = [("convert_items", C.c_int64)]
+    converting kernels of mixed-precision transforms; tri_items: sub-tiles run by the edge-tile
+    kernels of triangular transforms)."""
+    _fields_ = [("convert_items", C.c_int64), ("tri_items", C.c_int64)]
 
 
 # COSTA_LIB: another build of the library (A/B runs against a tuning build of the sources)
@@ -171,6 +188,14 @@ def lib():
         "costa_hip_execute_tiles": (i, [i, C.POINTER(TileOp), i64, vp, vp, vp, i, i]),
         "costa_hip_execute_tiles_mixed": (i, [i, i, C.POINTER(TileOp), i64, vp, vp, vp, i, i]),
         "costa_hip_convert_subtile": (i, [i, i, C.POINTER(i), C.POINTER(i)]),
+        "costa_hip_transform_tri": (i, [vp, vp, c, c, i, vp, vp, vp]),
+        "costa_hip_transform_tri_async": (i, [vp, vp, c, c, i, vp, vp, vp, vp]),
+        "costa_hip_execute_tiles_tri": (i, [i, C.POINTER(TriOp), i64, vp, vp, vp, i, i]),
+        "costa_hip_tri_cut": (i, []),
+        "costa_hip_tri_phase_ms": (i, [C.POINTER(C.c_double), i]),
+        "costa_hip_tri_subtile": (i, [i, C.POINTER(i), C.POINTER(i)]),
+        "costa_hip_plan_export_tri": (i, [vp, vp, c, c, i, vp, vp, i, i, C.POINTER(TriPlanInfo), vp, vp,
+                                          vp, vp, vp, vp, vp, vp, vp, vp]),
         "costa_hip_plan_export": (i, [i, C.POINTER(vp), C.POINTER(vp), C.c_char_p, vp, vp, i, i,
                                       C.POINTER(PlanInfo), vp, vp, vp, vp, vp, vp, vp, vp]),
         "costa_hip_set_profiling": (i, [i]),
@@ -493,6 +518,67 @@ def convert_subtile(src_dtype, dst_dtype) -> tuple:
     return bf.value, bs.value
 
 
+# ------------------------------------------------------------------ triangular transforms
+def _one_pair(A, Cl):
+    if not isinstance(A, Layout) or not isinstance(Cl, Layout):
+        raise CostaError(1, "costa: batches of triangular (masked) layout pairs are not supported")
+
+
+def transform_tri(A: Layout, Cl: Layout, comm: Comm, trans: str = "N", uplo: str = "U", k: int = 0,
+                  alpha=1, beta=0):
+    """C(i, j) = beta*C(i, j) + alpha*op(A)(i, j) where j - i >= k (uplo 'U', numpy triu(k)) or
+    j - i <= k ('L', tril(k)); every other element of C keeps its bytes (costa_hip_transform_tri)."""
+    _one_pair(A, Cl)
+    code = Cl.dtype
+    _check(lib().costa_hip_transform_tri(A.handle, Cl.handle, _chr(trans), _chr(uplo), int(k),
+                                         _scalar_bytes(code, alpha), _scalar_bytes(code, beta),
+                                         comm.handle))
+
+
+def transform_tri_async(A: Layout, Cl: Layout, comm: Comm, trans: str = "N", uplo: str = "U",
+                        k: int = 0, alpha=1, beta=0, stream=None):
+    """Stream-ordered transform_tri (device-resident layouts); `stream` as for transform_async."""
+    _one_pair(A, Cl)
+    code = Cl.dtype
+    s = getattr(stream, "cuda_stream", stream) or 0
+    _check(lib().costa_hip_transform_tri_async(A.handle, Cl.handle, _chr(trans), _chr(uplo), int(k),
+                                               _scalar_bytes(code, alpha), _scalar_bytes(code, beta),
+                                               comm.handle, C.c_void_p(s)))
+
+
+def execute_tiles_tri(dtype, ops: np.ndarray, scalars: np.ndarray, src_base=0, dst_base=0,
+                      device: int = 0):
+    """Run a list of edge ops (numpy array of TRI_OP_DTYPE) in one launch of the edge-tile kernel."""
+    code = dtype_code(dtype)
+    ops = np.ascontiguousarray(ops, dtype=TRI_OP_DTYPE)
+    sc = np.ascontiguousarray(scalars, dtype=_NP[code]).reshape(-1)
+    assert sc.size % 2 == 0
+    _check(lib().costa_hip_execute_tiles_tri(code, ops.ctypes.data_as(C.POINTER(TriOp)), ops.size,
+                                             C.c_void_p(_ptr(src_base)), C.c_void_p(_ptr(dst_base)),
+                                             sc.ctypes.data, sc.size // 2, device))
+
+
+def tri_cut() -> int:
+    """Rows of the bands the planner cuts a tile crossing the mask's diagonal into."""
+    return lib().costa_hip_tri_cut()
+
+
+def tri_phase_ms(reset: bool = False) -> float:
+    """Event time (ms, profiling on) of the edge-tile launches since the last reset: a part of the
+    statistics' local_ms + unpack_ms."""
+    v = C.c_double(0)
+    _check(lib().costa_hip_tri_phase_ms(C.byref(v), int(reset)))
+    return v.value
+
+
+def tri_subtile(dtype) -> tuple:
+    """(BF, BS): the sub-tile one workgroup of the edge-tile kernel runs, in elements along the
+    source's fast and slow dimension."""
+    bf, bs = C.c_int(0), C.c_int(0)
+    _check(lib().costa_hip_tri_subtile(dtype_code(dtype), C.byref(bf), C.byref(bs)))
+    return bf.value, bs.value
+
+
 @dataclass
 class Plan:
     local_ops: np.ndarray
@@ -540,6 +626,36 @@ def plan_export(As: Sequence[Layout], Cs: Sequence[Layout], rank: int, nranks: i
                   lo.ctypes.data, po.ctypes.data, uo.ctypes.data,
                   *[x.ctypes.data for x in cnt], sc.ctypes.data))
     return Plan(lo, po, uo, *cnt, sc, info.send_elems, info.recv_elems, info.local_elems)
+
+
+@dataclass
+class TriPlan(Plan):
+    local_tri: np.ndarray = None   # TRI_OP_DTYPE: edge tiles that stay on the rank
+    unpack_tri: np.ndarray = None  # TRI_OP_DTYPE: edge tiles read from the receive package
+
+
+def plan_export_tri(A: Layout, Cl: Layout, rank: int, nranks: int, trans: str = "N", uplo: str = "U",
+                    k: int = 0, alpha=1, beta=0) -> TriPlan:
+    """Tile-op lists of `rank` for a triangular transform (host planner, never touches a GPU)."""
+    _one_pair(A, Cl)
+    code = Cl.dtype
+    ab, bb = _scalar_bytes(code, alpha), _scalar_bytes(code, beta)
+    info = TriPlanInfo()
+    L = lib()
+    args = (A.handle, Cl.handle, _chr(trans), _chr(uplo), int(k), ab, bb, rank, nranks, C.byref(info))
+    _check(L.costa_hip_plan_export_tri(*args, *([None] * 10)))
+    b = info.base
+    lo = np.zeros(b.n_local, TILE_OP_DTYPE)
+    po = np.zeros(b.n_pack, TILE_OP_DTYPE)
+    uo = np.zeros(b.n_unpack, TILE_OP_DTYPE)
+    lt = np.zeros(info.n_local_tri, TRI_OP_DTYPE)
+    ut = np.zeros(info.n_unpack_tri, TRI_OP_DTYPE)
+    cnt = [np.zeros(nranks, np.int64) for _ in range(4)]
+    sc = np.zeros(2 * b.n_slots, _NP[code])
+    _check(L.costa_hip_plan_export_tri(*args, lo.ctypes.data, po.ctypes.data, uo.ctypes.data,
+                                       lt.ctypes.data, ut.ctypes.data, *[x.ctypes.data for x in cnt],
+                                       sc.ctypes.data))
+    return TriPlan(lo, po, uo, *cnt, sc, b.send_elems, b.recv_elems, b.local_elems, lt, ut)
 
 
 # ------------------------------------------------------------------ measurement

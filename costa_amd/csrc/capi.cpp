@@ -108,6 +108,18 @@ std::vector<job> make_jobs(int n, const costa_layout_t* A, const costa_layout_t*
     }
     return jobs;
 }
+
+// the one job of a triangular transform; uplo 'U' or 'L' in either case
+std::vector<job> make_tri_job(costa_layout_t A, costa_layout_t C, char trans, char uplo, int k,
+                              const void* alpha, const void* beta) {
+    const char ul = char(std::toupper(static_cast<unsigned char>(uplo)));
+    if (ul != 'U' && ul != 'L')
+        throw costa::engine::error(COSTA_ERR_ARG, "costa: uplo must be 'U' or 'L'");
+    auto jobs = make_jobs(1, &A, &C, &trans, alpha, beta);
+    jobs[0].uplo = ul;
+    jobs[0].k = k;
+    return jobs;
+}
 }  // namespace
 
 namespace {
@@ -323,6 +335,94 @@ int costa_hip_transform_batch_async(int n, const costa_layout_t* A, const costa_
     });
 }
 
+int costa_hip_transform_tri(costa_layout_t A, costa_layout_t C, char trans, char uplo, int k,
+                            const void* alpha, const void* beta, costa_comm_t comm) {
+    return gpu_guarded([&] {
+        if (!comm || !alpha || !beta) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::transform(make_tri_job(A, C, trans, uplo, k, alpha, beta), comm->c);
+    });
+}
+
+int costa_hip_transform_tri_async(costa_layout_t A, costa_layout_t C, char trans, char uplo, int k,
+                                  const void* alpha, const void* beta, costa_comm_t comm,
+                                  void* stream) {
+    return gpu_guarded([&] {
+        if (!comm || !alpha || !beta) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::transform(make_tri_job(A, C, trans, uplo, k, alpha, beta), comm->c, stream, true);
+    });
+}
+
+int costa_hip_execute_tiles_tri(costa_dtype_t dtype, const costa_tri_op_t* ops, int64_t n,
+                                const void* src_base, void* dst_base, const void* scalars,
+                                int n_slots, int device) {
+    static_assert(sizeof(costa_tile_op_t) == 40 && sizeof(costa_tri_op_t) == 48, "descriptor sizes");
+    return gpu_guarded([&] {
+        if (n < 0 || (n > 0 && (!ops || !scalars)))
+            throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::execute_tiles_tri(dtype, ops, n, src_base, dst_base, scalars, n_slots, device);
+    });
+}
+
+int costa_hip_tri_cut(void) { return costa::engine::kTriCut; }
+
+int costa_hip_tri_phase_ms(double* ms, int reset) {
+    return guarded([&] {
+        if (!ms) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        *ms = costa::engine::tri_phase_ms(reset != 0);
+    });
+}
+
+int costa_hip_tri_subtile(costa_dtype_t dtype, int* bf, int* bs) {
+    return guarded([&] {
+        if (!bf || !bs) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::tri_subtile(dtype, bf, bs);
+    });
+}
+
+int costa_hip_plan_export_tri(costa_layout_t A, costa_layout_t C, char trans, char uplo, int k,
+                              const void* alpha, const void* beta, int rank, int nranks,
+                              costa_tri_plan_info_t* info, costa_tile_op_t* local_ops,
+                              costa_tile_op_t* pack_ops, costa_tile_op_t* unpack_ops,
+                              costa_tri_op_t* local_tri, costa_tri_op_t* unpack_tri,
+                              int64_t* send_counts, int64_t* send_displs, int64_t* recv_counts,
+                              int64_t* recv_displs, void* scalars) {
+    return guarded([&] {
+        if (!info || !alpha || !beta) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        if (nranks < 1 || rank < 0 || rank >= nranks)
+            throw costa::engine::error(COSTA_ERR_ARG, "bad rank/size");
+        check_handles(1, &A, &C);
+        auto p = costa::engine::make_plan(make_tri_job(A, C, trans, uplo, k, alpha, beta), rank, nranks);
+        info->base.n_local = int64_t(p->local_ops.size());
+        info->base.n_pack = int64_t(p->pack_ops.size());
+        info->base.n_unpack = int64_t(p->unpack_ops.size());
+        info->base.send_elems = p->send_elems;
+        info->base.recv_elems = p->recv_elems;
+        info->base.local_elems = p->local_elems;
+        info->base.n_ranks = nranks;
+        info->base.n_slots = int32_t(p->slots.size());
+        info->n_local_tri = int64_t(p->local_tri.size());
+        info->n_unpack_tri = int64_t(p->unpack_tri.size());
+        auto cp = [](const auto& v, auto* dst) {
+            if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0]));
+        };
+        cp(p->local_ops, local_ops);
+        cp(p->pack_ops, pack_ops);
+        cp(p->unpack_ops, unpack_ops);
+        cp(p->local_tri, local_tri);
+        cp(p->unpack_tri, unpack_tri);
+        cp(p->send_counts, send_counts);
+        cp(p->send_displs, send_displs);
+        cp(p->recv_counts, recv_counts);
+        cp(p->recv_displs, recv_displs);
+        if (scalars) {
+            const size_t E = dtype_size(p->dtype);
+            auto* out = static_cast<unsigned char*>(scalars);
+            std::memcpy(out, p->slots[0].alpha.data(), E);
+            std::memcpy(out + E, p->slots[0].beta.data(), E);
+        }
+    });
+}
+
 int costa_hip_synchronize(costa_comm_t comm) {
     return gpu_guarded([&] {
         if (!comm) throw costa::engine::error(COSTA_ERR_ARG, "null communicator");
@@ -529,6 +629,34 @@ void transform(std::vector<layout_ref<T>>& from, std::vector<layout_ref<T>>& to,
                const T* alpha, const T* beta, costa_comm_t comm) {
     run<T>(from, to, trans, alpha, beta, comm);
 }
+
+template <typename T>
+void transform_triangular(grid_layout<T>& A, grid_layout<T>& C, char trans, char uplo, int k, T alpha,
+                          T beta, costa_comm_t comm) {
+    raise(gpu_guarded([&] {
+        if (!comm) throw engine::error(COSTA_ERR_ARG, "costa::transform_triangular: null communicator");
+        const char ul = char(std::toupper(static_cast<unsigned char>(uplo)));
+        if (ul != 'U' && ul != 'L')
+            throw engine::error(COSTA_ERR_ARG, "costa::transform_triangular: uplo must be 'U' or 'L'");
+        engine::elayout a = engine::erase(A), c = engine::erase(C);
+        engine::job jb;
+        jb.A = &a;
+        jb.C = &c;
+        jb.trans = trans;
+        jb.s = scal_of(alpha, beta);
+        jb.uplo = ul;
+        jb.k = k;
+        engine::transform({jb}, comm->c);
+    }));
+}
+#define COSTA_INSTANTIATE_TRI(T)                                                                  \
+    template void transform_triangular<T>(grid_layout<T>&, grid_layout<T>&, char, char, int, T, T, \
+                                          costa_comm_t);
+COSTA_INSTANTIATE_TRI(float)
+COSTA_INSTANTIATE_TRI(double)
+COSTA_INSTANTIATE_TRI(std::complex<float>)
+COSTA_INSTANTIATE_TRI(std::complex<double>)
+COSTA_INSTANTIATE_TRI(int)
 
 // mixed precision: one (A, C) pair, scalars of C's type
 template <typename Ta, typename Tc>

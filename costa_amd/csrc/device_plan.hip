@@ -316,6 +316,8 @@ std::unique_ptr<plan> make_plan_device(const std::vector<job>& jobs, int rank, i
     const double t0 = now();
     // mixed-precision pairs are planned on the host (whose checks also report unsupported pairs)
     if (any_mixed(jobs)) return nullptr;
+    // ... and so are triangular (masked) transforms: the mask's cut lives in plan.cpp decompose
+    if (any_masked(jobs)) return nullptr;
     auto p = std::make_unique<plan>();
     const std::vector<job_params> prm = check_jobs(jobs, n_ranks, p->dtype);
     p->src_dtype = p->pkg_dtype = p->dtype;

@@ -303,6 +303,17 @@ void exchange_round_of_ops(const plan& p, int rounds, std::vector<int>& pack_rou
     }
 }
 
+void exchange_round_of_tri(const plan& p, int rounds, std::vector<int>& unpack_tri_round) {
+    const size_t E = dtype_size(p.pkg_dtype);
+    unpack_tri_round.clear();
+    for (const auto& t : p.unpack_tri) {  // by its last element, like every unpack op
+        const int64_t first = int64_t(t.op.src / E);
+        const int64_t last = first + int64_t(t.op.nf) * t.op.ns - 1;
+        const size_t q = peer_of(p.recv_displs, first);
+        unpack_tri_round.push_back(round_of(last - p.recv_displs[q], p.recv_counts[q], E, rounds));
+    }
+}
+
 int comm_rank(const comm* c) { return c->rank; }
 int comm_size(const comm* c) { return c->size; }
 void comm_destroy(comm* c) { delete c; }
@@ -1126,7 +1137,7 @@ bool granule_split(const std::vector<costa_tile_op_t>& ops, int64_t E, int64_t m
 
 work_split build_work(costa_dtype_t dtype, const std::vector<costa_tile_op_t>& ops_in,
                       std::vector<costa_tile_op_t>& ordered, std::vector<uint64_t>& work,
-                      list_kind kind, device_section* dev) {
+                      list_kind kind, device_section* dev, bool dst_order) {
     const bool pack_list = kind == list_pack, local = kind == list_local;
     // Sources off the 16-byte grid: 4-byte elements are read as 16-byte vectors anyway (dword
     // alignment suffices for global_load_dwordx4): fp32 16384^2 'T' with lld 16386 0.405 against
@@ -1386,8 +1397,8 @@ work_split build_work(costa_dtype_t dtype, const std::vector<costa_tile_op_t>& o
             if (n > 0xFFFFFFFFull) throw error(COSTA_ERR_ARG, "costa: tile too large");
             for (uint64_t q = 0; q < n; ++q) work.push_back((i << 32) | q);
         }
-        bool by_address = kn.large_sort == 2;
-        if (kn.large_sort == 3) {
+        bool by_address = kn.large_sort == 2 || dst_order;
+        if (kn.large_sort == 3 && !dst_order) {
             by_address = (E == 4 || E == 8 || (E == 16 && c == 0 && sq)) && ordered.size() > op0;
             for (size_t i = op0; i < ordered.size(); ++i)
                 by_address = by_address && (ordered[i].flags & COSTA_TILE_TRANSPOSE);
@@ -1751,11 +1762,16 @@ struct cached_plan {
     // converting lists of a mixed-precision plan (convert_kernels.hip) have a convert_list instead
     // of a work_split: LOCAL; PACK of a narrowing pair; UNPACK of a widening pair
     convert_list c_local;
+    // edge tiles of a triangular plan (tri_kernels.hip): LOCAL, and UNPACK per exchange round
+    dbuf d_local_tri, w_local_tri;
+    tri_list t_local;
     struct xround {  // one exchange round: its pack ops (by their first element) and unpack
                      // ops (by their last element)
         dbuf d_pack, w_pack, d_unpack, w_unpack;
         work_split l_pack, l_unpack;
         convert_list c_pack, c_unpack;
+        dbuf d_unpack_tri, w_unpack_tri;
+        tri_list t_unpack;
         bool tr_unpack = false, ax_unpack = false;
     };
     std::vector<std::unique_ptr<xround>> rounds;
@@ -1940,6 +1956,9 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
         for (bool cm : {true, false})
             w = w << 8 | scale_kind(j.C->dtype, j.s, cm, std::toupper(j.trans) == 'C');
         key.push_back(w);
+        // the mask of a triangular transform
+        key.push_back(uint64_t(uint8_t(std::toupper(static_cast<unsigned char>(j.uplo)))) << 32 |
+                      uint64_t(uint32_t(j.k)));
     }
     hasher h;
     for (uint64_t w : key) h.mix(w);
@@ -1961,7 +1980,8 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
     double t_resid = 0, t_plan = 0, t_work = 0;
 
     const bool mixed = any_mixed(jobs);
-    if (mixed) {  // an unsupported pair is reported as such, whatever the residency
+    const bool masked = any_masked(jobs);
+    if (mixed || masked) {  // an unsupported pair is reported as such, whatever the residency
         costa_dtype_t a, b;
         check_jobs(jobs, c->size, a, b);
     }
@@ -2034,7 +2054,8 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
         // Pipelined staging (host_pipe.cpp) when every layout is host-resident, no range holds
         // both source and target data (in-place) and no target range is shared by two jobs
         // (their updates would have to be applied in order).
-        bool pipe_ok = host_staging_mode() == 1 &&
+        // (triangular transforms always take the mirror scheme)
+        bool pipe_ok = host_staging_mode() == 1 && !masked &&
                        std::none_of(on_dev.begin(), on_dev.end(), [](bool d) { return d; });
         for (uint8_t f : range_flags)
             if ((f & 3) == 3 || (f & 4)) pipe_ok = false;
@@ -2103,7 +2124,8 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
         for (size_t i = 0; i < staged_ranges.size(); ++i) {
             const hrange& r = staged_ranges[i];
             const uint8_t f = range_flags[i];
-            const bool overwritten = f == 2 && !reads_c[i] && written[i] == r.hi - r.lo;
+            // (a masked plan never overwrites a range completely: dropped elements keep their bytes)
+            const bool overwritten = !masked && f == 2 && !reads_c[i] && written[i] == r.hi - r.lo;
             if ((f & 1) || ((f & 2) && !overwritten)) cp->h2d_ranges.push_back(r);
             if (f & 2) cp->d2h_ranges.push_back(r);
         }
@@ -2127,7 +2149,14 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
     if (p.mixed())
         cp->c_local = build_convert_work(p.src_dtype, p.dtype, p.local_ops, 0, 0, ord_l, w_l);
     else
-        cp->l_local = build_work(p.dtype, p.local_ops, ord_l, w_l, list_local, &sec_l);
+        // The wholly kept tiles of a triangular plan merge into row bands of unequal widths, one
+        // sub-tile tall: in list order consecutive workgroups walk along a band, a sub-tile's
+        // columns apart, and a copy list ran at 3.8 TB/s against 6.7 for the full rectangle;
+        // in destination-address order 6.2 (16384^2 fp64 'N').
+        cp->l_local = build_work(p.dtype, p.local_ops, ord_l, w_l, list_local, &sec_l, masked);
+    std::vector<costa_tri_op_t> ord_lt;
+    std::vector<uint64_t> w_lt;
+    if (!p.local_tri.empty()) cp->t_local = build_tri_work(p.dtype, p.local_tri, 0, 0, ord_lt, w_lt);
     // exchange rounds: pack ops go to the round of their first element (every element a round
     // sends is packed by then), unpack ops to the round of their last (every element they read
     // has arrived)
@@ -2138,6 +2167,13 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
         exchange_round_of_ops(p, R, pr, ur);
         for (size_t i = 0; i < p.pack_ops.size(); ++i) pk[size_t(pr[i])].push_back(p.pack_ops[i]);
         for (size_t i = 0; i < p.unpack_ops.size(); ++i) up[size_t(ur[i])].push_back(p.unpack_ops[i]);
+    }
+    std::vector<std::vector<costa_tri_op_t>> upt(static_cast<size_t>(R)), ord_ut(static_cast<size_t>(R));
+    std::vector<std::vector<uint64_t>> w_ut(static_cast<size_t>(R));
+    if (!p.unpack_tri.empty()) {
+        std::vector<int> tr;
+        exchange_round_of_tri(p, R, tr);
+        for (size_t i = 0; i < p.unpack_tri.size(); ++i) upt[size_t(tr[i])].push_back(p.unpack_tri[i]);
     }
     std::vector<std::vector<costa_tile_op_t>> ord_p(static_cast<size_t>(R)), ord_u(static_cast<size_t>(R));
     std::vector<std::vector<uint64_t>> w_p(static_cast<size_t>(R)), w_u(static_cast<size_t>(R));
@@ -2158,11 +2194,17 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
         else
             x->l_unpack = build_work(p.dtype, up[size_t(r)], ord_u[size_t(r)], w_u[size_t(r)], list_unpack,
                                      &sec_u[size_t(r)]);
+        if (!upt[size_t(r)].empty())
+            x->t_unpack = build_tri_work(p.dtype, upt[size_t(r)], 0, 0, ord_ut[size_t(r)], w_ut[size_t(r)]);
         cp->rounds.push_back(std::move(x));
     }
     t_work = now() - t0 - t_resid - t_plan;
     upload_list(cp->d_local, ord_l, sec_l.d_ordered, sec_l.at_ordered, sec_l.n_ordered, dc.main);
     upload_list(cp->w_local, w_l, sec_l.d_work, sec_l.at_work, sec_l.n_work, dc.main);
+    if (cp->t_local.n_items) {
+        cp->d_local_tri.upload(ord_lt, dc.main);
+        cp->w_local_tri.upload(w_lt, dc.main);
+    }
     for (int r = 0; r < R; ++r) {
         auto& x = *cp->rounds[size_t(r)];
         const device_section& su = sec_u[size_t(r)];
@@ -2170,6 +2212,10 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
         x.w_pack.upload(w_p[size_t(r)], dc.main);
         upload_list(x.d_unpack, ord_u[size_t(r)], su.d_ordered, su.at_ordered, su.n_ordered, dc.main);
         upload_list(x.w_unpack, w_u[size_t(r)], su.d_work, su.at_work, su.n_work, dc.main);
+        if (x.t_unpack.n_items) {
+            x.d_unpack_tri.upload(ord_ut[size_t(r)], dc.main);
+            x.w_unpack_tri.upload(w_ut[size_t(r)], dc.main);
+        }
     }
     HIP_CHECK(hipStreamSynchronize(dc.main));  // host vectors above are temporaries
     if (trace)
@@ -2215,7 +2261,10 @@ void release_caches() {
 // resolved (elapsed time added to the statistics) at the next synchronisation point, so
 // asynchronous transforms are timed too.
 namespace {
-enum phase { PH_LOCAL, PH_PACK, PH_EXCHANGE, PH_UNPACK, PH_H2D, PH_D2H };
+// (PH_TRI_*: the edge-tile launches of triangular plans; their time counts as LOCAL / UNPACK time
+// and is also kept on its own, tri_phase_ms())
+enum phase { PH_LOCAL, PH_PACK, PH_EXCHANGE, PH_UNPACK, PH_H2D, PH_D2H, PH_TRI_LOCAL, PH_TRI_UNPACK };
+double g_tri_ms = 0;
 
 struct phase_timer {
     device_ctx& dc;
@@ -2252,7 +2301,12 @@ void device_ctx::resolve(size_t max_n) {
         HIP_CHECK(hipEventElapsedTime(&ms, t.a, t.b));
         double* acc[] = {&g_stats.local_ms, &g_stats.pack_ms, &g_stats.exchange_ms,
                          &g_stats.unpack_ms, &g_stats.h2d_ms, &g_stats.d2h_ms};
-        *acc[t.phase] += ms;
+        if (t.phase == PH_TRI_LOCAL || t.phase == PH_TRI_UNPACK) {
+            (t.phase == PH_TRI_LOCAL ? g_stats.local_ms : g_stats.unpack_ms) += ms;
+            g_tri_ms += ms;
+        } else {
+            *acc[t.phase] += ms;
+        }
         free_events.push_back(t.a);
         free_events.push_back(t.b);
         ++n;
@@ -2276,6 +2330,14 @@ void resolve_pending() {
         HIP_CHECK(hipSetDevice(kv.first));
         kv.second->resolve();
     }
+}
+
+double tri_phase_ms(bool reset) {
+    resolve_pending();
+    std::lock_guard<std::recursive_mutex> lk(g_mutex);
+    const double v = g_tri_ms;
+    if (reset) g_tri_ms = 0;
+    return v;
 }
 
 void synchronize(comm* c) {
@@ -2389,6 +2451,13 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
                      ls);
         tm.stop();
     }
+    if (cp.t_local.n_items) {  // the edge tiles of a triangular plan, behind its ordinary LOCAL list
+        tm.start(PH_TRI_LOCAL, ls);
+        launch_tri(p.dtype, static_cast<const costa_tri_op_t*>(cp.d_local_tri.p),
+                   static_cast<const uint64_t*>(cp.w_local_tri.p), cp.t_local, nullptr, nullptr,
+                   cp.d_scal.p, ls);
+        tm.stop();
+    }
 
     if (exchange) {
         dc.send.reserve(size_t(p.send_elems) * E + 256);
@@ -2433,14 +2502,23 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
                                cp.d_scal.p, dc.aux);
                 tm.stop();
             }
-            if (!x.l_unpack.n_items()) continue;
-            HIP_CHECK(hipStreamWaitEvent(dc.aux, dc.ev_moved[size_t(r)], 0));
-            tm.start(PH_UNPACK, dc.aux);
-            launch_tiles(p.dtype,
-                         make_launch(x.l_unpack, x.d_unpack.p, x.w_unpack.p, rb, nullptr,
-                                     cp.d_scal.p, x.tr_unpack, x.ax_unpack),
-                         dc.aux);
-            tm.stop();
+            if (x.l_unpack.n_items()) {
+                HIP_CHECK(hipStreamWaitEvent(dc.aux, dc.ev_moved[size_t(r)], 0));
+                tm.start(PH_UNPACK, dc.aux);
+                launch_tiles(p.dtype,
+                             make_launch(x.l_unpack, x.d_unpack.p, x.w_unpack.p, rb, nullptr,
+                                         cp.d_scal.p, x.tr_unpack, x.ax_unpack),
+                             dc.aux);
+                tm.stop();
+            }
+            if (x.t_unpack.n_items) {  // the round's edge tiles, after its ordinary unpack launch
+                HIP_CHECK(hipStreamWaitEvent(dc.aux, dc.ev_moved[size_t(r)], 0));
+                tm.start(PH_TRI_UNPACK, dc.aux);
+                launch_tri(p.dtype, static_cast<const costa_tri_op_t*>(x.d_unpack_tri.p),
+                           static_cast<const uint64_t*>(x.w_unpack_tri.p), x.t_unpack, rb, nullptr,
+                           cp.d_scal.p, dc.aux);
+                tm.stop();
+            }
         }
         // the call ends on main once LOCAL, every unpack and every round of the exchange are done
         HIP_CHECK(hipEventRecord(dc.ev_local, dc.aux));
@@ -2467,7 +2545,8 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
         if (!dtype_is_complex(p.dtype) && pieces_in_group_launch(w.n_cblock, w.n_tiny))
             g_stats.fused_pieces += w.n_tiny;
     };
-    if (cp.l_local.n_items() || cp.c_local.n_items) {
+    g_stats.tri_items += cp.t_local.n_items;
+    if (cp.l_local.n_items() || cp.c_local.n_items || cp.t_local.n_items) {
         g_stats.local_launches++;
         g_stats.local_bytes += p.local_bytes;
         count_items(cp.l_local);
@@ -2476,7 +2555,8 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
     if (exchange) {
         for (const auto& x : cp.rounds) {
             g_stats.pack_launches += x->l_pack.n_items() || x->c_pack.n_items ? 1 : 0;
-            g_stats.unpack_launches += x->l_unpack.n_items() || x->c_unpack.n_items ? 1 : 0;
+            g_stats.unpack_launches += x->l_unpack.n_items() || x->c_unpack.n_items || x->t_unpack.n_items ? 1 : 0;
+            g_stats.tri_items += x->t_unpack.n_items;
             count_items(x->l_pack);
             count_items(x->l_unpack);
             g_stats.convert_items += x->c_pack.n_items + x->c_unpack.n_items;
@@ -2554,6 +2634,32 @@ void execute_tiles_mixed(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const
                    static_cast<char*>(dst_base), d_scal.p, dc.main);
     HIP_CHECK(hipStreamSynchronize(dc.main));
     g_stats.convert_items += l.n_items;
+}
+
+void execute_tiles_tri(costa_dtype_t dtype, const costa_tri_op_t* ops, int64_t n, const void* src_base,
+                       void* dst_base, const void* scalars, int n_slots, int device) {
+    std::lock_guard<std::recursive_mutex> lk(g_mutex);
+    device_ctx& dc = ctx(device);
+    std::vector<costa_tri_op_t> v(ops, ops + n);
+    for (const auto& t : v)
+        if ((t.op.flags >> COSTA_SLOT_SHIFT) >= uint32_t(std::max(n_slots, 0)))
+            throw error(COSTA_ERR_ARG, "costa_hip_execute_tiles_tri: scalar slot out of range");
+    std::vector<costa_tri_op_t> ord;
+    std::vector<uint64_t> w;
+    const tri_list l = build_tri_work(dtype, v, reinterpret_cast<uintptr_t>(src_base),
+                                      reinterpret_cast<uintptr_t>(dst_base), ord, w);
+    if (!l.n_items) return;
+    dbuf d_ops, d_work, d_scal;
+    d_ops.upload(ord, dc.main);
+    d_work.upload(w, dc.main);
+    const size_t E = dtype_size(dtype);
+    std::vector<unsigned char> sc(static_cast<const unsigned char*>(scalars),
+                                  static_cast<const unsigned char*>(scalars) + size_t(n_slots) * 2 * E);
+    d_scal.upload(sc, dc.main);
+    launch_tri(dtype, static_cast<const costa_tri_op_t*>(d_ops.p), static_cast<const uint64_t*>(d_work.p), l,
+               static_cast<const char*>(src_base), static_cast<char*>(dst_base), d_scal.p, dc.main);
+    HIP_CHECK(hipStreamSynchronize(dc.main));
+    g_stats.tri_items += l.n_items;
 }
 
 void copy_and_transform(costa_dtype_t dtype, int n_rows, int n_cols, const void* src,

@@ -65,6 +65,10 @@ struct job {
     const elayout* C = nullptr;
     char trans = 'N';
     scal s;
+    // triangular transforms: 'U' keeps target elements with j - i >= k, 'L' those with j - i <= k
+    // (i, j from the first row / column of C's layout), 'A' (the default) all of them
+    char uplo = 'A';
+    int k = 0;
 };
 
 // The three tile-op lists of one rank plus the exchange geometry.  Addresses of pack
@@ -80,6 +84,9 @@ struct plan {
     bool mixed() const { return src_dtype != dtype; }
     int rank = 0, n_ranks = 1;
     std::vector<costa_tile_op_t> local_ops, pack_ops, unpack_ops;
+    // triangular transforms: the LOCAL and UNPACK ops of the tiles the mask's diagonal cuts (their
+    // pack ops are ordinary dense copies in pack_ops); empty for every other plan
+    std::vector<costa_tri_op_t> local_tri, unpack_tri;
     std::vector<int64_t> send_counts, send_displs, recv_counts, recv_displs;  // elements
     int64_t send_elems = 0, recv_elems = 0, local_elems = 0;
     std::vector<scal> slots;
@@ -99,6 +106,12 @@ std::vector<job_params> check_jobs(const std::vector<job>& jobs, int n_ranks, co
 std::vector<job_params> check_jobs(const std::vector<job>& jobs, int n_ranks,
                                    costa_dtype_t& src_dtype, costa_dtype_t& dst_dtype);
 const char* dtype_name(costa_dtype_t t);
+// whether some job of the batch is masked (uplo 'U' or 'L')
+bool any_masked(const std::vector<job>& jobs);
+// rows of the bands a tile crossing the mask's diagonal is cut into (plan.cpp decompose): each band
+// gives at most one ordinary tile (its wholly kept columns) and one edge tile narrower than the
+// band is tall, so an edge tile's dense pack op carries fewer than kTriCut dropped columns.
+constexpr int kTriCut = 256;
 // whether some job of the batch converts (A's element type differs from C's)
 bool any_mixed(const std::vector<job>& jobs);
 
@@ -169,6 +182,9 @@ void transform(const std::vector<job>& jobs, struct comm* c, void* user_stream =
                bool async = false);
 void synchronize(struct comm* c);  // wait for every queued transform of c's device
 void resolve_pending();            // fold finished timing brackets into the statistics
+// event time of the edge-tile launches of triangular transforms (profiling on), a part of the
+// statistics' local_ms / unpack_ms
+double tri_phase_ms(bool reset);
 
 void copy_and_transform(costa_dtype_t dtype, int n_rows, int n_cols, const void* src,
                         int src_stride, bool src_cm, void* dst, int dst_stride, bool dst_cm,
@@ -202,6 +218,25 @@ convert_list build_convert_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype
 void launch_convert(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_tile_op_t* d_ops,
                     const uint64_t* d_work, const convert_list& l, const char* src_base,
                     char* dst_base, const void* d_scalars, void* stream /* hipStream_t */);
+
+// ---- edge tiles of triangular transforms (tri_kernels.hip) ----
+// One kernel family, tri_kernel<T>, one workgroup per sub-tile of one costa_tri_op_t; the work
+// items are (op index << 32) | (sub-tile << 1) | whole, `whole` meaning every element of the
+// sub-tile is kept.  Sub-tiles without a kept element are not listed.
+void tri_subtile(costa_dtype_t dtype, int* bf, int* bs);
+struct tri_list {
+    int64_t n_items = 0;
+    bool any_transpose = false;
+};
+// `ordered` = the ops with each side's VEC flag set from its actual address (base + offset)
+tri_list build_tri_work(costa_dtype_t dtype, const std::vector<costa_tri_op_t>& ops, uint64_t src_base,
+                        uint64_t dst_base, std::vector<costa_tri_op_t>& ordered,
+                        std::vector<uint64_t>& work);
+void launch_tri(costa_dtype_t dtype, const costa_tri_op_t* d_ops, const uint64_t* d_work,
+                const tri_list& l, const char* src_base, char* dst_base, const void* d_scalars,
+                void* stream /* hipStream_t */);
+void execute_tiles_tri(costa_dtype_t dtype, const costa_tri_op_t* ops, int64_t n, const void* src_base,
+                       void* dst_base, const void* scalars, int n_slots, int device);
 
 // kernel launcher (tile_kernels.hip); `work` and `ops` are device arrays
 // ops small enough for one wavefront each (tiny path): copy mode up to kTinyCopyBytes of
@@ -337,7 +372,9 @@ struct device_section {
 };
 work_split build_work(costa_dtype_t dtype, const std::vector<costa_tile_op_t>& ops,
                       std::vector<costa_tile_op_t>& ordered, std::vector<uint64_t>& work,
-                      list_kind kind = list_local, device_section* dev = nullptr);
+                      list_kind kind = list_local, device_section* dev = nullptr, bool dst_order = false);
+// (dst_order: the shaped sub-tiles in destination-address order whatever the ops do -- the ordinary
+// LOCAL list of a triangular plan, engine.cpp get_plan)
 // builder of the destination-block groups on a plan-cache miss (costa_hip_set_list_builder,
 // COSTA_LIST_BUILDER): 0 the host, 1 the GPU for lists of at least kDeviceGroupsMin wavefront ops
 // (default), 2 the GPU wherever it applies
@@ -388,6 +425,8 @@ void run_host_pipeline(host_pipeline& hp, int device, void* compute_stream, void
 // the exchange round of every pack op (by its first element) and unpack op (by its last)
 void exchange_round_of_ops(const struct plan& p, int rounds, std::vector<int>& pack_round,
                            std::vector<int>& unpack_round);
+// ... of every edge unpack op (plan::unpack_tri), by the same rule
+void exchange_round_of_tri(const struct plan& p, int rounds, std::vector<int>& unpack_tri_round);
 void release_host_rings();
 // host staging of host-resident layouts: 0 = mirror (every spanned range up, kernels, target
 // ranges down), 1 = pipelined (default; falls back to the mirror where it does not apply)

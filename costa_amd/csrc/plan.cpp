@@ -52,6 +52,12 @@ const char* dtype_name(costa_dtype_t t) {
     return "unknown";
 }
 
+bool any_masked(const std::vector<job>& jobs) {
+    for (const job& jb : jobs)
+        if (jb.uplo != 'A') return true;
+    return false;
+}
+
 bool any_mixed(const std::vector<job>& jobs) {
     for (const job& jb : jobs)
         if (jb.A && jb.C && jb.A->dtype != jb.C->dtype) return true;
@@ -119,6 +125,14 @@ struct side_tile {
     char* ptr;            // first element, stored orientation
     int ld;
     int n_rows, n_cols;   // stored orientation
+    bool edge;            // the mask's diagonal cuts it (triangular transforms)
+};
+
+// the mask of a triangular transform in target coordinates: element (r, c) is kept when
+// (c - oc) - (r - orow) >= k (upper) or <= k (lower); `on` false: no mask
+struct tri_mask {
+    bool on = false, upper = true;
+    int k = 0, orow = 0, oc = 0;
 };
 
 bool key_less(const side_tile& x, const side_tile& y) {
@@ -148,7 +162,13 @@ struct view {
 
 // decompose every local block of `src` (seen through `sv`) by the grid of `dst` (seen
 // through `dv`) and append the tiles (utils.hpp:26-115)
-void decompose(const view& sv, const view& dv, int tag, std::vector<side_tile>& out) {
+// Under a mask each intersection tile is classified in target coordinates: wholly dropped tiles
+// vanish, wholly kept ones are emitted as they are, and a tile the diagonal crosses is cut into row
+// bands of kTriCut target rows from its first row; in each band the wholly dropped columns vanish,
+// the wholly kept ones form one ordinary tile and the columns in between one edge tile (narrower
+// than the band is tall).  The cut depends on the rectangle alone, so both sides of a pair make
+// the same tiles with the same sort keys.
+void decompose(const view& sv, const view& dv, int tag, const tri_mask& mk, std::vector<side_tile>& out) {
     out.reserve(out.size() + sv.L->blocks.size() * 4);
     const size_t elem = dtype_size(sv.L->dtype);  // of the layout being decomposed
     const auto& drs = dv.rsplit();
@@ -169,12 +189,48 @@ void decompose(const view& sv, const view& dv, int tag, std::vector<side_tile>& 
             for (int i = i0; i < i1; ++i) {
                 const interval r(std::max(vr.start, drs[i]), std::min(vr.end, drs[i + 1]));
                 if (r.empty()) continue;
-                // back to the stored orientation of the block (block.cpp:85-99)
-                const tile_side ts = sub_tile(reinterpret_cast<uint64_t>(b.data), b.ld, b.rows.start,
-                                              b.cols.start, row_major, sv.t, r.start, r.end,
-                                              c.start, c.end, elem);
-                out.push_back({dv.owner(i, j), tag, r, c, reinterpret_cast<char*>(ts.ptr), b.ld,
-                               ts.n_rows, ts.n_cols});
+                const int peer = dv.owner(i, j);
+                auto emit = [&](const interval& rr, const interval& cc, bool edge) {
+                    // back to the stored orientation of the block (block.cpp:85-99)
+                    const tile_side ts = sub_tile(reinterpret_cast<uint64_t>(b.data), b.ld, b.rows.start,
+                                                  b.cols.start, row_major, sv.t, rr.start, rr.end,
+                                                  cc.start, cc.end, elem);
+                    out.push_back({peer, tag, rr, cc, reinterpret_cast<char*>(ts.ptr), b.ld, ts.n_rows,
+                                   ts.n_cols, edge});
+                };
+                if (!mk.on) {
+                    emit(r, c, false);
+                    continue;
+                }
+                // v = j - i over the tile, i / j from the mask's origin (64-bit: k is any int)
+                const int64_t k = mk.k;
+                const int64_t i_lo = int64_t(r.start) - mk.orow, i_hi = int64_t(r.end) - 1 - mk.orow;
+                const int64_t j_lo = int64_t(c.start) - mk.oc, j_hi = int64_t(c.end) - 1 - mk.oc;
+                const int64_t v_min = j_lo - i_hi, v_max = j_hi - i_lo;
+                if (mk.upper ? v_max < k : v_min > k) continue;  // wholly dropped
+                if (mk.upper ? v_min >= k : v_max <= k) {        // wholly kept
+                    emit(r, c, false);
+                    continue;
+                }
+                auto clampc = [&](int64_t j) {  // relative column -> a column of [c.start, c.end]
+                    return int(std::max<int64_t>(c.start, std::min<int64_t>(c.end, j + mk.oc)));
+                };
+                for (int b0 = r.start; b0 < r.end; b0 += kTriCut) {
+                    const int b1 = std::min(r.end, b0 + kTriCut);
+                    const interval rr(b0, b1);
+                    const int64_t ib0 = int64_t(b0) - mk.orow, ib1 = int64_t(b1) - 1 - mk.orow;
+                    if (mk.upper) {
+                        // column j: wholly dropped when j - ib0 < k, wholly kept when j - ib1 >= k
+                        const int e0 = clampc(k + ib0), e1 = std::max(e0, clampc(k + ib1));
+                        if (e1 > e0) emit(rr, interval(e0, e1), true);
+                        if (c.end > e1) emit(rr, interval(e1, c.end), false);
+                    } else {
+                        // column j: wholly kept when j - ib0 <= k, wholly dropped when j - ib1 > k
+                        const int e0 = clampc(k + ib0 + 1), e1 = std::max(e0, clampc(k + ib1 + 1));
+                        if (e0 > c.start) emit(rr, interval(c.start, e0), false);
+                        if (e1 > e0) emit(rr, interval(e0, e1), true);
+                    }
+                }
             }
         }
     }
@@ -269,6 +325,17 @@ std::vector<job_params> check_jobs(const std::vector<job>& jobs, int n_ranks, co
         const char op = upper(jb.trans);
         if (op != 'N' && op != 'T' && op != 'C')
             throw error(COSTA_ERR_ARG, "costa::transform: trans must be 'N', 'T' or 'C'");
+        const char ul = upper(jb.uplo);
+        if (ul != 'A' && ul != 'U' && ul != 'L')
+            throw error(COSTA_ERR_ARG, "costa::transform: uplo must be 'U' or 'L'");
+        if (ul != 'A' && src_dtype != dtype)
+            throw error(COSTA_ERR_ARG,
+                        std::string("costa::transform: a triangular (masked) transform needs A and C of "
+                                    "one element type, not ") +
+                            dtype_name(src_dtype) + " and " + dtype_name(dtype));
+        if (ul != 'A' && jobs.size() > 1)
+            throw error(COSTA_ERR_ARG, "costa::transform: batches of triangular (masked) layout pairs "
+                                       "are not supported");
         const bool tr = op != 'N';            // utils.cpp:9 (if_should_transpose)
         const bool cj = op == 'C' && cplx;    // communication_data.cpp:31-33
         out.push_back({tr, cj, jb.A->ordering == 'C', jb.C->ordering == 'C',
@@ -304,10 +371,18 @@ std::unique_ptr<plan> make_plan(const std::vector<job>& jobs, int rank, int n_ra
         for (size_t t = 0; t < jobs.size(); ++t) {
             const job& jb = jobs[t];
             const bool tr = tags[t].transpose;
+            tri_mask mk;
+            if (upper(jb.uplo) != 'A') {
+                mk.on = true;
+                mk.upper = upper(jb.uplo) == 'U';
+                mk.k = jb.k;
+                mk.orow = jb.C->rows_split.front();
+                mk.oc = jb.C->cols_split.front();
+            }
             if (send_side)
-                decompose(view{jb.A, tr}, view{jb.C, false}, int(t), out);  // prepare_to_send
+                decompose(view{jb.A, tr}, view{jb.C, false}, int(t), mk, out);  // prepare_to_send
             else
-                decompose(view{jb.C, false}, view{jb.A, tr}, int(t), out);  // prepare_to_recv
+                decompose(view{jb.C, false}, view{jb.A, tr}, int(t), mk, out);  // prepare_to_recv
         }
         std::sort(out.begin(), out.end(), key_less);
     };
@@ -349,6 +424,12 @@ std::unique_ptr<plan> make_plan(const std::vector<job>& jobs, int rank, int n_ra
 
     // target coordinates of every op, for the locality hint (costa_tile_op_t::order)
     std::vector<const side_tile*> at_pack, at_unpack, at_local;
+    // the edge op of a tile the mask's diagonal cuts, from its ordinary op (tile_op.hpp tri_op)
+    auto edge_op = [&](const costa_tile_op_t& op, const side_tile& m, const tag_info& ti) {
+        const job& jb = jobs[size_t(m.tag)];
+        const int e = (m.cols.start - jb.C->cols_split.front()) - (m.rows.start - jb.C->rows_split.front());
+        return tri_op(op, ti.a_cm, ti.transpose, upper(jb.uplo) == 'U', jb.k, e);
+    };
 
     // ---- send side: local tiles stay, remote tiles are packed in sorted order ----
     std::vector<const side_tile*> local_src;
@@ -385,10 +466,15 @@ std::unique_ptr<plan> make_plan(const std::vector<job>& jobs, int rank, int n_ra
         const int nr = ti.transpose ? m.n_cols : m.n_rows;
         const int nc = ti.transpose ? m.n_rows : m.n_cols;
         const bool wt = will_tr(ti, ti.a_cm, ti.c_cm);
-        p->unpack_ops.push_back(make_tile_op(nr, nc, uint64_t(off) * EP, 0, ti.a_cm, uint64_t(m.ptr),
-                                             m.ld, ti.c_cm, ti.transpose, ti.conj,
-                                             kind_of(ti, wt), uint32_t(m.tag), EP, EC));
-        at_unpack.push_back(&m);
+        const costa_tile_op_t op = make_tile_op(nr, nc, uint64_t(off) * EP, 0, ti.a_cm, uint64_t(m.ptr),
+                                                m.ld, ti.c_cm, ti.transpose, ti.conj, kind_of(ti, wt),
+                                                uint32_t(m.tag), EP, EC);
+        if (m.edge) {
+            p->unpack_tri.push_back(edge_op(op, m, ti));
+        } else {
+            p->unpack_ops.push_back(op);
+            at_unpack.push_back(&m);
+        }
         p->recv_counts[size_t(m.peer)] += n;
         off += n;
     }
@@ -400,13 +486,20 @@ std::unique_ptr<plan> make_plan(const std::vector<job>& jobs, int rank, int n_ra
     for (size_t k = 0; k < local_src.size(); ++k) {
         const side_tile& s = *local_src[k];
         const side_tile& d = *local_dst[k];
-        if (!key_equal(s, d) || int64_t(s.n_rows) * s.n_cols != int64_t(d.n_rows) * d.n_cols)
+        if (!key_equal(s, d) || s.edge != d.edge ||
+            int64_t(s.n_rows) * s.n_cols != int64_t(d.n_rows) * d.n_cols)
             throw error(COSTA_ERR_INTERNAL, "costa: local tiles do not pair up");
         const tag_info& ti = tags[size_t(s.tag)];
         const bool wt = will_tr(ti, ti.a_cm, ti.c_cm);
-        p->local_ops.push_back(make_tile_op(s.n_rows, s.n_cols, uint64_t(s.ptr), s.ld, ti.a_cm,
-                                            uint64_t(d.ptr), d.ld, ti.c_cm, ti.transpose, ti.conj,
-                                            kind_of(ti, wt), uint32_t(s.tag), EA, EC));
+        const costa_tile_op_t op = make_tile_op(s.n_rows, s.n_cols, uint64_t(s.ptr), s.ld, ti.a_cm,
+                                                uint64_t(d.ptr), d.ld, ti.c_cm, ti.transpose, ti.conj,
+                                                kind_of(ti, wt), uint32_t(s.tag), EA, EC);
+        if (d.edge) {
+            p->local_tri.push_back(edge_op(op, d, ti));
+            p->local_elems += tri_kept(p->local_tri.back());
+            continue;
+        }
+        p->local_ops.push_back(op);
         at_local.push_back(&d);
         p->local_elems += int64_t(s.n_rows) * s.n_cols;
     }
@@ -422,6 +515,8 @@ std::unique_ptr<plan> make_plan(const std::vector<job>& jobs, int rank, int n_ra
     for (auto& op : p->local_ops) p->local_bytes += op_alg_bytes(op, EA, EC);
     for (auto& op : p->pack_ops) p->pack_bytes += op_alg_bytes(op, EA, EP);
     for (auto& op : p->unpack_ops) p->unpack_bytes += op_alg_bytes(op, EP, EC);
+    for (auto& t : p->local_tri) p->local_bytes += op_alg_bytes(t, EC);  // kept elements only
+    for (auto& t : p->unpack_tri) p->unpack_bytes += op_alg_bytes(t, EC);
     return p;
 }
 

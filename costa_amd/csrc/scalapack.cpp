@@ -5,6 +5,9 @@
 // Reference behaviour followed (eth-cscs/COSTA):
 //   costa::pxgemr2d<T>     pxgemr2d/costa_pxgemr2d.cpp:14-171
 //   costa::pxtran_op<T>    pxtran_op/costa_pxtran_op.cpp:15-175  (sub(A) is n x m: :68-69)
+//   p?trmr2d               no reference counterpart: ScaLAPACK REDIST's trapezoidal copy, through
+//                          costa::transform_triangular (descriptors, grids and communicators as
+//                          p?gemr2d)
 //   descriptor fields      scalapack.hpp:9-45; leading_dimension scalapack.cpp:37-39
 //   ctxt -> MPI_Comm       scalapack.cpp:42-53 (Cblacs_get(ctxt, 10) + Cblacs2sys_handle)
 //   communicator           comm_union(comm_a, comm_c) (scalapack.cpp:172-185, costa_pxgemr2d.cpp:60)
@@ -279,6 +282,45 @@ void pxgemr2d(int m, int n, const T* a, int ia, int ja, const int* desca, T* c, 
 }
 
 template <typename T>
+void run_tri(costa::grid_layout<T>& A, costa::grid_layout<T>& C, char uplo, int k, MPI_Comm comm) {
+#if defined(COSTA_SCALAPACK_TEST_HOOK_TRI)
+    COSTA_SCALAPACK_TEST_HOOK_TRI(A, C, uplo, k, comm);
+#elif defined(COSTA_SCALAPACK_TEST_HOOK)
+    throw std::runtime_error("p?trmr2d is not hooked in this test build");
+#else
+    costa::transform_triangular<T>(A, C, 'N', uplo, k, T(1), T(0), costa::comm_from_mpi(comm));
+#endif
+}
+
+// p?trmr2d: the trapezoidal part of sub(A) (m x n) copied into sub(B).  ScaLAPACK's trapezoid:
+// 'U' hangs from the bottom-right corner for m > n (j - i >= -(m - n)), 'L' extends to the right
+// for n > m (j - i <= n - m); diag 'U' leaves the diagonal out.
+template <typename T>
+void pxtrmr2d(char uplo, char diag, int m, int n, const T* a, int ia, int ja, const int* desca, T* c,
+              int ic, int jc, const int* descc, int ictxt) {
+    if (m == 0 || n == 0) return;
+    try {
+        const char ul = char(std::toupper(static_cast<unsigned char>(uplo)));
+        const bool unit = std::toupper(static_cast<unsigned char>(diag)) == 'U';
+        if (ul != 'U' && ul != 'L') throw std::runtime_error("uplo must be 'U' or 'L'");
+        const int k = ul == 'U' ? -std::max(m - n, 0) + int(unit) : std::max(n - m, 0) - int(unit);
+        const grid_info gi = grid_of(ictxt);
+        if (!gi.member()) return;  // not a process of the call's context: nothing to do
+        call_comm cc;
+        grid_comm(ictxt, gi, cc);
+        MPI_Comm comm = cc.comm;
+        int P = 1;
+        MPI_Comm_size(comm, &P);
+        const auto d = distributions(comm, {desca, descc});
+        auto A = layout_of<T>(d[0], ia, ja, m, n, const_cast<T*>(a), desca[8], P);
+        auto C = layout_of<T>(d[1], ic, jc, m, n, c, descc[8], P);
+        run_tri<T>(A, C, ul, k, comm);
+    } catch (const std::exception& e) {
+        fatal("p?trmr2d", e);
+    }
+}
+
+template <typename T>
 void pxtran(int m, int n, T alpha, const T* a, int ia, int ja, const int* desca, T beta, T* c,
             int ic, int jc, const int* descc, char op) {
     if (m == 0 || n == 0) return;
@@ -329,6 +371,15 @@ using zd = std::complex<double>;
     void NAME(fn##_)(COSTA_TRAN_ARGS(TI)) { NAME(fn)(m, n, alpha, a, ia, ja, desca, beta, c, ic, jc, descc); } \
     void NAME(fn##__)(COSTA_TRAN_ARGS(TI)) { NAME(fn)(m, n, alpha, a, ia, ja, desca, beta, c, ic, jc, descc); }
 
+// (Fortran callers append the hidden lengths of uplo and diag after ictxt; they are ignored)
+#define TRMR2D(fn, T, TI)                                                                       \
+    void NAME(fn)(COSTA_TRMR2D_ARGS(TI)) {                                                      \
+        pxtrmr2d<T>(*uplo, *diag, *m, *n, reinterpret_cast<const T*>(a), *ia, *ja, desca,       \
+                    reinterpret_cast<T*>(b), *ib, *jb, descb, *ictxt);                          \
+    }                                                                                           \
+    void NAME(fn##_)(COSTA_TRMR2D_ARGS(TI)) { NAME(fn)(uplo, diag, m, n, a, ia, ja, desca, b, ib, jb, descb, ictxt); } \
+    void NAME(fn##__)(COSTA_TRMR2D_ARGS(TI)) { NAME(fn)(uplo, diag, m, n, a, ia, ja, desca, b, ib, jb, descb, ictxt); }
+
 extern "C" {
 GEMR2D(psgemr2d, float, float)
 GEMR2D(pdgemr2d, double, double)
@@ -341,9 +392,19 @@ TRAN(pztranu, zd, double, 'T')
 TRAN(pctranc, zf, float, 'C')
 TRAN(pztranc, zd, double, 'C')
 
+TRMR2D(pstrmr2d, float, float)
+TRMR2D(pdtrmr2d, double, double)
+TRMR2D(pctrmr2d, zf, float)
+TRMR2D(pztrmr2d, zd, double)
+
 #ifdef COSTA_PREFIXED
 GEMR2D(pigemr2d, int, int)
+TRMR2D(pitrmr2d, int, int)
 #else
+void PSTRMR2D(COSTA_TRMR2D_ARGS(float)) { pstrmr2d(uplo, diag, m, n, a, ia, ja, desca, b, ib, jb, descb, ictxt); }
+void PDTRMR2D(COSTA_TRMR2D_ARGS(double)) { pdtrmr2d(uplo, diag, m, n, a, ia, ja, desca, b, ib, jb, descb, ictxt); }
+void PCTRMR2D(COSTA_TRMR2D_ARGS(float)) { pctrmr2d(uplo, diag, m, n, a, ia, ja, desca, b, ib, jb, descb, ictxt); }
+void PZTRMR2D(COSTA_TRMR2D_ARGS(double)) { pztrmr2d(uplo, diag, m, n, a, ia, ja, desca, b, ib, jb, descb, ictxt); }
 void PSGEMR2D(COSTA_GEMR2D_ARGS(float)) { psgemr2d(m, n, a, ia, ja, desca, c, ic, jc, descc, ictxt); }
 void PDGEMR2D(COSTA_GEMR2D_ARGS(double)) { pdgemr2d(m, n, a, ia, ja, desca, c, ic, jc, descc, ictxt); }
 void PCGEMR2D(COSTA_GEMR2D_ARGS(float)) { pcgemr2d(m, n, a, ia, ja, desca, c, ic, jc, descc, ictxt); }

@@ -73,6 +73,39 @@ COSTA_HD inline costa_tile_op_t tile_op(int n_rows, int n_cols, uint64_t src, in
                    kind, slot, elem, elem);
 }
 
+// The edge tile of a triangular transform.  `op` is the tile's ordinary op; its first element sits
+// at target (C) position (r0, c0) counted from the mask's origin, `e` = c0 - r0, and the mask keeps
+// target element (i, j) when j - i >= k ('U') or j - i <= k ('L').  The op's source is A's stored
+// tile (or its dense image in the package), column-major when `src_cm`, seen transposed when
+// `transpose` (the job's op != 'N'): its fast index f walks target rows when src_cm != transpose,
+// target columns otherwise.  So j - i = e + (s - f) or e - (s - f), and the mask becomes
+// s - f >= diag or s - f <= diag (COSTA_TRI_LE) for every ordering / transpose combination.
+COSTA_HD inline costa_tri_op_t tri_op(const costa_tile_op_t& op, bool src_cm, bool transpose, bool upper,
+                                      int k, int e) {
+    costa_tri_op_t t{};
+    t.op = op;
+    const bool f_is_row = src_cm != transpose;
+    // f_is_row:  'U' s - f >= k - e,  'L' s - f <= k - e;  else:  'U' s - f <= e - k,  'L' s - f >= e - k
+    const int64_t d = f_is_row ? int64_t(k) - e : int64_t(e) - k;
+    const int64_t lim = int64_t(1) << 30;  // (beyond the op either way: clamped, no overflow)
+    t.diag = int32_t(d < -lim ? -lim : d > lim ? lim : d);
+    if (f_is_row != upper) t.op.flags |= COSTA_TRI_LE;
+    return t;
+}
+
+// kept elements of an edge op
+COSTA_HD inline int64_t tri_kept(const costa_tri_op_t& t) {
+    const bool le = t.op.flags & COSTA_TRI_LE;
+    int64_t n = 0;
+    for (int64_t s = 0; s < t.op.ns; ++s) {
+        // GE: f <= s - diag;  LE: f >= s - diag
+        const int64_t x = s - t.diag;
+        const int64_t c = le ? int64_t(t.op.nf) - x : x + 1;
+        n += c < 0 ? 0 : c > t.op.nf ? t.op.nf : c;
+    }
+    return n;
+}
+
 // algorithmic HBM bytes of one op: read + write (+ read of the target when beta != 0)
 COSTA_HD inline int64_t op_alg_bytes(const costa_tile_op_t& op, uint64_t elem) {
     const uint32_t k = (op.flags & COSTA_SCALE_MASK) >> COSTA_SCALE_SHIFT;
@@ -85,6 +118,12 @@ COSTA_HD inline int64_t op_alg_bytes(const costa_tile_op_t& op, uint64_t src_ele
     const int64_t n = int64_t(op.nf) * op.ns;
     return int64_t(src_elem) * n * (k != COSTA_SCALE_ZERO) +
            int64_t(dst_elem) * n * (1 + (k == COSTA_SCALE_AXPBY));
+}
+
+// ... of an edge op: kept elements only
+COSTA_HD inline int64_t op_alg_bytes(const costa_tri_op_t& t, uint64_t elem) {
+    const uint32_t k = (t.op.flags & COSTA_SCALE_MASK) >> COSTA_SCALE_SHIFT;
+    return int64_t(elem) * tri_kept(t) * (1 + (k != COSTA_SCALE_ZERO) + (k == COSTA_SCALE_AXPBY));
 }
 
 }  // namespace engine

@@ -60,6 +60,17 @@ typename std::enable_if<!std::is_same<Ta, Tc>::value>::type
 transform(grid_layout<Ta>& initial_layout, grid_layout<Tc>& final_layout, char trans, Tc alpha,
           Tc beta, costa_comm_t comm);
 
+// Triangular / trapezoidal transform (MI355X-native; costa_hip.h, "triangular"):
+//   C(i, j) = beta*C(i, j) + alpha*op(A)(i, j)  where j - i >= k (uplo 'U') or j - i <= k ('L'),
+// every other element of C untouched, bit for bit; i, j count from the first row and column of
+// the matrix C's layout describes.  Kept elements equal transform()'s; tiles outside the mask are
+// neither packed nor exchanged.  With trans 'T' / 'C' and a strict mask ('L' with k <= -1, 'U'
+// with k >= 1) A and C may be layouts over the same device buffer of a square matrix: the call
+// then fills one triangle from the (conjugate-)transposed other one in place.
+template <typename T>
+void transform_triangular(grid_layout<T>& initial_layout, grid_layout<T>& final_layout, char trans,
+                          char uplo, int k, T alpha, T beta, costa_comm_t comm);
+
 // Elements each rank pair exchanges when g_init is transformed into g_final with op `trans`
 // (reference transform.hpp:44-48 / transform.cpp:9-44): every block of g_init (transposed view
 // for 'T' / 'C') is intersected with the blocks of g_final; edge {a, b} (a <= b) adds the area
@@ -208,6 +219,11 @@ template <typename T>
 void transform(std::vector<layout_ref<T>>& A, std::vector<layout_ref<T>>& C, const char* trans,
                const T* alpha, const T* beta, MPI_Comm comm) {
     transform<T>(A, C, trans, alpha, beta, comm_from_mpi(comm));
+}
+template <typename T>
+void transform_triangular(grid_layout<T>& A, grid_layout<T>& C, char trans, char uplo, int k, T alpha,
+                          T beta, MPI_Comm comm) {
+    transform_triangular<T>(A, C, trans, uplo, k, alpha, beta, comm_from_mpi(comm));
 }
 #endif  // MPI_VERSION
 

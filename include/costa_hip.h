@@ -109,6 +109,20 @@ typedef struct {
                        tiles sharing partially used cache lines run together.  0 = none. */
 } costa_tile_op_t; /* 40 bytes */
 
+/* ---- edge tile of a triangular (masked) transform: a tile op that writes only the elements on
+ * one side of a diagonal.  In the op's own source coordinates (f, s) element (f, s) is kept when
+ *   s - f >= diag      (COSTA_TRI_LE clear)
+ *   s - f <= diag      (COSTA_TRI_LE set)
+ * whatever the orderings and the transpose; kept elements are computed exactly as costa_tile_op_t
+ * computes them, every other destination byte is neither read nor written, and source values at
+ * dropped positions never influence the result. */
+#define COSTA_TRI_LE 0x40u /* flag bit 6 of op.flags: the sense of the comparison */
+typedef struct {
+    costa_tile_op_t op;
+    int32_t diag;
+    int32_t pad; /* 0 */
+} costa_tri_op_t; /* 48 bytes */
+
 /* ---- library ---- */
 const char* costa_hip_last_error(void);
 int costa_hip_version(void); /* major*10000 + minor*100 + patch */
@@ -181,6 +195,30 @@ int costa_hip_transform_batch(int n, const costa_layout_t* A, const costa_layout
                               const char* trans, const void* alpha, const void* beta,
                               costa_comm_t comm);
 
+/* ---- triangular / trapezoidal transforms (MI355X-native; ScaLAPACK's p?trmr2d is the copy) ----
+ *   C(i, j) = beta*C(i, j) + alpha*op(A)(i, j)   where keep(i, j)
+ *   C(i, j) untouched, bit for bit               elsewhere
+ *   keep(i, j) = (j - i >= k) for uplo 'U' (numpy triu(k)), (j - i <= k) for uplo 'L' (tril(k)),
+ * i, j counted from the first row and column of the matrix C's layout describes (its
+ * rows_split / cols_split front; the sub-matrix origin of a block-cyclic layout built over a
+ * sub-matrix).  `uplo` is 'U' or 'L' in either case (anything else: COSTA_ERR_ARG), `k` any int: a
+ * mask that keeps everything is the ordinary transform, one that keeps nothing is a no-op.  Kept
+ * elements equal the ordinary transform's bit for bit; dropped bytes of C are never written, and
+ * A's values at dropped positions (NaN, Inf) never reach C.  Tiles wholly outside the mask are
+ * neither packed, exchanged nor unpacked.  A and C must share one dtype (COSTA_ERR_ARG otherwise);
+ * host-resident layouts take the mirror staging, with C's ranges uploaded first.
+ *
+ * In-place fill of the other triangle: A and C may be layouts over the SAME device buffer of a
+ * square matrix when trans is 'T' or 'C' and the mask is strict (uplo 'L' with k <= -1, or 'U'
+ * with k >= 1): the elements read for kept positions and the elements written are then disjoint,
+ * and values read at dropped positions are discarded.  Device-resident layouts, one rank (also
+ * through the loopback test mode). */
+int costa_hip_transform_tri(costa_layout_t A, costa_layout_t C, char trans, char uplo, int k,
+                            const void* alpha, const void* beta, costa_comm_t comm);
+int costa_hip_transform_tri_async(costa_layout_t A, costa_layout_t C, char trans, char uplo, int k,
+                                  const void* alpha, const void* beta, costa_comm_t comm,
+                                  void* stream);
+
 /* ---- stream-ordered variants (MI355X-native; no reference counterpart) ----
  * Enqueue the transform and return.  Layouts must be device-resident.  `stream` (a hipStream_t,
  * may be NULL) is joined at entry and made to wait for the result, so work queued on it after
@@ -215,6 +253,17 @@ int costa_hip_execute_tiles_mixed(costa_dtype_t src_dtype, costa_dtype_t dst_dty
  * source's fast (*bf) and slow (*bs) dimension */
 int costa_hip_convert_subtile(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, int* bf, int* bs);
 
+/* edge ops (costa_tri_op_t) of one dtype in ONE launch of tri_kernel; the VEC flags are recomputed
+ * from each side's actual address */
+int costa_hip_execute_tiles_tri(costa_dtype_t dtype, const costa_tri_op_t* ops, int64_t n,
+                                const void* src_base, void* dst_base, const void* scalars,
+                                int n_slots, int device);
+/* rows of the bands the planner cuts a tile crossing the mask's diagonal into */
+int costa_hip_tri_cut(void);
+/* the sub-tile one workgroup of tri_kernel runs: elements along the source's fast (*bf) and slow
+ * (*bs) dimension */
+int costa_hip_tri_subtile(costa_dtype_t dtype, int* bf, int* bs);
+
 /* ---- plan inspection (host only, never touches a GPU) ----
  * Plans the transform for rank `rank` of `nranks` and copies the three descriptor
  * lists out.  Offsets of pack destinations / unpack sources are byte offsets into the
@@ -244,6 +293,22 @@ int costa_hip_plan_export(int n, const costa_layout_t* A, const costa_layout_t* 
                           int64_t* send_counts, int64_t* send_displs, int64_t* recv_counts,
                           int64_t* recv_displs, void* scalars);
 
+/* The plan of a triangular transform (costa_hip_transform_tri): the ordinary lists hold the tiles
+ * wholly inside the mask (and the dense pack ops of edge tiles), local_tri / unpack_tri the edge
+ * tiles that write C. */
+typedef struct {
+    costa_plan_info_t base;
+    int64_t n_local_tri;
+    int64_t n_unpack_tri;
+} costa_tri_plan_info_t;
+int costa_hip_plan_export_tri(costa_layout_t A, costa_layout_t C, char trans, char uplo, int k,
+                              const void* alpha, const void* beta, int rank, int nranks,
+                              costa_tri_plan_info_t* info, costa_tile_op_t* local_ops,
+                              costa_tile_op_t* pack_ops, costa_tile_op_t* unpack_ops,
+                              costa_tri_op_t* local_tri, costa_tri_op_t* unpack_tri,
+                              int64_t* send_counts, int64_t* send_displs, int64_t* recv_counts,
+                              int64_t* recv_displs, void* scalars);
+
 /* ---- measurement ----
  * With profiling on, every kernel launch and exchange is bracketed by HIP events on
  * the stream it runs on; the sums are read (and optionally reset) here. */
@@ -272,7 +337,12 @@ typedef struct {
                              destination-block group launch (no tiny_kernel launch of their own) */
     int64_t convert_items; /* sub-tiles run by convert_kernel (the converting lists of mixed
                               transforms, costa_hip_execute_tiles_mixed) */
+    int64_t tri_items; /* sub-tiles run by tri_kernel (the edge tiles of triangular transforms,
+                          costa_hip_execute_tiles_tri) */
 } costa_stats_t;
+/* of local_ms + unpack_ms: the event time of the edge-tile launches of triangular transforms since
+ * the last reset (their share of a masked call, tools/bench_tri.py) */
+int costa_hip_tri_phase_ms(double* ms, int reset);
 int costa_hip_set_profiling(int on);
 int costa_hip_get_stats(costa_stats_t* out, int reset);
 /* drop cached plans and device workspaces of this process */
