@@ -27,7 +27,8 @@ from typing import Iterable, Sequence
 import numpy as np
 
 __all__ = [
-    "CostaError", "lib", "FLOAT", "DOUBLE", "CFLOAT", "CDOUBLE", "INT32", "dtype_code",
+    "CostaError", "lib", "FLOAT", "DOUBLE", "CFLOAT", "CDOUBLE", "INT32", "HALF", "BFLOAT16",
+    "dtype_code",
     "np_dtype", "Layout", "block_cyclic_layout", "custom_layout", "Comm", "transform",
     "transform_batch", "transform_async", "transform_batch_async", "synchronize", "transformer", "copy_and_transform", "execute_tiles", "execute_tiles_mixed",
     "convert_subtile", "TileOp", "TriOp", "TRI_OP_DTYPE", "transform_tri", "transform_tri_async",
@@ -36,8 +37,15 @@ __all__ = [
 ]
 
 FLOAT, DOUBLE, CFLOAT, CDOUBLE, INT32 = 0, 1, 2, 3, 4
+# 2-byte element types (costa_hip.h, "Half precision"): IEEE binary16 and bfloat16, raw bits.  The
+# pairs are H -> H, FLOAT -> H and H -> FLOAT on device-resident layouts, and alpha / beta are fp32.
+HALF, BFLOAT16 = 5, 6
 _NP = {FLOAT: np.float32, DOUBLE: np.float64, CFLOAT: np.complex64,
-       CDOUBLE: np.complex128, INT32: np.int32}
+       CDOUBLE: np.complex128, INT32: np.int32, HALF: np.float16, BFLOAT16: np.uint16}
+# torch dtype objects by name (recognised without importing torch)
+_TORCH = {"torch.float32": FLOAT, "torch.float64": DOUBLE, "torch.complex64": CFLOAT,
+          "torch.complex128": CDOUBLE, "torch.int32": INT32, "torch.float16": HALF,
+          "torch.bfloat16": BFLOAT16}
 
 TILE_TRANSPOSE, TILE_CONJ, TILE_VEC_SRC, TILE_VEC_DST = 0x1, 0x2, 0x4, 0x8
 SCALE_BITCOPY, SCALE_ZERO, SCALE_ALPHA, SCALE_AXPBY = 0, 1, 2, 3
@@ -62,17 +70,29 @@ class CostaError(RuntimeError):
 
 
 def dtype_code(dtype) -> int:
+    """The element-type code of a code, a numpy dtype (``np.float16`` is HALF; numpy has no
+    bfloat16) or a torch dtype object (``torch.bfloat16`` is BFLOAT16)."""
     if isinstance(dtype, int):
         return dtype
+    if type(dtype).__module__.split(".")[0] == "torch":
+        if str(dtype) in _TORCH:
+            return _TORCH[str(dtype)]
+        raise ValueError(f"unsupported element type {dtype}")
     d = np.dtype(dtype)
     for k, v in _NP.items():
-        if np.dtype(v) == d:
+        if k != BFLOAT16 and np.dtype(v) == d:
             return k
     raise ValueError(f"unsupported element type {dtype}")
 
 
 def np_dtype(code: int):
+    """numpy type holding one element of ``code``; BFLOAT16 is ``np.uint16`` (its bits)."""
     return _NP[code]
+
+
+def _scalar_code(a_code: int, c_code: int) -> int:
+    """the type of alpha / beta of an (A, C) pair: C's, FLOAT when A or C is a 2-byte type"""
+    return FLOAT if a_code in (HALF, BFLOAT16) or c_code in (HALF, BFLOAT16) else c_code
 
 
 class _Block(C.Structure):
@@ -236,6 +256,8 @@ def _ptr(p) -> int:
 
 
 def _scalar_bytes(code: int, x) -> bytes:
+    if code in (HALF, BFLOAT16):  # the scalars of half-precision transforms are fp32
+        code = FLOAT
     if code == DOUBLE:
         return struct.pack("<d", float(x))
     if code == CDOUBLE:
@@ -397,7 +419,9 @@ def transform(A: Layout, Cl: Layout, comm: Comm, trans: str = "N", alpha=1, beta
 
     A and C may differ in dtype (FLOAT <-> DOUBLE, CFLOAT <-> CDOUBLE; device-resident layouts):
     sub(A) is converted to C's type inside the tile kernels, and alpha / beta are of C's type
-    (costa_hip.h, "Mixed precision")."""
+    (costa_hip.h, "Mixed precision").  HALF / BFLOAT16 layouts pair with themselves and with FLOAT
+    (H -> H, FLOAT -> H, H -> FLOAT): fp32 arithmetic with one rounding at the store, alpha / beta
+    fp32 (costa_hip.h, "Half precision")."""
     transform_batch([A], [Cl], comm, [trans], [alpha], [beta])
 
 
@@ -406,7 +430,7 @@ def transform_batch(As: Sequence[Layout], Cs: Sequence[Layout], comm: Comm,
     """Several layout pairs in one exchange (reference transform.hpp:38-43)."""
     n = len(As)
     assert n == len(Cs) and n > 0
-    code = Cs[0].dtype  # alpha / beta are elements of C's type
+    code = _scalar_code(As[0].dtype, Cs[0].dtype)  # alpha / beta: C's type (half pairs: fp32)
     trans = list(trans) if trans is not None else ["N"] * n
     alpha = list(alpha) if alpha is not None else [1] * n
     beta = list(beta) if beta is not None else [0] * n
@@ -426,7 +450,7 @@ def transform_async(A: Layout, Cl: Layout, comm: Comm, trans: str = "N", alpha=1
 
 def transform_batch_async(As, Cs, comm: Comm, trans=None, alpha=None, beta=None, stream=None):
     n = len(As)
-    code = Cs[0].dtype  # alpha / beta are elements of C's type
+    code = _scalar_code(As[0].dtype, Cs[0].dtype)  # alpha / beta: C's type (half pairs: fp32)
     trans = list(trans) if trans is not None else ["N"] * n
     alpha = list(alpha) if alpha is not None else [1] * n
     beta = list(beta) if beta is not None else [0] * n
@@ -498,10 +522,11 @@ def execute_tiles_mixed(src_dtype, dst_dtype, ops: np.ndarray, scalars: np.ndarr
                         dst_base=0, device: int = 0):
     """Run a list of converting tile ops (sources of ``src_dtype``, destinations of ``dst_dtype``:
     FLOAT <-> DOUBLE or CFLOAT <-> CDOUBLE) in one batched launch; ``scalars`` are of
-    ``dst_dtype`` (costa_hip_execute_tiles_mixed)."""
+    ``dst_dtype`` (costa_hip_execute_tiles_mixed).  Half-precision pairs ((H, H), (FLOAT, H),
+    (H, FLOAT) with H = HALF or BFLOAT16) run here too, with fp32 ``scalars``."""
     sc_, dc_ = dtype_code(src_dtype), dtype_code(dst_dtype)
     ops = np.ascontiguousarray(ops, dtype=TILE_OP_DTYPE)
-    sc = np.ascontiguousarray(scalars, dtype=_NP[dc_]).reshape(-1)
+    sc = np.ascontiguousarray(scalars, dtype=_NP[_scalar_code(sc_, dc_)]).reshape(-1)
     assert sc.size % 2 == 0
     _check(lib().costa_hip_execute_tiles_mixed(sc_, dc_, ops.ctypes.data_as(C.POINTER(TileOp)),
                                                ops.size, C.c_void_p(_ptr(src_base)),
@@ -599,7 +624,7 @@ def plan_export(As: Sequence[Layout], Cs: Sequence[Layout], rank: int, nranks: i
     """Tile-op lists of `rank`: by the host planner (never touches a GPU), or with ``device``
     set by the GPU planner of that device (costa_hip_plan_export_device)."""
     n = len(As)
-    code = Cs[0].dtype  # alpha / beta are elements of C's type
+    code = _scalar_code(As[0].dtype, Cs[0].dtype)  # alpha / beta: C's type (half pairs: fp32)
     trans = list(trans) if trans is not None else ["N"] * n
     alpha = list(alpha) if alpha is not None else [1] * n
     beta = list(beta) if beta is not None else [0] * n

@@ -75,6 +75,8 @@ void with_type(costa_dtype_t t, F&& f) {
     case COSTA_CFLOAT: f(std::complex<float>{}); return;
     case COSTA_CDOUBLE: f(std::complex<double>{}); return;
     case COSTA_INT32: f(int{}); return;
+    case COSTA_HALF: f(costa::half_bits{}); return;
+    case COSTA_BFLOAT16: f(costa::bfloat16_bits{}); return;
     }
     throw costa::engine::error(COSTA_ERR_ARG, "unknown dtype");
 }
@@ -96,7 +98,8 @@ void check_handles(int n, const costa_layout_t* A, const costa_layout_t* C) {
 std::vector<job> make_jobs(int n, const costa_layout_t* A, const costa_layout_t* C,
                            const char* trans, const void* alpha, const void* beta) {
     check_handles(n, A, C);
-    const costa_dtype_t t = C[0]->e.dtype;  // alpha / beta are elements of C's type
+    // alpha / beta are elements of C's type (fp32 when A or C is a 2-byte type)
+    const costa_dtype_t t = costa::engine::compute_dtype(A[0]->e.dtype, C[0]->e.dtype);
     const size_t E = dtype_size(t);
     std::vector<job> jobs(static_cast<size_t>(n));
     for (int i = 0; i < n; ++i) {
@@ -155,7 +158,7 @@ int export_plan(F make, int n, const costa_layout_t* A, const costa_layout_t* C,
         cp(p->recv_counts, recv_counts);
         cp(p->recv_displs, recv_displs);
         if (scalars) {
-            const size_t E = dtype_size(p->dtype);
+            const size_t E = dtype_size(p->scalar_dtype());
             auto* out = static_cast<unsigned char*>(scalars);
             for (size_t t = 0; t < p->slots.size(); ++t) {
                 std::memcpy(out + (2 * t) * E, p->slots[t].alpha.data(), E);

@@ -78,7 +78,9 @@ struct dp_args {
     const int32_t* tab;
     const dp_block* blocks;
     int rank, n_ranks, loopback;
-    uint64_t elem;
+    // element sizes of A, of C and of the package (all equal but for half-precision pairs, whose
+    // package holds the 2-byte type)
+    uint64_t elem_a, elem_c, elem_p;
 };
 
 struct dp_cell {
@@ -124,13 +126,13 @@ __device__ inline int64_t cm_index(const dp_cell& c) {
 __device__ inline tile_side a_side(const dp_args& a, const dp_cell& c) {
     const dp_job& J = *c.j;
     const dp_block& b = a.blocks[a.tab[J.a_tab + int64_t(c.ar) * J.a_nbc + c.ac]];
-    return sub_tile(b.data, b.ld, b.row0, b.col0, J.a_rm, J.tr, c.r0, c.r1, c.c0, c.c1, a.elem);
+    return sub_tile(b.data, b.ld, b.row0, b.col0, J.a_rm, J.tr, c.r0, c.r1, c.c0, c.c1, a.elem_a);
 }
 // the receive side's tile (prepare_to_recv: C's block)
 __device__ inline tile_side c_side(const dp_args& a, const dp_cell& c) {
     const dp_job& J = *c.j;
     const dp_block& b = a.blocks[a.tab[J.c_tab + int64_t(c.cr) * J.c_nbc + c.cc]];
-    return sub_tile(b.data, b.ld, b.row0, b.col0, J.c_rm, false, c.r0, c.r1, c.c0, c.c1, a.elem);
+    return sub_tile(b.data, b.ld, b.row0, b.col0, J.c_rm, false, c.r0, c.r1, c.c0, c.c1, a.elem_c);
 }
 
 enum { L_LOCAL = 0, L_PACK = 1, L_UNPACK = 2 };
@@ -196,17 +198,17 @@ __global__ void dp_emit(dp_args a, const uint32_t* cells, const uint32_t* keys, 
     costa_tile_op_t op;
     if (L == L_PACK) {  // copy_to_buffer: stored shape and ordering, dense, no transform
         const tile_side s = a_side(a, c);
-        op = tile_op(s.n_rows, s.n_cols, s.ptr, s.ld, J.a_cm, uint64_t(off[k]) * a.elem, 0, J.a_cm,
-                     false, false, COSTA_SCALE_BITCOPY, 0, a.elem);
+        op = tile_op(s.n_rows, s.n_cols, s.ptr, s.ld, J.a_cm, uint64_t(off[k]) * a.elem_p, 0, J.a_cm,
+                     false, false, COSTA_SCALE_BITCOPY, 0, a.elem_a, a.elem_p);
     } else if (L == L_UNPACK) {  // copy_from_buffer: A's stored shape, dims swapped back
         const tile_side d = c_side(a, c);
         const int nr = J.tr ? d.n_cols : d.n_rows, nc = J.tr ? d.n_rows : d.n_cols;
-        op = tile_op(nr, nc, uint64_t(off[k]) * a.elem, 0, J.a_cm, d.ptr, d.ld, J.c_cm, J.tr, J.cj,
-                     kind, uint32_t(J.tag), a.elem);
+        op = tile_op(nr, nc, uint64_t(off[k]) * a.elem_p, 0, J.a_cm, d.ptr, d.ld, J.c_cm, J.tr, J.cj,
+                     kind, uint32_t(J.tag), a.elem_p, a.elem_c);
     } else {  // copy_local_blocks
         const tile_side s = a_side(a, c), d = c_side(a, c);
         op = tile_op(s.n_rows, s.n_cols, s.ptr, s.ld, J.a_cm, d.ptr, d.ld, J.c_cm, J.tr, J.cj, kind,
-                     uint32_t(J.tag), a.elem);
+                     uint32_t(J.tag), a.elem_a, a.elem_c);
     }
     op.order = rank_cm[cm_index(c)] + 1;
     out[k] = op;
@@ -314,14 +316,16 @@ std::unique_ptr<plan> make_plan_device(const std::vector<job>& jobs, int rank, i
                    std::chrono::steady_clock::now().time_since_epoch()).count();
     };
     const double t0 = now();
-    // mixed-precision pairs are planned on the host (whose checks also report unsupported pairs)
-    if (any_mixed(jobs)) return nullptr;
+    // mixed-precision pairs are planned on the host (whose checks also report unsupported pairs);
+    // half-precision pairs (FLOAT <-> a 2-byte type, package of the 2-byte type) are planned here
+    if (any_mixed(jobs) && !any_half(jobs)) return nullptr;
     // ... and so are triangular (masked) transforms: the mask's cut lives in plan.cpp decompose
     if (any_masked(jobs)) return nullptr;
     auto p = std::make_unique<plan>();
-    const std::vector<job_params> prm = check_jobs(jobs, n_ranks, p->dtype);
-    p->src_dtype = p->pkg_dtype = p->dtype;
-    const uint64_t E = dtype_size(p->dtype);
+    const std::vector<job_params> prm = check_jobs(jobs, n_ranks, p->src_dtype, p->dtype);
+    const uint64_t EA = dtype_size(p->src_dtype), EC = dtype_size(p->dtype);
+    p->pkg_dtype = EA < EC ? p->src_dtype : p->dtype;  // as make_plan
+    const uint64_t EP = std::min(EA, EC);
 
     // ---- host: merged grids and tables, O(split points + blocks) ----
     std::vector<dp_job> J;
@@ -425,7 +429,9 @@ std::unique_ptr<plan> make_plan_device(const std::vector<job>& jobs, int rank, i
     a.rank = rank;
     a.n_ranks = n_ranks;
     a.loopback = loopback;
-    a.elem = E;
+    a.elem_a = EA;
+    a.elem_c = EC;
+    a.elem_p = EP;
     uint32_t* keys = m.at<uint32_t>(o_keys);
     uint32_t* iota = m.at<uint32_t>(o_iota);
     uint32_t* skeys = m.at<uint32_t>(o_skeys);
@@ -519,10 +525,10 @@ std::unique_ptr<plan> make_plan_device(const std::vector<job>& jobs, int rank, i
     }
     for (const auto& op : p->local_ops) {
         p->local_elems += int64_t(op.nf) * op.ns;
-        p->local_bytes += op_alg_bytes(op, E);
+        p->local_bytes += op_alg_bytes(op, EA, EC);
     }
-    for (const auto& op : p->pack_ops) p->pack_bytes += op_alg_bytes(op, E);
-    for (const auto& op : p->unpack_ops) p->unpack_bytes += op_alg_bytes(op, E);
+    for (const auto& op : p->pack_ops) p->pack_bytes += op_alg_bytes(op, EA, EP);
+    for (const auto& op : p->unpack_ops) p->unpack_bytes += op_alg_bytes(op, EP, EC);
     if (trace)
         std::fprintf(stderr,
                      "[costa device plan] %lld cells, %lld / %lld / %lld ops: host tables %.2f ms, "

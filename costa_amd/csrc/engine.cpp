@@ -1979,7 +1979,8 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
     const double t0 = now();
     double t_resid = 0, t_plan = 0, t_work = 0;
 
-    const bool mixed = any_mixed(jobs);
+    const bool half = any_half(jobs);  // 2-byte element types: treated like mixed pairs here
+    const bool mixed = any_mixed(jobs) || half;
     const bool masked = any_masked(jobs);
     if (mixed || masked) {  // an unsupported pair is reported as such, whatever the residency
         costa_dtype_t a, b;
@@ -2003,8 +2004,10 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
     std::vector<uint8_t> range_flags;
     if (!all_dev && mixed)
         throw error(COSTA_ERR_ARG,
-                    "costa: mixed-precision transforms (A and C of different element types) need "
-                    "device-resident layouts");
+                    half ? "costa: half-precision transforms (A or C of a 2-byte element type) need "
+                           "device-resident layouts"
+                         : "costa: mixed-precision transforms (A and C of different element types) need "
+                           "device-resident layouts");
     if (!all_dev) {
         cp->staged = true;
         std::vector<const elayout*> As, Cs;
@@ -2143,10 +2146,11 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
     };
     device_section sec_l = section();
     // (a mixed plan's LOCAL list converts; its package holds the narrower type, so PACK converts
-    // for narrowing pairs and UNPACK for widening ones, the other being a same-type list)
-    const bool cv_pack = p.mixed() && p.pkg_dtype != p.src_dtype;
-    const bool cv_unpack = p.mixed() && p.pkg_dtype != p.dtype;
-    if (p.mixed())
+    // for narrowing pairs and UNPACK for widening ones, the other being a same-type list; every
+    // list of a half-precision plan runs on the converting family, its same-type H -> H lists too)
+    const bool cv_pack = p.half() || (p.mixed() && p.pkg_dtype != p.src_dtype);
+    const bool cv_unpack = p.half() || (p.mixed() && p.pkg_dtype != p.dtype);
+    if (p.converting())
         cp->c_local = build_convert_work(p.src_dtype, p.dtype, p.local_ops, 0, 0, ord_l, w_l);
     else
         // The wholly kept tiles of a triangular plan merge into row bands of unequal widths, one
@@ -2231,7 +2235,7 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
 }
 
 void upload_scalars(cached_plan& cp, const std::vector<job>& jobs, hipStream_t s) {
-    const size_t E = dtype_size(cp.p->dtype);
+    const size_t E = dtype_size(cp.p->scalar_dtype());  // (fp32 for half-precision plans)
     std::vector<unsigned char> host(jobs.size() * 2 * E);
     for (size_t t = 0; t < jobs.size(); ++t) {
         std::memcpy(&host[(2 * t) * E], jobs[t].s.alpha.data(), E);
@@ -2582,6 +2586,9 @@ void execute_tiles(costa_dtype_t dtype, const costa_tile_op_t* ops, int64_t n,
                    const void* src_base, void* dst_base, const void* scalars, int n_slots,
                    int device) {
     std::lock_guard<std::recursive_mutex> lk(g_mutex);
+    if (dtype_is_half(dtype))
+        throw error(COSTA_ERR_ARG, std::string("costa_hip_execute_tiles: no same-type tile kernel for ") +
+                                       dtype_name(dtype) + " (use costa_hip_execute_tiles_mixed)");
     device_ctx& dc = ctx(device);
     std::vector<costa_tile_op_t> v(ops, ops + n);
     for (const auto& op : v)
@@ -2612,7 +2619,8 @@ void execute_tiles_mixed(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const
     if (!convertible(src_dtype, dst_dtype))
         throw error(COSTA_ERR_ARG, std::string("costa_hip_execute_tiles_mixed: cannot convert ") +
                                        dtype_name(src_dtype) + " to " + dtype_name(dst_dtype) +
-                                       " (FLOAT <-> DOUBLE and CFLOAT <-> CDOUBLE only)");
+                                       " (FLOAT <-> DOUBLE, CFLOAT <-> CDOUBLE, and HALF or BFLOAT16 with "
+                                       "itself or FLOAT only)");
     device_ctx& dc = ctx(device);
     std::vector<costa_tile_op_t> v(ops, ops + n);
     for (const auto& op : v)
@@ -2625,7 +2633,7 @@ void execute_tiles_mixed(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const
     dbuf d_ops, d_work, d_scal;
     d_ops.upload(ord, dc.main);
     d_work.upload(w, dc.main);
-    const size_t E = dtype_size(dst_dtype);
+    const size_t E = dtype_size(compute_dtype(src_dtype, dst_dtype));  // (fp32 for half pairs)
     std::vector<unsigned char> sc(static_cast<const unsigned char*>(scalars),
                                   static_cast<const unsigned char*>(scalars) + size_t(n_slots) * 2 * E);
     d_scal.upload(sc, dc.main);
@@ -2639,6 +2647,9 @@ void execute_tiles_mixed(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const
 void execute_tiles_tri(costa_dtype_t dtype, const costa_tri_op_t* ops, int64_t n, const void* src_base,
                        void* dst_base, const void* scalars, int n_slots, int device) {
     std::lock_guard<std::recursive_mutex> lk(g_mutex);
+    if (dtype_is_half(dtype))
+        throw error(COSTA_ERR_ARG, std::string("costa_hip_execute_tiles_tri: no edge-tile kernel for ") +
+                                       dtype_name(dtype));
     device_ctx& dc = ctx(device);
     std::vector<costa_tri_op_t> v(ops, ops + n);
     for (const auto& t : v)
@@ -2667,6 +2678,9 @@ void copy_and_transform(costa_dtype_t dtype, int n_rows, int n_cols, const void*
                         bool trans, bool conj, const void* alpha, const void* beta) {
     if (n_rows < 0 || n_cols < 0 || src_stride < 0 || dst_stride < 0)
         throw error(COSTA_ERR_ARG, "costa_hip_copy_and_transform: negative size or stride");
+    if (dtype_is_half(dtype))
+        throw error(COSTA_ERR_ARG, std::string("costa_hip_copy_and_transform: no same-type tile kernel for ") +
+                                       dtype_name(dtype));
     if (size_t(n_rows) * size_t(n_cols) == 0) return;  // memory_utils.hpp:72-74
     const size_t E = dtype_size(dtype);
     scal s;

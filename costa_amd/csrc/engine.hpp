@@ -16,6 +16,12 @@ namespace engine {
 
 size_t dtype_size(costa_dtype_t t);
 bool dtype_is_complex(costa_dtype_t t);
+bool dtype_is_half(costa_dtype_t t);  // the 2-byte types: COSTA_HALF, COSTA_BFLOAT16
+// the type of alpha / beta and of the arithmetic of an (A, C) pair: C's type, FLOAT when A or C is
+// a 2-byte type
+costa_dtype_t compute_dtype(costa_dtype_t src, costa_dtype_t dst);
+// H -> H of one H, FLOAT -> H, H -> FLOAT (H a 2-byte type): the pairs of half_kernels.hip
+bool half_pair(costa_dtype_t src, costa_dtype_t dst);
 
 // One local block, element-type erased.  Intervals are in the layout's own (untransposed)
 // global coordinates; `data` points at its first element.
@@ -82,6 +88,14 @@ struct plan {
     costa_dtype_t src_dtype = COSTA_DOUBLE;  // A's element type
     costa_dtype_t pkg_dtype = COSTA_DOUBLE;  // element type of the send / receive packages
     bool mixed() const { return src_dtype != dtype; }
+    // Half-precision plans (A or C of a 2-byte type H; H -> H, FLOAT -> H, H -> FLOAT): pkg_dtype is
+    // H and all three lists run on the converting family of half_kernels.hip, the same-type H -> H
+    // lists included (tile_kernels.hip has no 2-byte shape); the scalars are fp32.
+    bool half() const { return dtype_is_half(src_dtype) || dtype_is_half(dtype); }
+    // every list of the plan runs on a converting family, or (mixed, not half) LOCAL and one of
+    // PACK / UNPACK
+    bool converting() const { return mixed() || half(); }
+    costa_dtype_t scalar_dtype() const { return compute_dtype(src_dtype, dtype); }
     int rank = 0, n_ranks = 1;
     std::vector<costa_tile_op_t> local_ops, pack_ops, unpack_ops;
     // triangular transforms: the LOCAL and UNPACK ops of the tiles the mask's diagonal cuts (their
@@ -114,6 +128,8 @@ bool any_masked(const std::vector<job>& jobs);
 constexpr int kTriCut = 256;
 // whether some job of the batch converts (A's element type differs from C's)
 bool any_mixed(const std::vector<job>& jobs);
+// whether some job of the batch has a 2-byte element type on either side
+bool any_half(const std::vector<job>& jobs);
 
 // Build the plan of `rank` (of `n_ranks`) for a batch of jobs (host only).  `loopback` (test
 // mode, see loopback_exchange()): 1 = the rank's own tiles all go through pack -> exchange with
@@ -199,6 +215,8 @@ void execute_tiles_mixed(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const
                          int n_slots, int device);
 
 // ---- converting lists (convert_kernels.hip): dst = g(static_cast<dst type>(src)) ----
+// (half pairs -- half_pair() -- go through the same four entry points to half_kernels.hip, with
+// fp32 scalars: dst = cvt(g(w(src), w(dst))), costa_hip.h "Half precision")
 // One kernel family, one workgroup per sub-tile of one op; the work items are
 // (op index << 32) | sub-tile, as for tile_kernel, in list order.  Scale kind BITCOPY of a
 // converting op means "convert only".
@@ -208,7 +226,7 @@ struct convert_list {
     int64_t n_items = 0;
     bool any_transpose = false;
 };
-bool convertible(costa_dtype_t src, costa_dtype_t dst);  // FLOAT <-> DOUBLE, CFLOAT <-> CDOUBLE
+bool convertible(costa_dtype_t src, costa_dtype_t dst);  // FLOAT <-> DOUBLE, CFLOAT <-> CDOUBLE, half_pair
 // the work list of a converting list: `ordered` = the ops with each side's VEC flag set from its
 // actual address (base + offset) and element size, `work` = every sub-tile of every op
 convert_list build_convert_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
@@ -218,6 +236,12 @@ convert_list build_convert_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype
 void launch_convert(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_tile_op_t* d_ops,
                     const uint64_t* d_work, const convert_list& l, const char* src_base,
                     char* dst_base, const void* d_scalars, void* stream /* hipStream_t */);
+
+// ---- half-precision lists (half_kernels.hip), reached through convert_subtile / launch_convert ----
+void half_subtile(int* bf, int* bs);
+void launch_half(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_tile_op_t* d_ops,
+                 const uint64_t* d_work, const convert_list& l, const char* src_base, char* dst_base,
+                 const void* d_scalars, void* stream /* hipStream_t */);
 
 // ---- edge tiles of triangular transforms (tri_kernels.hip) ----
 // One kernel family, tri_kernel<T>, one workgroup per sub-tile of one costa_tri_op_t; the work

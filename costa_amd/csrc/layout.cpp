@@ -185,5 +185,7 @@ COSTA_INSTANTIATE_LAYOUTS(double)
 COSTA_INSTANTIATE_LAYOUTS(std::complex<float>)
 COSTA_INSTANTIATE_LAYOUTS(std::complex<double>)
 COSTA_INSTANTIATE_LAYOUTS(int)
+COSTA_INSTANTIATE_LAYOUTS(half_bits)
+COSTA_INSTANTIATE_LAYOUTS(bfloat16_bits)
 
 }  // namespace costa

@@ -35,11 +35,23 @@ size_t dtype_size(costa_dtype_t t) {
     case COSTA_CFLOAT: return 8;
     case COSTA_CDOUBLE: return 16;
     case COSTA_INT32: return 4;
+    case COSTA_HALF: return 2;
+    case COSTA_BFLOAT16: return 2;
     }
     throw error(COSTA_ERR_ARG, "unknown dtype");
 }
 
 bool dtype_is_complex(costa_dtype_t t) { return t == COSTA_CFLOAT || t == COSTA_CDOUBLE; }
+bool dtype_is_half(costa_dtype_t t) { return t == COSTA_HALF || t == COSTA_BFLOAT16; }
+
+costa_dtype_t compute_dtype(costa_dtype_t src, costa_dtype_t dst) {
+    return dtype_is_half(src) || dtype_is_half(dst) ? COSTA_FLOAT : dst;
+}
+
+bool half_pair(costa_dtype_t src, costa_dtype_t dst) {
+    return (dtype_is_half(src) && (dst == src || dst == COSTA_FLOAT)) ||
+           (src == COSTA_FLOAT && dtype_is_half(dst));
+}
 
 const char* dtype_name(costa_dtype_t t) {
     switch (t) {
@@ -48,6 +60,8 @@ const char* dtype_name(costa_dtype_t t) {
     case COSTA_CFLOAT: return "CFLOAT";
     case COSTA_CDOUBLE: return "CDOUBLE";
     case COSTA_INT32: return "INT32";
+    case COSTA_HALF: return "HALF";
+    case COSTA_BFLOAT16: return "BFLOAT16";
     }
     return "unknown";
 }
@@ -64,11 +78,19 @@ bool any_mixed(const std::vector<job>& jobs) {
     return false;
 }
 
+bool any_half(const std::vector<job>& jobs) {
+    for (const job& jb : jobs)
+        if (jb.A && jb.C && (dtype_is_half(jb.A->dtype) || dtype_is_half(jb.C->dtype))) return true;
+    return false;
+}
+
 template <> costa_dtype_t dtype_of<float>() { return COSTA_FLOAT; }
 template <> costa_dtype_t dtype_of<double>() { return COSTA_DOUBLE; }
 template <> costa_dtype_t dtype_of<std::complex<float>>() { return COSTA_CFLOAT; }
 template <> costa_dtype_t dtype_of<std::complex<double>>() { return COSTA_CDOUBLE; }
 template <> costa_dtype_t dtype_of<int>() { return COSTA_INT32; }
+template <> costa_dtype_t dtype_of<half_bits>() { return COSTA_HALF; }
+template <> costa_dtype_t dtype_of<bfloat16_bits>() { return COSTA_BFLOAT16; }
 
 template <typename T>
 elayout erase(const grid_layout<T>& L) {
@@ -97,6 +119,8 @@ template elayout erase<double>(const grid_layout<double>&);
 template elayout erase<std::complex<float>>(const grid_layout<std::complex<float>>&);
 template elayout erase<std::complex<double>>(const grid_layout<std::complex<double>>&);
 template elayout erase<int>(const grid_layout<int>&);
+template elayout erase<half_bits>(const grid_layout<half_bits>&);
+template elayout erase<bfloat16_bits>(const grid_layout<bfloat16_bits>&);
 
 namespace {
 
@@ -264,6 +288,9 @@ uint32_t scale_kind(costa_dtype_t dtype, const scal& s, bool copy_mode, bool con
     case COSTA_CFLOAT: return kind_t<std::complex<float>>(s, copy_mode, conj);
     case COSTA_CDOUBLE: return kind_t<std::complex<double>>(s, copy_mode, conj);
     case COSTA_INT32: return kind_t<int>(s, copy_mode, conj);
+    // 2-byte types: the scalars are fp32 and the branches those of the FLOAT transform
+    case COSTA_HALF: return kind_t<float>(s, copy_mode, conj);
+    case COSTA_BFLOAT16: return kind_t<float>(s, copy_mode, conj);
     }
     throw error(COSTA_ERR_ARG, "unknown dtype");
 }
@@ -297,14 +324,16 @@ std::vector<job_params> check_jobs(const std::vector<job>& jobs, int n_ranks, co
     src_dtype = jobs[0].A->dtype;
     dtype = jobs[0].C->dtype;
     // mixed precision: convert(A) in C's type; only the 2:1 pairs of one kind convert
+    // (half precision: H -> H, FLOAT -> H, H -> FLOAT, computed in fp32)
     const bool pair_ok =
-        src_dtype == dtype ||
+        src_dtype == dtype || half_pair(src_dtype, dtype) ||
         (src_dtype == COSTA_FLOAT && dtype == COSTA_DOUBLE) || (src_dtype == COSTA_DOUBLE && dtype == COSTA_FLOAT) ||
         (src_dtype == COSTA_CFLOAT && dtype == COSTA_CDOUBLE) || (src_dtype == COSTA_CDOUBLE && dtype == COSTA_CFLOAT);
     if (!pair_ok)
         throw error(COSTA_ERR_ARG, std::string("costa::transform: cannot convert ") + dtype_name(src_dtype) +
                                        " (A) to " + dtype_name(dtype) +
-                                       " (C): mixed transforms are FLOAT <-> DOUBLE and CFLOAT <-> CDOUBLE");
+                                       " (C): mixed transforms are FLOAT <-> DOUBLE, CFLOAT <-> CDOUBLE and "
+                                       "FLOAT <-> HALF or BFLOAT16");
     const bool cplx = dtype_is_complex(dtype);
     std::vector<job_params> out;
     for (const job& jb : jobs) {
@@ -328,6 +357,11 @@ std::vector<job_params> check_jobs(const std::vector<job>& jobs, int n_ranks, co
         const char ul = upper(jb.uplo);
         if (ul != 'A' && ul != 'U' && ul != 'L')
             throw error(COSTA_ERR_ARG, "costa::transform: uplo must be 'U' or 'L'");
+        if (ul != 'A' && (dtype_is_half(src_dtype) || dtype_is_half(dtype)))
+            throw error(COSTA_ERR_ARG,
+                        std::string("costa::transform: triangular (masked) transforms take no 2-byte "
+                                    "element type: ") +
+                            dtype_name(src_dtype) + " (A), " + dtype_name(dtype) + " (C)");
         if (ul != 'A' && src_dtype != dtype)
             throw error(COSTA_ERR_ARG,
                         std::string("costa::transform: a triangular (masked) transform needs A and C of "

@@ -1191,6 +1191,7 @@ void tile_shapes(costa_dtype_t dtype, bool transposing_list, shape_dims* d) {
     case COSTA_CFLOAT: shape_of<cpx<float>>(t, d); return;
     case COSTA_CDOUBLE: shape_of<cpx<double>>(t, d); return;
     case COSTA_INT32: shape_of<int>(t, d); return;
+    default: break;  // (no 2-byte shape: half-precision lists run on half_kernels.hip)
     }
     throw error(COSTA_ERR_ARG, "unknown dtype");
 }
@@ -1213,6 +1214,7 @@ void launch_tiles(costa_dtype_t dtype, const launch_args& a, void* stream) {
     case COSTA_CFLOAT: launch_t<cpx<float>>(a, s); break;
     case COSTA_CDOUBLE: launch_t<cpx<double>>(a, s); break;
     case COSTA_INT32: launch_t<int>(a, s); break;
+    default: throw error(COSTA_ERR_ARG, std::string("costa: no same-type tile kernel for ") + dtype_name(dtype));
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)

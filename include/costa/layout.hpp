@@ -321,8 +321,19 @@ struct block_t {
     int col;
 };
 
+// The 2-byte element types of the C ABI (COSTA_HALF, COSTA_BFLOAT16) as raw bits: enough to build
+// and erase their layouts.  costa::transform<T> has no overload for them (costa_hip.h, "Half
+// precision").
+struct half_bits {
+    uint16_t bits;
+};
+struct bfloat16_bits {
+    uint16_t bits;
+};
+
 // ---- layout builders (defined in costa_amd/csrc/layout.cpp, instantiated for
-//      float, double, std::complex<float>, std::complex<double>, int) ----
+//      float, double, std::complex<float>, std::complex<double>, int and the two bits-only
+//      2-byte types above) ----
 
 template <typename T>
 grid_layout<T> custom_layout(int rowblocks, int colblocks, const int* rowsplit, const int* colsplit,

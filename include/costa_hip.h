@@ -54,7 +54,9 @@ typedef enum {
     COSTA_DOUBLE = 1,
     COSTA_CFLOAT = 2,  /* std::complex<float>, interleaved re/im */
     COSTA_CDOUBLE = 3, /* std::complex<double>, interleaved re/im */
-    COSTA_INT32 = 4
+    COSTA_INT32 = 4,
+    COSTA_HALF = 5,    /* IEEE binary16, 2 bytes, raw bits ("Half precision" below) */
+    COSTA_BFLOAT16 = 6 /* bfloat16, 2 bytes, raw bits */
 } costa_dtype_t;
 
 typedef struct costa_layout_s* costa_layout_t;
@@ -186,7 +188,29 @@ void costa_hip_comm_destroy(costa_comm_t comm);
  * pairs while unpacking).  Every pair of a batch must share one (A dtype, C dtype); any other
  * unequal pair (COSTA_INT32 with anything, real with complex) is COSTA_ERR_ARG with a message
  * naming both types.  Mixed transforms need device-resident layouts (blocking and _async entry
- * points, any communicator size): on host-resident layouts they return COSTA_ERR_ARG. */
+ * points, any communicator size): on host-resident layouts they return COSTA_ERR_ARG.
+ *
+ * Half precision (MI355X-native): COSTA_HALF and COSTA_BFLOAT16 are 2-byte element types held as
+ * raw bits; offsets, leading dimensions and counts are in elements as for every other type.  Write
+ * H for one of the two.  The supported (A, C) pairs are H -> H of the same H, COSTA_FLOAT -> H and
+ * H -> COSTA_FLOAT; every other pair with a 2-byte type (COSTA_HALF <-> COSTA_BFLOAT16, H with
+ * COSTA_DOUBLE, COSTA_INT32 or a complex type) is COSTA_ERR_ARG with a message naming both types.
+ * Whenever A or C is 2-byte, alpha/beta are ONE fp32 each (not an element of C's dtype): the
+ * compute type of such a transform is COSTA_FLOAT.  With w() the exact widening to fp32, cvt() the
+ * conversion fp32 -> C's type (round to nearest even, overflow to +-inf, subnormals kept) and
+ * F(a, c) the COSTA_FLOAT same-type transform of one element (same branches, same operation
+ * order, no fma):
+ *   H -> H            C = cvt(F(w(A), w(C)))      (scale kind BITCOPY -- copy mode, alpha = 1,
+ *                                                  beta = 0 -- is a byte copy)
+ *   COSTA_FLOAT -> H  the H -> H transform of cvt(A): A is rounded to C's type first
+ *   H -> COSTA_FLOAT  C = F(w(A), C)
+ * so all arithmetic is fp32 with ONE rounding at the store.  The packages of the exchange hold H
+ * for all three pairs (LOCAL and PACK -> UNPACK give the same bits).  'C' is 'T'.  Bytes of C that
+ * no tile writes stay bit-identical.  Device-resident layouts only (COSTA_ERR_ARG with
+ * "device-resident" otherwise); blocking, _async, batches and any communicator size work;
+ * costa_hip_transform_tri, costa_hip_execute_tiles, costa_hip_execute_tiles_tri and
+ * costa_hip_copy_and_transform refuse a 2-byte dtype with COSTA_ERR_ARG.  The C++
+ * costa::transform<T> overloads and the ScaLAPACK shims take no half types. */
 int costa_hip_transform(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
                         const void* beta, costa_comm_t comm);
 /* several layout pairs in one exchange; trans/alpha/beta are arrays of n entries
@@ -245,12 +269,16 @@ int costa_hip_execute_tiles(costa_dtype_t dtype, const costa_tile_op_t* ops, int
  * elements / bytes as in costa_tile_op_t; `scalars` = n_slots (alpha, beta) pairs of dst_dtype.
  * COSTA_SCALE_BITCOPY means "convert only" here (never a byte copy).  The VEC flags are recomputed
  * from each side's actual address: the side of the wider type takes 16-byte vector accesses when
- * 16-byte aligned, the other side 8-byte ones when 8-byte aligned. */
+ * 16-byte aligned, the other side 8-byte ones when 8-byte aligned.
+ * Half-precision pairs ("Half precision" above: (H, H), (COSTA_FLOAT, H), (H, COSTA_FLOAT)) run
+ * here too, on half_kernel: `scalars` are then n_slots (alpha, beta) pairs of fp32, a 2-byte side
+ * takes 8-byte vector accesses when 8-byte aligned, an fp32 side 16-byte ones when 16-byte aligned,
+ * and COSTA_SCALE_BITCOPY of an (H, H) op is a byte copy. */
 int costa_hip_execute_tiles_mixed(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
                                   const costa_tile_op_t* ops, int64_t n, const void* src_base,
                                   void* dst_base, const void* scalars, int n_slots, int device);
-/* the sub-tile one workgroup of the converting kernels runs for a mixed pair: elements along the
- * source's fast (*bf) and slow (*bs) dimension */
+/* the sub-tile one workgroup of the converting kernels runs for a mixed or half-precision pair
+ * ((H, H) included): elements along the source's fast (*bf) and slow (*bs) dimension */
 int costa_hip_convert_subtile(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, int* bf, int* bs);
 
 /* edge ops (costa_tri_op_t) of one dtype in ONE launch of tri_kernel; the VEC flags are recomputed
@@ -272,7 +300,8 @@ int costa_hip_tri_subtile(costa_dtype_t dtype, int* bf, int* bs);
  * dtypes) it is the smaller of the two: pack ops then read A's type and write the package type,
  * unpack ops read the package type and write C's, local ops read A's and write C's, and each
  * side's byte offsets and VEC flag follow its own element size.  Counts and displacements are in
- * elements; `scalars` are of C's dtype.
+ * elements; `scalars` are of C's dtype -- of the compute type COSTA_FLOAT (fp32) when A or C is a
+ * 2-byte type, whose package holds the 2-byte type.
  * Call once with NULL arrays to get the sizes in *info, then again with arrays of
  * at least those sizes. */
 typedef struct {
@@ -335,8 +364,9 @@ typedef struct {
                              (costa_hip_set_list_builder) */
     int64_t fused_pieces; /* of tiny_items: wavefront pieces run as workgroups at the end of the
                              destination-block group launch (no tiny_kernel launch of their own) */
-    int64_t convert_items; /* sub-tiles run by convert_kernel (the converting lists of mixed
-                              transforms, costa_hip_execute_tiles_mixed) */
+    int64_t convert_items; /* sub-tiles run by convert_kernel and half_kernel (the converting lists
+                              of mixed and half-precision transforms,
+                              costa_hip_execute_tiles_mixed) */
     int64_t tri_items; /* sub-tiles run by tri_kernel (the edge tiles of triangular transforms,
                           costa_hip_execute_tiles_tri) */
 } costa_stats_t;
