@@ -28,7 +28,7 @@ import numpy as np
 
 __all__ = [
     "CostaError", "lib", "FLOAT", "DOUBLE", "CFLOAT", "CDOUBLE", "INT32", "HALF", "BFLOAT16",
-    "dtype_code",
+    "FP8_E4M3", "FP8_E5M2", "dtype_code", "element_code",
     "np_dtype", "Layout", "block_cyclic_layout", "custom_layout", "Comm", "transform",
     "transform_batch", "transform_async", "transform_batch_async", "synchronize", "transformer", "copy_and_transform", "execute_tiles", "execute_tiles_mixed",
     "convert_subtile", "TileOp", "TriOp", "TRI_OP_DTYPE", "transform_tri", "transform_tri_async",
@@ -46,6 +46,14 @@ _NP = {FLOAT: np.float32, DOUBLE: np.float64, CFLOAT: np.complex64,
 _TORCH = {"torch.float32": FLOAT, "torch.float64": DOUBLE, "torch.complex64": CFLOAT,
           "torch.complex128": CDOUBLE, "torch.int32": INT32, "torch.float16": HALF,
           "torch.bfloat16": BFLOAT16}
+
+# 1-byte element types (costa_hip.h, "FP8"): OCP e4m3fn and e5m2, raw bits (np.uint8).  The pairs
+# are Q -> Q, FLOAT -> Q and Q -> FLOAT on device-resident layouts, and alpha / beta are fp32.  They
+# are kept out of _NP and _TORCH: dtype_code() does not know them, element_code() does.
+FP8_E4M3, FP8_E5M2 = 7, 8
+_NP_FP8 = {FP8_E4M3: np.uint8, FP8_E5M2: np.uint8}
+_TORCH_FP8 = {"torch.float8_e4m3fn": FP8_E4M3, "torch.float8_e5m2": FP8_E5M2}
+_FP32_SCALARS = (HALF, BFLOAT16, FP8_E4M3, FP8_E5M2)
 
 TILE_TRANSPOSE, TILE_CONJ, TILE_VEC_SRC, TILE_VEC_DST = 0x1, 0x2, 0x4, 0x8
 SCALE_BITCOPY, SCALE_ZERO, SCALE_ALPHA, SCALE_AXPBY = 0, 1, 2, 3
@@ -85,14 +93,26 @@ def dtype_code(dtype) -> int:
     raise ValueError(f"unsupported element type {dtype}")
 
 
+def element_code(dtype) -> int:
+    """dtype_code() plus the FP8 types: ``torch.float8_e4m3fn`` is FP8_E4M3 and
+    ``torch.float8_e5m2`` is FP8_E5M2 (by module and name, without importing torch).  numpy has no
+    FP8 type, and a plain ``np.uint8`` array is not an FP8 matrix: pass the code."""
+    if not isinstance(dtype, int) and type(dtype).__module__.split(".")[0] == "torch" \
+            and str(dtype) in _TORCH_FP8:
+        return _TORCH_FP8[str(dtype)]
+    return dtype_code(dtype)
+
+
 def np_dtype(code: int):
-    """numpy type holding one element of ``code``; BFLOAT16 is ``np.uint16`` (its bits)."""
-    return _NP[code]
+    """numpy type holding one element of ``code``; BFLOAT16 is ``np.uint16`` and the FP8 types are
+    ``np.uint8`` (their bits)."""
+    return _NP_FP8[code] if code in _NP_FP8 else _NP[code]
 
 
 def _scalar_code(a_code: int, c_code: int) -> int:
-    """the type of alpha / beta of an (A, C) pair: C's, FLOAT when A or C is a 2-byte type"""
-    return FLOAT if a_code in (HALF, BFLOAT16) or c_code in (HALF, BFLOAT16) else c_code
+    """the type of alpha / beta of an (A, C) pair: C's, FLOAT when A or C is a 2-byte or a 1-byte
+    type"""
+    return FLOAT if a_code in _FP32_SCALARS or c_code in _FP32_SCALARS else c_code
 
 
 class _Block(C.Structure):
@@ -256,7 +276,7 @@ def _ptr(p) -> int:
 
 
 def _scalar_bytes(code: int, x) -> bytes:
-    if code in (HALF, BFLOAT16):  # the scalars of half-precision transforms are fp32
+    if code in _FP32_SCALARS:  # the scalars of half-precision and FP8 transforms are fp32
         code = FLOAT
     if code == DOUBLE:
         return struct.pack("<d", float(x))
@@ -326,7 +346,7 @@ class Layout:
 def block_cyclic_layout(m, n, block_m, block_n, i, j, sub_m, sub_n, p_m, p_n, order, rsrc, csrc,
                         ptr, lld, ordering, rank, dtype=DOUBLE) -> Layout:
     """ScaLAPACK block-cyclic layout of sub(A) (reference layout.hpp:70-86)."""
-    code = dtype_code(dtype)
+    code = element_code(dtype)
     h = C.c_void_p()
     _check(lib().costa_hip_block_cyclic_layout(code, m, n, block_m, block_n, i, j, sub_m, sub_n,
                                                p_m, p_n, _chr(order), rsrc, csrc,
@@ -339,7 +359,7 @@ def custom_layout(rowblocks, colblocks, rowsplit, colsplit, owners, localblocks,
                   dtype=DOUBLE) -> Layout:
     """Arbitrary grid layout (reference layout.hpp:34-42).  ``localblocks`` is a sequence of
     (data, ld, row, col) with data an address/array/tensor."""
-    code = dtype_code(dtype)
+    code = element_code(dtype)
     rs = np.ascontiguousarray(rowsplit, dtype=np.int32)
     cs = np.ascontiguousarray(colsplit, dtype=np.int32)
     ow = np.ascontiguousarray(owners, dtype=np.int32).reshape(-1)
@@ -421,7 +441,9 @@ def transform(A: Layout, Cl: Layout, comm: Comm, trans: str = "N", alpha=1, beta
     sub(A) is converted to C's type inside the tile kernels, and alpha / beta are of C's type
     (costa_hip.h, "Mixed precision").  HALF / BFLOAT16 layouts pair with themselves and with FLOAT
     (H -> H, FLOAT -> H, H -> FLOAT): fp32 arithmetic with one rounding at the store, alpha / beta
-    fp32 (costa_hip.h, "Half precision")."""
+    fp32 (costa_hip.h, "Half precision").  FP8_E4M3 / FP8_E5M2 layouts pair the same way (Q -> Q,
+    FLOAT -> Q, Q -> FLOAT); a FLOAT source is not rounded before the arithmetic, so FLOAT -> Q
+    with alpha = 1 / scale quantises (costa_hip.h, "FP8")."""
     transform_batch([A], [Cl], comm, [trans], [alpha], [beta])
 
 
@@ -499,7 +521,7 @@ class transformer:
 def copy_and_transform(dtype, n_rows, n_cols, src, src_stride, src_col_major, dst, dst_stride,
                        dst_col_major, transpose=False, conjugate=False, alpha=1, beta=0):
     """One tile on device pointers (reference memory_utils.hpp:339-412)."""
-    code = dtype_code(dtype)
+    code = element_code(dtype)
     _check(lib().costa_hip_copy_and_transform(
         code, n_rows, n_cols, C.c_void_p(_ptr(src)), src_stride, int(bool(src_col_major)),
         C.c_void_p(_ptr(dst)), dst_stride, int(bool(dst_col_major)), int(bool(transpose)),
@@ -509,9 +531,9 @@ def copy_and_transform(dtype, n_rows, n_cols, src, src_stride, src_col_major, ds
 def execute_tiles(dtype, ops: np.ndarray, scalars: np.ndarray, src_base=0, dst_base=0,
                   device: int = 0):
     """Run a tile-op list (numpy array of TILE_OP_DTYPE) in one batched launch."""
-    code = dtype_code(dtype)
+    code = element_code(dtype)
     ops = np.ascontiguousarray(ops, dtype=TILE_OP_DTYPE)
-    sc = np.ascontiguousarray(scalars, dtype=_NP[code]).reshape(-1)
+    sc = np.ascontiguousarray(scalars, dtype=np_dtype(code)).reshape(-1)
     assert sc.size % 2 == 0
     _check(lib().costa_hip_execute_tiles(code, ops.ctypes.data_as(C.POINTER(TileOp)), ops.size,
                                          C.c_void_p(_ptr(src_base)), C.c_void_p(_ptr(dst_base)),
@@ -523,8 +545,9 @@ def execute_tiles_mixed(src_dtype, dst_dtype, ops: np.ndarray, scalars: np.ndarr
     """Run a list of converting tile ops (sources of ``src_dtype``, destinations of ``dst_dtype``:
     FLOAT <-> DOUBLE or CFLOAT <-> CDOUBLE) in one batched launch; ``scalars`` are of
     ``dst_dtype`` (costa_hip_execute_tiles_mixed).  Half-precision pairs ((H, H), (FLOAT, H),
-    (H, FLOAT) with H = HALF or BFLOAT16) run here too, with fp32 ``scalars``."""
-    sc_, dc_ = dtype_code(src_dtype), dtype_code(dst_dtype)
+    (H, FLOAT) with H = HALF or BFLOAT16) and FP8 pairs (the same shapes with FP8_E4M3 or FP8_E5M2)
+    run here too, with fp32 ``scalars``."""
+    sc_, dc_ = element_code(src_dtype), element_code(dst_dtype)
     ops = np.ascontiguousarray(ops, dtype=TILE_OP_DTYPE)
     sc = np.ascontiguousarray(scalars, dtype=_NP[_scalar_code(sc_, dc_)]).reshape(-1)
     assert sc.size % 2 == 0
@@ -538,7 +561,7 @@ def convert_subtile(src_dtype, dst_dtype) -> tuple:
     """(BF, BS): the sub-tile of the converting kernels for a mixed pair, in elements along the
     source's fast and slow dimension (one workgroup each)."""
     bf, bs = C.c_int(0), C.c_int(0)
-    _check(lib().costa_hip_convert_subtile(dtype_code(src_dtype), dtype_code(dst_dtype),
+    _check(lib().costa_hip_convert_subtile(element_code(src_dtype), element_code(dst_dtype),
                                            C.byref(bf), C.byref(bs)))
     return bf.value, bs.value
 
@@ -574,9 +597,9 @@ def transform_tri_async(A: Layout, Cl: Layout, comm: Comm, trans: str = "N", upl
 def execute_tiles_tri(dtype, ops: np.ndarray, scalars: np.ndarray, src_base=0, dst_base=0,
                       device: int = 0):
     """Run a list of edge ops (numpy array of TRI_OP_DTYPE) in one launch of the edge-tile kernel."""
-    code = dtype_code(dtype)
+    code = element_code(dtype)
     ops = np.ascontiguousarray(ops, dtype=TRI_OP_DTYPE)
-    sc = np.ascontiguousarray(scalars, dtype=_NP[code]).reshape(-1)
+    sc = np.ascontiguousarray(scalars, dtype=np_dtype(code)).reshape(-1)
     assert sc.size % 2 == 0
     _check(lib().costa_hip_execute_tiles_tri(code, ops.ctypes.data_as(C.POINTER(TriOp)), ops.size,
                                              C.c_void_p(_ptr(src_base)), C.c_void_p(_ptr(dst_base)),
@@ -600,7 +623,7 @@ def tri_subtile(dtype) -> tuple:
     """(BF, BS): the sub-tile one workgroup of the edge-tile kernel runs, in elements along the
     source's fast and slow dimension."""
     bf, bs = C.c_int(0), C.c_int(0)
-    _check(lib().costa_hip_tri_subtile(dtype_code(dtype), C.byref(bf), C.byref(bs)))
+    _check(lib().costa_hip_tri_subtile(element_code(dtype), C.byref(bf), C.byref(bs)))
     return bf.value, bs.value
 
 
@@ -727,7 +750,7 @@ _WORK_META = ("n_large", "n_medium", "n_skew", "n_cblock", "cblock_lds", "cb_map
 def work_export(dtype, ops: np.ndarray, kind: str = "local", device=None) -> WorkLists:
     """The executor's work lists of one tile-op list (costa_hip_work_export): built on the host, or
     with ``device`` set with the destination-block groups on that GPU.  No kernel runs."""
-    code = dtype_code(dtype)
+    code = element_code(dtype)
     ops = np.ascontiguousarray(ops, dtype=TILE_OP_DTYPE)
     k = {"local": 0, "pack": 1, "unpack": 2}[kind]
     dev = -1 if device is None else int(device)

@@ -77,6 +77,8 @@ void with_type(costa_dtype_t t, F&& f) {
     case COSTA_INT32: f(int{}); return;
     case COSTA_HALF: f(costa::half_bits{}); return;
     case COSTA_BFLOAT16: f(costa::bfloat16_bits{}); return;
+    case COSTA_FP8_E4M3: f(costa::fp8_e4m3_bits{}); return;
+    case COSTA_FP8_E5M2: f(costa::fp8_e5m2_bits{}); return;
     }
     throw costa::engine::error(COSTA_ERR_ARG, "unknown dtype");
 }

@@ -396,6 +396,7 @@ void launch_pair(const costa_tile_op_t* d_ops, const uint64_t* d_work, const con
 
 void convert_subtile(costa_dtype_t src, costa_dtype_t dst, int* bf, int* bs) {
     if (half_pair(src, dst)) return half_subtile(bf, bs);
+    if (fp8_pair(src, dst)) return fp8_subtile(bf, bs);
     if (!convertible(src, dst))
         throw error(COSTA_ERR_ARG, std::string("costa: no converting kernel for ") + dtype_name(src) +
                                        " -> " + dtype_name(dst));
@@ -405,7 +406,7 @@ void convert_subtile(costa_dtype_t src, costa_dtype_t dst, int* bf, int* bs) {
 }
 
 bool convertible(costa_dtype_t src, costa_dtype_t dst) {
-    return half_pair(src, dst) || (src == COSTA_FLOAT && dst == COSTA_DOUBLE) || (src == COSTA_DOUBLE && dst == COSTA_FLOAT) ||
+    return half_pair(src, dst) || fp8_pair(src, dst) || (src == COSTA_FLOAT && dst == COSTA_DOUBLE) || (src == COSTA_DOUBLE && dst == COSTA_FLOAT) ||
            (src == COSTA_CFLOAT && dst == COSTA_CDOUBLE) || (src == COSTA_CDOUBLE && dst == COSTA_CFLOAT);
 }
 
@@ -427,7 +428,12 @@ convert_list build_convert_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype
         op.flags &= ~uint32_t(COSTA_TILE_VEC_SRC | COSTA_TILE_VEC_DST);
         // a side may use vector accesses when it is aligned to its strip: 16 bytes on the side of
         // the wider type, 8 on the other (half pairs: 8 on a 2-byte side, 16 on an fp32 side)
-        const uint64_t as = es > ed ? 16 : 8, ad = ed > es ? 16 : 8;
+        // (FP8 pairs: 16 on both sides of Q -> Q; with FLOAT, 4 on the 1-byte side, 16 on the fp32 side)
+        uint64_t as = es > ed ? 16 : 8, ad = ed > es ? 16 : 8;
+        if (es == 1 || ed == 1) {
+            as = es == 1 && ed != 1 ? 4 : 16;
+            ad = ed == 1 && es != 1 ? 4 : 16;
+        }
         if ((src_base + op.src) % as == 0 && (uint64_t(op.lds) * es) % as == 0) op.flags |= COSTA_TILE_VEC_SRC;
         if ((dst_base + op.dst) % ad == 0 && (uint64_t(op.ldd) * ed) % ad == 0) op.flags |= COSTA_TILE_VEC_DST;
         if (op.flags & COSTA_TILE_TRANSPOSE) l.any_transpose = true;
@@ -449,6 +455,8 @@ void launch_convert(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const cost
     if (l.n_items <= 0) return;
     if (half_pair(src_dtype, dst_dtype))
         return launch_half(src_dtype, dst_dtype, d_ops, d_work, l, src_base, dst_base, d_scalars, stream);
+    if (fp8_pair(src_dtype, dst_dtype))
+        return launch_fp8(src_dtype, dst_dtype, d_ops, d_work, l, src_base, dst_base, d_scalars, stream);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (src_dtype == COSTA_DOUBLE && dst_dtype == COSTA_FLOAT)
         launch_pair<double, float>(d_ops, d_work, l, src_base, dst_base, d_scalars, s);

@@ -79,7 +79,7 @@ struct dp_args {
     const dp_block* blocks;
     int rank, n_ranks, loopback;
     // element sizes of A, of C and of the package (all equal but for half-precision pairs, whose
-    // package holds the 2-byte type)
+    // package holds the 2-byte type, and FP8 pairs, whose package holds A's type)
     uint64_t elem_a, elem_c, elem_p;
 };
 
@@ -317,15 +317,16 @@ std::unique_ptr<plan> make_plan_device(const std::vector<job>& jobs, int rank, i
     };
     const double t0 = now();
     // mixed-precision pairs are planned on the host (whose checks also report unsupported pairs);
-    // half-precision pairs (FLOAT <-> a 2-byte type, package of the 2-byte type) are planned here
-    if (any_mixed(jobs) && !any_half(jobs)) return nullptr;
+    // half-precision pairs (FLOAT <-> a 2-byte type, package of the 2-byte type) and FP8 pairs
+    // (FLOAT <-> a 1-byte type, package of A's type) are planned here
+    if (any_mixed(jobs) && !any_half(jobs) && !any_fp8(jobs)) return nullptr;
     // ... and so are triangular (masked) transforms: the mask's cut lives in plan.cpp decompose
     if (any_masked(jobs)) return nullptr;
     auto p = std::make_unique<plan>();
     const std::vector<job_params> prm = check_jobs(jobs, n_ranks, p->src_dtype, p->dtype);
     const uint64_t EA = dtype_size(p->src_dtype), EC = dtype_size(p->dtype);
-    p->pkg_dtype = EA < EC ? p->src_dtype : p->dtype;  // as make_plan
-    const uint64_t EP = std::min(EA, EC);
+    p->pkg_dtype = plan_pkg_dtype(p->src_dtype, p->dtype);  // as make_plan
+    const uint64_t EP = dtype_size(p->pkg_dtype);
 
     // ---- host: merged grids and tables, O(split points + blocks) ----
     std::vector<dp_job> J;

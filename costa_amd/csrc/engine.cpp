@@ -1980,7 +1980,8 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
     double t_resid = 0, t_plan = 0, t_work = 0;
 
     const bool half = any_half(jobs);  // 2-byte element types: treated like mixed pairs here
-    const bool mixed = any_mixed(jobs) || half;
+    const bool fp8 = any_fp8(jobs);    // 1-byte element types: the same
+    const bool mixed = any_mixed(jobs) || half || fp8;
     const bool masked = any_masked(jobs);
     if (mixed || masked) {  // an unsupported pair is reported as such, whatever the residency
         costa_dtype_t a, b;
@@ -2004,7 +2005,9 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
     std::vector<uint8_t> range_flags;
     if (!all_dev && mixed)
         throw error(COSTA_ERR_ARG,
-                    half ? "costa: half-precision transforms (A or C of a 2-byte element type) need "
+                    fp8  ? "costa: FP8 transforms (A or C of a 1-byte element type) need "
+                           "device-resident layouts"
+                    : half ? "costa: half-precision transforms (A or C of a 2-byte element type) need "
                            "device-resident layouts"
                          : "costa: mixed-precision transforms (A and C of different element types) need "
                            "device-resident layouts");
@@ -2148,8 +2151,10 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
     // (a mixed plan's LOCAL list converts; its package holds the narrower type, so PACK converts
     // for narrowing pairs and UNPACK for widening ones, the other being a same-type list; every
     // list of a half-precision plan runs on the converting family, its same-type H -> H lists too)
-    const bool cv_pack = p.half() || (p.mixed() && p.pkg_dtype != p.src_dtype);
-    const bool cv_unpack = p.half() || (p.mixed() && p.pkg_dtype != p.dtype);
+    // (an FP8 plan's package holds A's type: PACK is a byte copy on the FP8 family when A holds Q and
+    // an ordinary FLOAT list when A is FLOAT; UNPACK always runs on the FP8 family, Q -> Q included)
+    const bool cv_pack = p.half() || (p.fp8() ? dtype_is_fp8(p.src_dtype) : p.mixed() && p.pkg_dtype != p.src_dtype);
+    const bool cv_unpack = p.half() || p.fp8() || (p.mixed() && p.pkg_dtype != p.dtype);
     if (p.converting())
         cp->c_local = build_convert_work(p.src_dtype, p.dtype, p.local_ops, 0, 0, ord_l, w_l);
     else
@@ -2586,7 +2591,7 @@ void execute_tiles(costa_dtype_t dtype, const costa_tile_op_t* ops, int64_t n,
                    const void* src_base, void* dst_base, const void* scalars, int n_slots,
                    int device) {
     std::lock_guard<std::recursive_mutex> lk(g_mutex);
-    if (dtype_is_half(dtype))
+    if (dtype_is_half(dtype) || dtype_is_fp8(dtype))
         throw error(COSTA_ERR_ARG, std::string("costa_hip_execute_tiles: no same-type tile kernel for ") +
                                        dtype_name(dtype) + " (use costa_hip_execute_tiles_mixed)");
     device_ctx& dc = ctx(device);
@@ -2620,7 +2625,7 @@ void execute_tiles_mixed(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const
         throw error(COSTA_ERR_ARG, std::string("costa_hip_execute_tiles_mixed: cannot convert ") +
                                        dtype_name(src_dtype) + " to " + dtype_name(dst_dtype) +
                                        " (FLOAT <-> DOUBLE, CFLOAT <-> CDOUBLE, and HALF or BFLOAT16 with "
-                                       "itself or FLOAT only)");
+                                       "itself or FLOAT only, and FP8_E4M3 or FP8_E5M2 with itself or FLOAT)");
     device_ctx& dc = ctx(device);
     std::vector<costa_tile_op_t> v(ops, ops + n);
     for (const auto& op : v)
@@ -2647,7 +2652,7 @@ void execute_tiles_mixed(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const
 void execute_tiles_tri(costa_dtype_t dtype, const costa_tri_op_t* ops, int64_t n, const void* src_base,
                        void* dst_base, const void* scalars, int n_slots, int device) {
     std::lock_guard<std::recursive_mutex> lk(g_mutex);
-    if (dtype_is_half(dtype))
+    if (dtype_is_half(dtype) || dtype_is_fp8(dtype))
         throw error(COSTA_ERR_ARG, std::string("costa_hip_execute_tiles_tri: no edge-tile kernel for ") +
                                        dtype_name(dtype));
     device_ctx& dc = ctx(device);
@@ -2678,7 +2683,7 @@ void copy_and_transform(costa_dtype_t dtype, int n_rows, int n_cols, const void*
                         bool trans, bool conj, const void* alpha, const void* beta) {
     if (n_rows < 0 || n_cols < 0 || src_stride < 0 || dst_stride < 0)
         throw error(COSTA_ERR_ARG, "costa_hip_copy_and_transform: negative size or stride");
-    if (dtype_is_half(dtype))
+    if (dtype_is_half(dtype) || dtype_is_fp8(dtype))
         throw error(COSTA_ERR_ARG, std::string("costa_hip_copy_and_transform: no same-type tile kernel for ") +
                                        dtype_name(dtype));
     if (size_t(n_rows) * size_t(n_cols) == 0) return;  // memory_utils.hpp:72-74

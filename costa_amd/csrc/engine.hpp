@@ -22,6 +22,13 @@ bool dtype_is_half(costa_dtype_t t);  // the 2-byte types: COSTA_HALF, COSTA_BFL
 costa_dtype_t compute_dtype(costa_dtype_t src, costa_dtype_t dst);
 // H -> H of one H, FLOAT -> H, H -> FLOAT (H a 2-byte type): the pairs of half_kernels.hip
 bool half_pair(costa_dtype_t src, costa_dtype_t dst);
+// the 1-byte types (COSTA_FP8_E4M3, COSTA_FP8_E5M2; compute_dtype is FLOAT for them too) and their
+// pairs Q -> Q of one Q, FLOAT -> Q, Q -> FLOAT: the pairs of fp8_kernels.hip
+bool dtype_is_fp8(costa_dtype_t t);
+bool fp8_pair(costa_dtype_t src, costa_dtype_t dst);
+// element type of the packages of an (A, C) plan: the narrower of the two; A's for FP8 pairs
+// (FLOAT -> Q carries FLOAT: its source is not rounded before the arithmetic)
+costa_dtype_t plan_pkg_dtype(costa_dtype_t src, costa_dtype_t dst);
 
 // One local block, element-type erased.  Intervals are in the layout's own (untransposed)
 // global coordinates; `data` points at its first element.
@@ -94,7 +101,11 @@ struct plan {
     bool half() const { return dtype_is_half(src_dtype) || dtype_is_half(dtype); }
     // every list of the plan runs on a converting family, or (mixed, not half) LOCAL and one of
     // PACK / UNPACK
-    bool converting() const { return mixed() || half(); }
+    // FP8 plans (A or C of a 1-byte type Q; Q -> Q, FLOAT -> Q, Q -> FLOAT): pkg_dtype is A's type.
+    // LOCAL and UNPACK run on the converting family of fp8_kernels.hip; PACK is a byte copy of
+    // 1-byte tiles on it when A holds Q, and a same-type FLOAT list on tile_kernel when A is FLOAT.
+    bool fp8() const { return dtype_is_fp8(src_dtype) || dtype_is_fp8(dtype); }
+    bool converting() const { return mixed() || half() || fp8(); }
     costa_dtype_t scalar_dtype() const { return compute_dtype(src_dtype, dtype); }
     int rank = 0, n_ranks = 1;
     std::vector<costa_tile_op_t> local_ops, pack_ops, unpack_ops;
@@ -130,6 +141,8 @@ constexpr int kTriCut = 256;
 bool any_mixed(const std::vector<job>& jobs);
 // whether some job of the batch has a 2-byte element type on either side
 bool any_half(const std::vector<job>& jobs);
+// whether some job of the batch has a 1-byte element type on either side
+bool any_fp8(const std::vector<job>& jobs);
 
 // Build the plan of `rank` (of `n_ranks`) for a batch of jobs (host only).  `loopback` (test
 // mode, see loopback_exchange()): 1 = the rank's own tiles all go through pack -> exchange with
@@ -226,7 +239,7 @@ struct convert_list {
     int64_t n_items = 0;
     bool any_transpose = false;
 };
-bool convertible(costa_dtype_t src, costa_dtype_t dst);  // FLOAT <-> DOUBLE, CFLOAT <-> CDOUBLE, half_pair
+bool convertible(costa_dtype_t src, costa_dtype_t dst);  // FLOAT <-> DOUBLE, CFLOAT <-> CDOUBLE, half_pair, fp8_pair
 // the work list of a converting list: `ordered` = the ops with each side's VEC flag set from its
 // actual address (base + offset) and element size, `work` = every sub-tile of every op
 convert_list build_convert_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
@@ -242,6 +255,12 @@ void half_subtile(int* bf, int* bs);
 void launch_half(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_tile_op_t* d_ops,
                  const uint64_t* d_work, const convert_list& l, const char* src_base, char* dst_base,
                  const void* d_scalars, void* stream /* hipStream_t */);
+
+// ---- FP8 lists (fp8_kernels.hip), reached through convert_subtile / launch_convert ----
+void fp8_subtile(int* bf, int* bs);
+void launch_fp8(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_tile_op_t* d_ops,
+                const uint64_t* d_work, const convert_list& l, const char* src_base, char* dst_base,
+                const void* d_scalars, void* stream /* hipStream_t */);
 
 // ---- edge tiles of triangular transforms (tri_kernels.hip) ----
 // One kernel family, tri_kernel<T>, one workgroup per sub-tile of one costa_tri_op_t; the work

@@ -187,5 +187,7 @@ COSTA_INSTANTIATE_LAYOUTS(std::complex<double>)
 COSTA_INSTANTIATE_LAYOUTS(int)
 COSTA_INSTANTIATE_LAYOUTS(half_bits)
 COSTA_INSTANTIATE_LAYOUTS(bfloat16_bits)
+COSTA_INSTANTIATE_LAYOUTS(fp8_e4m3_bits)
+COSTA_INSTANTIATE_LAYOUTS(fp8_e5m2_bits)
 
 }  // namespace costa

@@ -37,6 +37,8 @@ size_t dtype_size(costa_dtype_t t) {
     case COSTA_INT32: return 4;
     case COSTA_HALF: return 2;
     case COSTA_BFLOAT16: return 2;
+    case COSTA_FP8_E4M3: return 1;
+    case COSTA_FP8_E5M2: return 1;
     }
     throw error(COSTA_ERR_ARG, "unknown dtype");
 }
@@ -44,13 +46,20 @@ size_t dtype_size(costa_dtype_t t) {
 bool dtype_is_complex(costa_dtype_t t) { return t == COSTA_CFLOAT || t == COSTA_CDOUBLE; }
 bool dtype_is_half(costa_dtype_t t) { return t == COSTA_HALF || t == COSTA_BFLOAT16; }
 
+bool dtype_is_fp8(costa_dtype_t t) { return t == COSTA_FP8_E4M3 || t == COSTA_FP8_E5M2; }
+
 costa_dtype_t compute_dtype(costa_dtype_t src, costa_dtype_t dst) {
-    return dtype_is_half(src) || dtype_is_half(dst) ? COSTA_FLOAT : dst;
+    return dtype_is_half(src) || dtype_is_half(dst) || dtype_is_fp8(src) || dtype_is_fp8(dst) ? COSTA_FLOAT : dst;
 }
 
 bool half_pair(costa_dtype_t src, costa_dtype_t dst) {
     return (dtype_is_half(src) && (dst == src || dst == COSTA_FLOAT)) ||
            (src == COSTA_FLOAT && dtype_is_half(dst));
+}
+
+bool fp8_pair(costa_dtype_t src, costa_dtype_t dst) {
+    return (dtype_is_fp8(src) && (dst == src || dst == COSTA_FLOAT)) ||
+           (src == COSTA_FLOAT && dtype_is_fp8(dst));
 }
 
 const char* dtype_name(costa_dtype_t t) {
@@ -62,8 +71,15 @@ const char* dtype_name(costa_dtype_t t) {
     case COSTA_INT32: return "INT32";
     case COSTA_HALF: return "HALF";
     case COSTA_BFLOAT16: return "BFLOAT16";
+    case COSTA_FP8_E4M3: return "FP8_E4M3";
+    case COSTA_FP8_E5M2: return "FP8_E5M2";
     }
     return "unknown";
+}
+
+costa_dtype_t plan_pkg_dtype(costa_dtype_t src, costa_dtype_t dst) {
+    if (fp8_pair(src, dst)) return src;
+    return dtype_size(src) < dtype_size(dst) ? src : dst;
 }
 
 bool any_masked(const std::vector<job>& jobs) {
@@ -84,6 +100,12 @@ bool any_half(const std::vector<job>& jobs) {
     return false;
 }
 
+bool any_fp8(const std::vector<job>& jobs) {
+    for (const job& jb : jobs)
+        if (jb.A && jb.C && (dtype_is_fp8(jb.A->dtype) || dtype_is_fp8(jb.C->dtype))) return true;
+    return false;
+}
+
 template <> costa_dtype_t dtype_of<float>() { return COSTA_FLOAT; }
 template <> costa_dtype_t dtype_of<double>() { return COSTA_DOUBLE; }
 template <> costa_dtype_t dtype_of<std::complex<float>>() { return COSTA_CFLOAT; }
@@ -91,6 +113,8 @@ template <> costa_dtype_t dtype_of<std::complex<double>>() { return COSTA_CDOUBL
 template <> costa_dtype_t dtype_of<int>() { return COSTA_INT32; }
 template <> costa_dtype_t dtype_of<half_bits>() { return COSTA_HALF; }
 template <> costa_dtype_t dtype_of<bfloat16_bits>() { return COSTA_BFLOAT16; }
+template <> costa_dtype_t dtype_of<fp8_e4m3_bits>() { return COSTA_FP8_E4M3; }
+template <> costa_dtype_t dtype_of<fp8_e5m2_bits>() { return COSTA_FP8_E5M2; }
 
 template <typename T>
 elayout erase(const grid_layout<T>& L) {
@@ -121,6 +145,8 @@ template elayout erase<std::complex<double>>(const grid_layout<std::complex<doub
 template elayout erase<int>(const grid_layout<int>&);
 template elayout erase<half_bits>(const grid_layout<half_bits>&);
 template elayout erase<bfloat16_bits>(const grid_layout<bfloat16_bits>&);
+template elayout erase<fp8_e4m3_bits>(const grid_layout<fp8_e4m3_bits>&);
+template elayout erase<fp8_e5m2_bits>(const grid_layout<fp8_e5m2_bits>&);
 
 namespace {
 
@@ -291,6 +317,9 @@ uint32_t scale_kind(costa_dtype_t dtype, const scal& s, bool copy_mode, bool con
     // 2-byte types: the scalars are fp32 and the branches those of the FLOAT transform
     case COSTA_HALF: return kind_t<float>(s, copy_mode, conj);
     case COSTA_BFLOAT16: return kind_t<float>(s, copy_mode, conj);
+    // 1-byte types: the same
+    case COSTA_FP8_E4M3: return kind_t<float>(s, copy_mode, conj);
+    case COSTA_FP8_E5M2: return kind_t<float>(s, copy_mode, conj);
     }
     throw error(COSTA_ERR_ARG, "unknown dtype");
 }
@@ -324,16 +353,16 @@ std::vector<job_params> check_jobs(const std::vector<job>& jobs, int n_ranks, co
     src_dtype = jobs[0].A->dtype;
     dtype = jobs[0].C->dtype;
     // mixed precision: convert(A) in C's type; only the 2:1 pairs of one kind convert
-    // (half precision: H -> H, FLOAT -> H, H -> FLOAT, computed in fp32)
+    // (half precision: H -> H, FLOAT -> H, H -> FLOAT, computed in fp32; FP8: the same three shapes)
     const bool pair_ok =
-        src_dtype == dtype || half_pair(src_dtype, dtype) ||
+        src_dtype == dtype || half_pair(src_dtype, dtype) || fp8_pair(src_dtype, dtype) ||
         (src_dtype == COSTA_FLOAT && dtype == COSTA_DOUBLE) || (src_dtype == COSTA_DOUBLE && dtype == COSTA_FLOAT) ||
         (src_dtype == COSTA_CFLOAT && dtype == COSTA_CDOUBLE) || (src_dtype == COSTA_CDOUBLE && dtype == COSTA_CFLOAT);
     if (!pair_ok)
         throw error(COSTA_ERR_ARG, std::string("costa::transform: cannot convert ") + dtype_name(src_dtype) +
                                        " (A) to " + dtype_name(dtype) +
                                        " (C): mixed transforms are FLOAT <-> DOUBLE, CFLOAT <-> CDOUBLE and "
-                                       "FLOAT <-> HALF or BFLOAT16");
+                                       "FLOAT <-> HALF or BFLOAT16, and FLOAT <-> FP8_E4M3 or FP8_E5M2");
     const bool cplx = dtype_is_complex(dtype);
     std::vector<job_params> out;
     for (const job& jb : jobs) {
@@ -360,6 +389,11 @@ std::vector<job_params> check_jobs(const std::vector<job>& jobs, int n_ranks, co
         if (ul != 'A' && (dtype_is_half(src_dtype) || dtype_is_half(dtype)))
             throw error(COSTA_ERR_ARG,
                         std::string("costa::transform: triangular (masked) transforms take no 2-byte "
+                                    "element type: ") +
+                            dtype_name(src_dtype) + " (A), " + dtype_name(dtype) + " (C)");
+        if (ul != 'A' && (dtype_is_fp8(src_dtype) || dtype_is_fp8(dtype)))
+            throw error(COSTA_ERR_ARG,
+                        std::string("costa::transform: triangular (masked) transforms take no 1-byte "
                                     "element type: ") +
                             dtype_name(src_dtype) + " (A), " + dtype_name(dtype) + " (C)");
         if (ul != 'A' && src_dtype != dtype)
@@ -393,10 +427,12 @@ std::unique_ptr<plan> make_plan(const std::vector<job>& jobs, int rank, int n_ra
     using tag_info = job_params;
     const std::vector<tag_info> tags = check_jobs(jobs, n_ranks, p->src_dtype, p->dtype);
     // element sizes of A, of C and of the package (the narrower type crosses the exchange:
-    // narrowing pairs convert in PACK, widening pairs in UNPACK); all equal for same-type plans
+    // narrowing pairs convert in PACK, widening pairs in UNPACK); all equal for same-type plans.
+    // FP8 pairs carry A's type, FLOAT -> Q too: its source is not rounded before the arithmetic,
+    // which happens in UNPACK
     const size_t EA = dtype_size(p->src_dtype), EC = dtype_size(p->dtype);
-    p->pkg_dtype = EA < EC ? p->src_dtype : p->dtype;
-    const size_t EP = std::min(EA, EC);
+    p->pkg_dtype = plan_pkg_dtype(p->src_dtype, p->dtype);
+    const size_t EP = dtype_size(p->pkg_dtype);
     std::vector<side_tile> send, recv;
     for (const job& jb : jobs) p->slots.push_back(jb.s);
     // prepare_to_send and prepare_to_recv are independent: the receive side runs on a second

@@ -330,6 +330,13 @@ struct half_bits {
 struct bfloat16_bits {
     uint16_t bits;
 };
+// ... and the 1-byte ones (COSTA_FP8_E4M3, COSTA_FP8_E5M2; costa_hip.h, "FP8"), likewise
+struct fp8_e4m3_bits {
+    uint8_t bits;
+};
+struct fp8_e5m2_bits {
+    uint8_t bits;
+};
 
 // ---- layout builders (defined in costa_amd/csrc/layout.cpp, instantiated for
 //      float, double, std::complex<float>, std::complex<double>, int and the two bits-only

@@ -56,7 +56,9 @@ typedef enum {
     COSTA_CDOUBLE = 3, /* std::complex<double>, interleaved re/im */
     COSTA_INT32 = 4,
     COSTA_HALF = 5,    /* IEEE binary16, 2 bytes, raw bits ("Half precision" below) */
-    COSTA_BFLOAT16 = 6 /* bfloat16, 2 bytes, raw bits */
+    COSTA_BFLOAT16 = 6, /* bfloat16, 2 bytes, raw bits */
+    COSTA_FP8_E4M3 = 7, /* OCP e4m3fn, 1 byte, raw bits ("FP8" below) */
+    COSTA_FP8_E5M2 = 8  /* OCP e5m2, 1 byte, raw bits */
 } costa_dtype_t;
 
 typedef struct costa_layout_s* costa_layout_t;
@@ -210,7 +212,39 @@ void costa_hip_comm_destroy(costa_comm_t comm);
  * "device-resident" otherwise); blocking, _async, batches and any communicator size work;
  * costa_hip_transform_tri, costa_hip_execute_tiles, costa_hip_execute_tiles_tri and
  * costa_hip_copy_and_transform refuse a 2-byte dtype with COSTA_ERR_ARG.  The C++
- * costa::transform<T> overloads and the ScaLAPACK shims take no half types. */
+ * costa::transform<T> overloads and the ScaLAPACK shims take no half types.
+ *
+ * FP8 (MI355X-native): COSTA_FP8_E4M3 is OCP e4m3fn (bias 7, no infinities, NaN = 0x7F / 0xFF,
+ * largest finite 448) and COSTA_FP8_E5M2 is OCP e5m2 (bias 15, infinities and NaNs as IEEE, largest
+ * finite 57344).  Both are 1 byte, held as raw bits; offsets, leading dimensions and counts are in
+ * elements as for every other type.  Write Q for one of the two.  The supported (A, C) pairs are
+ * Q -> Q of the same Q, COSTA_FLOAT -> Q and Q -> COSTA_FLOAT; every other pair with a 1-byte type
+ * (e4m3 <-> e5m2, Q with COSTA_HALF, COSTA_BFLOAT16, COSTA_DOUBLE, COSTA_INT32 or a complex type) is
+ * COSTA_ERR_ARG with a message naming both types.  alpha/beta are ONE fp32 each and the compute
+ * type is COSTA_FLOAT whenever a side is Q.  With w() the exact widening to fp32 and F(a, c) the
+ * COSTA_FLOAT same-type transform of one element (same branches, same operation order, no fma):
+ *   Q -> Q            C = cvt(F(w(A), w(C)))      (scale kind BITCOPY -- copy mode, alpha = 1,
+ *                                                  beta = 0 -- is a byte copy: NaN payloads survive)
+ *   COSTA_FLOAT -> Q  C = cvt(F(A, w(C)))
+ *   Q -> COSTA_FLOAT  C = F(w(A), C)
+ * cvt(), the conversion fp32 -> Q, is what torch-CPU's x.to(torch.float8_e4m3fn) / .to(torch.
+ * float8_e5m2) gives: round to nearest even, subnormals kept, the tie below the smallest subnormal
+ * to zero, the sign of zero kept, NaN to NaN; e4m3: any value that rounds above 448, and +-inf,
+ * becomes NaN (0x7F with the sign bit; 464 is a tie that rounds to 448, 465 becomes NaN); e5m2: any
+ * value that rounds above 57344 becomes +-inf (61440 is a tie that rounds to inf).
+ * COSTA_FLOAT -> Q differs from COSTA_FLOAT -> H on purpose: A is NOT rounded before the
+ * arithmetic.  The point of this leg is quantisation with alpha = 1 / scale, and rounding a value
+ * outside Q's range before scaling it destroys it.
+ * Packages of the exchange: Q -> Q and Q -> COSTA_FLOAT carry Q (PACK is a byte copy of 1-byte
+ * tiles, UNPACK converts); COSTA_FLOAT -> Q carries COSTA_FLOAT (PACK is an ordinary same-type
+ * COSTA_FLOAT list, UNPACK converts): the package type is A's although it is the wider one.  In all
+ * three pairs a tile gives the same bits whether it stays local or crosses.
+ * As for the half types: 'C' is 'T'.  Bytes of C that no tile writes stay bit-identical.
+ * Device-resident layouts only (COSTA_ERR_ARG with "device-resident" otherwise); blocking, _async,
+ * batches and any communicator size work, one (A, C) pair per batch; costa_hip_transform_tri,
+ * costa_hip_plan_export_tri, costa_hip_execute_tiles, costa_hip_execute_tiles_tri and
+ * costa_hip_copy_and_transform refuse a 1-byte dtype with COSTA_ERR_ARG.  The C++
+ * costa::transform<T> overloads and the ScaLAPACK shims take no FP8 types. */
 int costa_hip_transform(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
                         const void* beta, costa_comm_t comm);
 /* several layout pairs in one exchange; trans/alpha/beta are arrays of n entries
@@ -273,12 +307,16 @@ int costa_hip_execute_tiles(costa_dtype_t dtype, const costa_tile_op_t* ops, int
  * Half-precision pairs ("Half precision" above: (H, H), (COSTA_FLOAT, H), (H, COSTA_FLOAT)) run
  * here too, on half_kernel: `scalars` are then n_slots (alpha, beta) pairs of fp32, a 2-byte side
  * takes 8-byte vector accesses when 8-byte aligned, an fp32 side 16-byte ones when 16-byte aligned,
- * and COSTA_SCALE_BITCOPY of an (H, H) op is a byte copy. */
+ * and COSTA_SCALE_BITCOPY of an (H, H) op is a byte copy.
+ * FP8 pairs ("FP8" above: (Q, Q), (COSTA_FLOAT, Q), (Q, COSTA_FLOAT)) run here on fp8_kernel, with
+ * fp32 `scalars`: both sides of a (Q, Q) op take vector accesses when 16-byte aligned; next to an
+ * fp32 side (16-byte aligned) a 1-byte side takes 4-byte ones when 4-byte aligned; and
+ * COSTA_SCALE_BITCOPY of a (Q, Q) op is a byte copy. */
 int costa_hip_execute_tiles_mixed(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
                                   const costa_tile_op_t* ops, int64_t n, const void* src_base,
                                   void* dst_base, const void* scalars, int n_slots, int device);
-/* the sub-tile one workgroup of the converting kernels runs for a mixed or half-precision pair
- * ((H, H) included): elements along the source's fast (*bf) and slow (*bs) dimension */
+/* the sub-tile one workgroup of the converting kernels runs for a mixed, half-precision or FP8 pair
+ * ((H, H) and (Q, Q) included): elements along the source's fast (*bf) and slow (*bs) dimension */
 int costa_hip_convert_subtile(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, int* bf, int* bs);
 
 /* edge ops (costa_tri_op_t) of one dtype in ONE launch of tri_kernel; the VEC flags are recomputed
@@ -301,7 +339,7 @@ int costa_hip_tri_subtile(costa_dtype_t dtype, int* bf, int* bs);
  * unpack ops read the package type and write C's, local ops read A's and write C's, and each
  * side's byte offsets and VEC flag follow its own element size.  Counts and displacements are in
  * elements; `scalars` are of C's dtype -- of the compute type COSTA_FLOAT (fp32) when A or C is a
- * 2-byte type, whose package holds the 2-byte type.
+ * 2-byte type, whose package holds the 2-byte type, or a 1-byte type, whose package holds A's type.
  * Call once with NULL arrays to get the sizes in *info, then again with arrays of
  * at least those sizes. */
 typedef struct {
@@ -364,8 +402,8 @@ typedef struct {
                              (costa_hip_set_list_builder) */
     int64_t fused_pieces; /* of tiny_items: wavefront pieces run as workgroups at the end of the
                              destination-block group launch (no tiny_kernel launch of their own) */
-    int64_t convert_items; /* sub-tiles run by convert_kernel and half_kernel (the converting lists
-                              of mixed and half-precision transforms,
+    int64_t convert_items; /* sub-tiles run by convert_kernel, half_kernel and fp8_kernel (the
+                              converting lists of mixed, half-precision and FP8 transforms,
                               costa_hip_execute_tiles_mixed) */
     int64_t tri_items; /* sub-tiles run by tri_kernel (the edge tiles of triangular transforms,
                           costa_hip_execute_tiles_tri) */
