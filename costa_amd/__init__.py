@@ -34,6 +34,8 @@ __all__ = [
     "convert_subtile", "TileOp", "TriOp", "TRI_OP_DTYPE", "transform_tri", "transform_tri_async",
     "execute_tiles_tri", "plan_export_tri", "tri_cut", "tri_subtile", "tri_phase_ms",
     "plan_export", "set_profiling", "get_stats", "release_caches", "TILE_OP_DTYPE",
+    "ScaledOp", "SCALED_OP_DTYPE", "SCALED_F_ROWS", "transform_scaled", "execute_tiles_scaled",
+    "plan_export_scaled", "scaled_subtile", "scaled_items",
 ]
 
 FLOAT, DOUBLE, CFLOAT, CDOUBLE, INT32 = 0, 1, 2, 3, 4
@@ -67,6 +69,12 @@ TILE_OP_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8"), ("nf", "<i4"), ("ns", 
 # numpy view of costa_tri_op_t (48 bytes): the tile op's fields, then the diagonal
 TRI_LE = 0x40
 TRI_OP_DTYPE = np.dtype(TILE_OP_DTYPE.descr + [("diag", "<i4"), ("pad", "<i4")])
+
+
+# numpy view of costa_scaled_op_t (48 bytes): the tile op, then the target coordinates of its source
+# element (0, 0); flag SCALED_F_ROWS: the op's fast index walks target rows
+SCALED_F_ROWS = 0x80
+SCALED_OP_DTYPE = np.dtype([("op", TILE_OP_DTYPE), ("row0", "<i4"), ("col0", "<i4")])
 
 
 class CostaError(RuntimeError):
@@ -136,6 +144,12 @@ class TriOp(C.Structure):
     _fields_ = [("op", TileOp), ("diag", C.c_int32), ("pad", C.c_int32)]
 
 
+class ScaledOp(C.Structure):
+    """costa_scaled_op_t: source element (f, s) of the op is target element (row0 + f, col0 + s)
+    with flag SCALED_F_ROWS, (row0 + s, col0 + f) without."""
+    _fields_ = [("op", TileOp), ("row0", C.c_int32), ("col0", C.c_int32)]
+
+
 class PlanInfo(C.Structure):
     _fields_ = [("n_local", C.c_int64), ("n_pack", C.c_int64), ("n_unpack", C.c_int64),
                 ("send_elems", C.c_int64), ("recv_elems", C.c_int64),
@@ -144,6 +158,10 @@ class PlanInfo(C.Structure):
 
 class TriPlanInfo(C.Structure):
     _fields_ = [("base", PlanInfo), ("n_local_tri", C.c_int64), ("n_unpack_tri", C.c_int64)]
+
+
+class ScaledPlanInfo(C.Structure):
+    _fields_ = [("base", PlanInfo), ("n_local_scaled", C.c_int64), ("n_unpack_scaled", C.c_int64)]
 
 
 class Stats(C.Structure):
@@ -207,6 +225,7 @@ def lib():
         "costa_hip_layout_destroy": (None, [vp]),
         "costa_hip_layout_reorder_ranks": (i, [vp, C.POINTER(i), i]),
         "costa_hip_layout_num_blocks": (i, [vp]),
+        "costa_hip_layout_shape": (i, [vp, C.POINTER(i), C.POINTER(i)]),
         "costa_hip_layout_block": (i, [vp, i, C.POINTER(i), C.POINTER(i), C.POINTER(i),
                                        C.POINTER(i), C.POINTER(vp), C.POINTER(i)]),
         "costa_hip_comm_self": (i, [i, C.POINTER(vp)]),
@@ -236,6 +255,13 @@ def lib():
         "costa_hip_tri_subtile": (i, [i, C.POINTER(i), C.POINTER(i)]),
         "costa_hip_plan_export_tri": (i, [vp, vp, c, c, i, vp, vp, i, i, C.POINTER(TriPlanInfo), vp, vp,
                                           vp, vp, vp, vp, vp, vp, vp, vp]),
+        "costa_hip_transform_scaled": (i, [vp, vp, c, vp, vp, vp, vp, vp]),
+        "costa_hip_transform_scaled_async": (i, [vp, vp, c, vp, vp, vp, vp, vp, vp]),
+        "costa_hip_execute_tiles_scaled": (i, [i, i, C.POINTER(ScaledOp), i64, vp, vp, vp, i, vp, vp, i]),
+        "costa_hip_scaled_subtile": (i, [i, i, C.POINTER(i), C.POINTER(i)]),
+        "costa_hip_scaled_items": (i, [C.POINTER(i64), i]),
+        "costa_hip_plan_export_scaled": (i, [vp, vp, c, vp, vp, i, i, C.POINTER(ScaledPlanInfo), vp, vp,
+                                             vp, vp, vp, vp, vp, vp]),
         "costa_hip_plan_export": (i, [i, C.POINTER(vp), C.POINTER(vp), C.c_char_p, vp, vp, i, i,
                                       C.POINTER(PlanInfo), vp, vp, vp, vp, vp, vp, vp, vp]),
         "costa_hip_set_profiling": (i, [i]),
@@ -323,6 +349,12 @@ class Layout:
         _check(lib().costa_hip_layout_block(self._h, i, *[C.byref(x) for x in v], C.byref(d),
                                             C.byref(ld)))
         return BlockInfo(v[0].value, v[1].value, v[2].value, v[3].value, d.value or 0, ld.value)
+
+    def shape(self) -> tuple:
+        """(m, n) of the matrix the layout describes (costa_hip_layout_shape)."""
+        m, n = C.c_int(), C.c_int()
+        _check(lib().costa_hip_layout_shape(self._h, C.byref(m), C.byref(n)))
+        return m.value, n.value
 
     def reorder_ranks(self, reordering: Sequence[int]):
         """Rank relabelling: owner(i, j) -> reordering[owner(i, j)] (reference
@@ -704,6 +736,116 @@ def plan_export_tri(A: Layout, Cl: Layout, rank: int, nranks: int, trans: str = 
                                        lt.ctypes.data, ut.ctypes.data, *[x.ctypes.data for x in cnt],
                                        sc.ctypes.data))
     return TriPlan(lo, po, uo, *cnt, sc, b.send_elems, b.recv_elems, b.local_elems, lt, ut)
+
+
+# ------------------------------------------------------------------ scaled transforms
+def _scale_arg(v, code: int, count: int, what: str) -> int:
+    """Address of a scale vector: None, a raw device address, or a torch CUDA tensor, which is
+    checked against the compute type, for contiguity and for its length."""
+    if v is None:
+        return 0
+    if isinstance(v, int):
+        return v
+    if type(v).__module__.split(".")[0] != "torch":
+        raise ValueError(f"{what}: a torch CUDA tensor or a raw device address, not {type(v)}")
+    if not v.is_cuda:
+        raise ValueError(f"{what}: the tensor must be device-resident (a CUDA tensor)")
+    if dtype_code(v.dtype) != code:
+        raise ValueError(f"{what}: dtype {v.dtype}, the compute type is {np.dtype(_NP[code]).name}")
+    if not v.is_contiguous():
+        raise ValueError(f"{what}: the tensor must be contiguous")
+    if v.numel() != count:
+        raise ValueError(f"{what}: {v.numel()} elements, the matrix has {count}")
+    return v.data_ptr()
+
+
+def transform_scaled(A: Layout, Cl: Layout, comm: Comm, trans: str = "N", alpha=1, beta=0,
+                     row_scale=None, col_scale=None, stream=None):
+    """C(i, j) = beta*C(i, j) + alpha*((op(A)(i, j) * row_scale[i]) * col_scale[j]), the scale
+    vectors fused into the tile kernels (costa_hip_transform_scaled).  ``row_scale`` (m elements)
+    and ``col_scale`` (n elements; m x n the matrix C's layout describes) are torch CUDA tensors or
+    raw device addresses of the compute type (float32; float64 for DOUBLE layouts); either may be
+    None, not both.  A tensor is checked for dtype, contiguity and length (ValueError).  With
+    ``stream`` (a torch stream or a raw hipStream_t address) the call is stream-ordered
+    (costa_hip_transform_scaled_async) and the vectors must stay valid until the stream has passed
+    it.  A and C may be the same layout when trans is 'N' (in place)."""
+    if not isinstance(A, Layout) or not isinstance(Cl, Layout):
+        raise CostaError(1, "costa: batches of scaled layout pairs are not supported")
+    code = _scalar_code(A.dtype, Cl.dtype)
+    m, n = Cl.shape()
+    rp = _scale_arg(row_scale, code, m, "row_scale")
+    cp = _scale_arg(col_scale, code, n, "col_scale")
+    ab, bb = _scalar_bytes(code, alpha), _scalar_bytes(code, beta)
+    if stream is None:
+        _check(lib().costa_hip_transform_scaled(A.handle, Cl.handle, _chr(trans), ab, bb,
+                                                C.c_void_p(rp), C.c_void_p(cp), comm.handle))
+    else:
+        s = getattr(stream, "cuda_stream", stream) or 0
+        _check(lib().costa_hip_transform_scaled_async(A.handle, Cl.handle, _chr(trans), ab, bb,
+                                                      C.c_void_p(rp), C.c_void_p(cp), comm.handle,
+                                                      C.c_void_p(s)))
+
+
+def execute_tiles_scaled(src_dtype, dst_dtype, ops: np.ndarray, scalars: np.ndarray, src_base=0,
+                         dst_base=0, row_scale=None, col_scale=None, device: int = 0):
+    """Run a list of scaled ops (numpy array of SCALED_OP_DTYPE) in one launch of the scaled kernel;
+    ``scalars`` are of the compute type, the scale vectors device arrays of it indexed by the ops'
+    target coordinates (costa_hip_execute_tiles_scaled)."""
+    sc_, dc_ = element_code(src_dtype), element_code(dst_dtype)
+    ops = np.ascontiguousarray(ops, dtype=SCALED_OP_DTYPE)
+    sc = np.ascontiguousarray(scalars, dtype=_NP[_scalar_code(sc_, dc_)]).reshape(-1)
+    assert sc.size % 2 == 0
+    _check(lib().costa_hip_execute_tiles_scaled(sc_, dc_, ops.ctypes.data_as(C.POINTER(ScaledOp)),
+                                                ops.size, C.c_void_p(_ptr(src_base)),
+                                                C.c_void_p(_ptr(dst_base)), sc.ctypes.data,
+                                                sc.size // 2, C.c_void_p(_ptr(row_scale)),
+                                                C.c_void_p(_ptr(col_scale)), device))
+
+
+def scaled_subtile(src_dtype, dst_dtype) -> tuple:
+    """(BF, BS): the sub-tile one workgroup of the scaled kernel runs for an accepted pair."""
+    bf, bs = C.c_int(0), C.c_int(0)
+    _check(lib().costa_hip_scaled_subtile(element_code(src_dtype), element_code(dst_dtype),
+                                          C.byref(bf), C.byref(bs)))
+    return bf.value, bs.value
+
+
+def scaled_items(reset: bool = False) -> int:
+    """Sub-tiles run by the scaled kernel since the last reset."""
+    v = C.c_int64(0)
+    _check(lib().costa_hip_scaled_items(C.byref(v), int(reset)))
+    return v.value
+
+
+@dataclass
+class ScaledPlan(Plan):
+    local_scaled: np.ndarray = None   # SCALED_OP_DTYPE: every tile that stays on the rank
+    unpack_scaled: np.ndarray = None  # SCALED_OP_DTYPE: every tile read from the receive package
+
+
+def plan_export_scaled(A: Layout, Cl: Layout, rank: int, nranks: int, trans: str = "N", alpha=1,
+                       beta=0) -> ScaledPlan:
+    """Tile-op lists of `rank` for a scaled transform (host planner, never touches a GPU): the
+    ordinary plan with every local and unpack op in ``local_scaled`` / ``unpack_scaled``; the
+    ordinary ``local_ops`` / ``unpack_ops`` are empty."""
+    if not isinstance(A, Layout) or not isinstance(Cl, Layout):
+        raise CostaError(1, "costa: batches of scaled layout pairs are not supported")
+    code = _scalar_code(A.dtype, Cl.dtype)
+    ab, bb = _scalar_bytes(code, alpha), _scalar_bytes(code, beta)
+    info = ScaledPlanInfo()
+    L = lib()
+    args = (A.handle, Cl.handle, _chr(trans), ab, bb, rank, nranks, C.byref(info))
+    _check(L.costa_hip_plan_export_scaled(*args, *([None] * 8)))
+    b = info.base
+    po = np.zeros(b.n_pack, TILE_OP_DTYPE)
+    ls = np.zeros(info.n_local_scaled, SCALED_OP_DTYPE)
+    us = np.zeros(info.n_unpack_scaled, SCALED_OP_DTYPE)
+    cnt = [np.zeros(nranks, np.int64) for _ in range(4)]
+    sc = np.zeros(2 * b.n_slots, _NP[code])
+    _check(L.costa_hip_plan_export_scaled(*args, po.ctypes.data, ls.ctypes.data, us.ctypes.data,
+                                          *[x.ctypes.data for x in cnt], sc.ctypes.data))
+    return ScaledPlan(np.zeros(b.n_local, TILE_OP_DTYPE), po, np.zeros(b.n_unpack, TILE_OP_DTYPE), *cnt,
+                      sc, b.send_elems, b.recv_elems, b.local_elems, ls, us)
 
 
 # ------------------------------------------------------------------ measurement

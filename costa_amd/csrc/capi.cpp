@@ -264,6 +264,15 @@ int costa_hip_layout_num_blocks(costa_layout_t layout) {
     return layout ? int(layout->e.blocks.size()) : -1;
 }
 
+int costa_hip_layout_shape(costa_layout_t layout, int* m, int* n) {
+    return guarded([&] {
+        if (!layout || !m || !n) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        const auto& e = layout->e;
+        *m = e.rows_split.empty() ? 0 : e.rows_split.back() - e.rows_split.front();
+        *n = e.cols_split.empty() ? 0 : e.cols_split.back() - e.cols_split.front();
+    });
+}
+
 int costa_hip_layout_block(costa_layout_t layout, int i, int* row_start, int* row_end,
                            int* col_start, int* col_end, void** data, int* ld) {
     return guarded([&] {
@@ -421,6 +430,118 @@ int costa_hip_plan_export_tri(costa_layout_t A, costa_layout_t C, char trans, ch
         cp(p->recv_displs, recv_displs);
         if (scalars) {
             const size_t E = dtype_size(p->dtype);
+            auto* out = static_cast<unsigned char*>(scalars);
+            std::memcpy(out, p->slots[0].alpha.data(), E);
+            std::memcpy(out + E, p->slots[0].beta.data(), E);
+        }
+    });
+}
+
+namespace {
+// the one job of a scaled transform
+std::vector<job> make_scaled_job(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                                 const void* beta, const void* row_scale, const void* col_scale) {
+    auto jobs = make_jobs(1, &A, &C, &trans, alpha, beta);
+    jobs[0].scaled = true;
+    jobs[0].row_scale = row_scale;
+    jobs[0].col_scale = col_scale;
+    return jobs;
+}
+void check_scale_vectors(const void* row_scale, const void* col_scale) {
+    if (!row_scale && !col_scale)
+        throw costa::engine::error(COSTA_ERR_ARG, "costa_hip_transform_scaled: both scale vectors are "
+                                                  "NULL (use costa_hip_transform)");
+}
+}  // namespace
+
+int costa_hip_transform_scaled(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                               const void* beta, const void* row_scale, const void* col_scale,
+                               costa_comm_t comm) {
+    return gpu_guarded([&] {
+        if (!comm || !alpha || !beta) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        auto jobs = make_scaled_job(A, C, trans, alpha, beta, row_scale, col_scale);
+        costa_dtype_t a, c;  // an unsupported pair is reported first
+        costa::engine::check_jobs(jobs, costa::engine::comm_size(comm->c), a, c);
+        check_scale_vectors(row_scale, col_scale);
+        costa::engine::transform(jobs, comm->c);
+    });
+}
+
+int costa_hip_transform_scaled_async(costa_layout_t A, costa_layout_t C, char trans,
+                                     const void* alpha, const void* beta, const void* row_scale,
+                                     const void* col_scale, costa_comm_t comm, void* stream) {
+    return gpu_guarded([&] {
+        if (!comm || !alpha || !beta) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        auto jobs = make_scaled_job(A, C, trans, alpha, beta, row_scale, col_scale);
+        costa_dtype_t a, c;
+        costa::engine::check_jobs(jobs, costa::engine::comm_size(comm->c), a, c);
+        check_scale_vectors(row_scale, col_scale);
+        costa::engine::transform(jobs, comm->c, stream, true);
+    });
+}
+
+int costa_hip_execute_tiles_scaled(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
+                                   const costa_scaled_op_t* ops, int64_t n, const void* src_base,
+                                   void* dst_base, const void* scalars, int n_slots,
+                                   const void* row_scale, const void* col_scale, int device) {
+    static_assert(sizeof(costa_scaled_op_t) == 48, "descriptor size");
+    return gpu_guarded([&] {
+        if (n < 0 || (n > 0 && (!ops || !scalars)))
+            throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::execute_tiles_scaled(src_dtype, dst_dtype, ops, n, src_base, dst_base, scalars,
+                                            n_slots, row_scale, col_scale, device);
+    });
+}
+
+int costa_hip_scaled_subtile(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, int* bf, int* bs) {
+    return guarded([&] {
+        if (!bf || !bs) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::scaled_subtile(src_dtype, dst_dtype, bf, bs);
+    });
+}
+
+int costa_hip_scaled_items(int64_t* items, int reset) {
+    return guarded([&] {
+        if (!items) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        *items = costa::engine::scaled_items(reset != 0);
+    });
+}
+
+int costa_hip_plan_export_scaled(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                                 const void* beta, int rank, int nranks,
+                                 costa_scaled_plan_info_t* info, costa_tile_op_t* pack_ops,
+                                 costa_scaled_op_t* local_scaled, costa_scaled_op_t* unpack_scaled,
+                                 int64_t* send_counts, int64_t* send_displs, int64_t* recv_counts,
+                                 int64_t* recv_displs, void* scalars) {
+    return guarded([&] {
+        if (!info || !alpha || !beta) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        if (nranks < 1 || rank < 0 || rank >= nranks)
+            throw costa::engine::error(COSTA_ERR_ARG, "bad rank/size");
+        check_handles(1, &A, &C);
+        auto p = costa::engine::make_plan(make_scaled_job(A, C, trans, alpha, beta, nullptr, nullptr), rank,
+                                          nranks);
+        info->base.n_local = int64_t(p->local_ops.size());
+        info->base.n_pack = int64_t(p->pack_ops.size());
+        info->base.n_unpack = int64_t(p->unpack_ops.size());
+        info->base.send_elems = p->send_elems;
+        info->base.recv_elems = p->recv_elems;
+        info->base.local_elems = p->local_elems;
+        info->base.n_ranks = nranks;
+        info->base.n_slots = int32_t(p->slots.size());
+        info->n_local_scaled = int64_t(p->local_scaled.size());
+        info->n_unpack_scaled = int64_t(p->unpack_scaled.size());
+        auto cp = [](const auto& v, auto* dst) {
+            if (dst && !v.empty()) std::memcpy(dst, v.data(), v.size() * sizeof(v[0]));
+        };
+        cp(p->pack_ops, pack_ops);
+        cp(p->local_scaled, local_scaled);
+        cp(p->unpack_scaled, unpack_scaled);
+        cp(p->send_counts, send_counts);
+        cp(p->send_displs, send_displs);
+        cp(p->recv_counts, recv_counts);
+        cp(p->recv_displs, recv_displs);
+        if (scalars) {
+            const size_t E = dtype_size(p->scalar_dtype());
             auto* out = static_cast<unsigned char*>(scalars);
             std::memcpy(out, p->slots[0].alpha.data(), E);
             std::memcpy(out + E, p->slots[0].beta.data(), E);

@@ -314,6 +314,17 @@ void exchange_round_of_tri(const plan& p, int rounds, std::vector<int>& unpack_t
     }
 }
 
+void exchange_round_of_scaled(const plan& p, int rounds, std::vector<int>& unpack_round) {
+    const size_t E = dtype_size(p.pkg_dtype);
+    unpack_round.clear();
+    for (const auto& t : p.unpack_scaled) {  // by its last element, like every unpack op
+        const int64_t first = int64_t(t.op.src / E);
+        const int64_t last = first + int64_t(t.op.nf) * t.op.ns - 1;
+        const size_t q = peer_of(p.recv_displs, first);
+        unpack_round.push_back(round_of(last - p.recv_displs[q], p.recv_counts[q], E, rounds));
+    }
+}
+
 int comm_rank(const comm* c) { return c->rank; }
 int comm_size(const comm* c) { return c->size; }
 void comm_destroy(comm* c) { delete c; }
@@ -1765,6 +1776,9 @@ struct cached_plan {
     // edge tiles of a triangular plan (tri_kernels.hip): LOCAL, and UNPACK per exchange round
     dbuf d_local_tri, w_local_tri;
     tri_list t_local;
+    // the lists of a scaled plan (scaled_kernels.hip): LOCAL, and UNPACK per exchange round
+    dbuf d_local_sc, w_local_sc;
+    scaled_list s_local;
     struct xround {  // one exchange round: its pack ops (by their first element) and unpack
                      // ops (by their last element)
         dbuf d_pack, w_pack, d_unpack, w_unpack;
@@ -1772,6 +1786,8 @@ struct cached_plan {
         convert_list c_pack, c_unpack;
         dbuf d_unpack_tri, w_unpack_tri;
         tri_list t_unpack;
+        dbuf d_unpack_sc, w_unpack_sc;
+        scaled_list s_unpack;
         bool tr_unpack = false, ax_unpack = false;
     };
     std::vector<std::unique_ptr<xround>> rounds;
@@ -1957,8 +1973,10 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
             w = w << 8 | scale_kind(j.C->dtype, j.s, cm, std::toupper(j.trans) == 'C');
         key.push_back(w);
         // the mask of a triangular transform
+        // ... and whether the ops carry target coordinates (a scaled transform; its vectors are
+        // arguments of the call, not of the plan)
         key.push_back(uint64_t(uint8_t(std::toupper(static_cast<unsigned char>(j.uplo)))) << 32 |
-                      uint64_t(uint32_t(j.k)));
+                      uint64_t(j.scaled) << 40 | uint64_t(uint32_t(j.k)));
     }
     hasher h;
     for (uint64_t w : key) h.mix(w);
@@ -1983,7 +2001,8 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
     const bool fp8 = any_fp8(jobs);    // 1-byte element types: the same
     const bool mixed = any_mixed(jobs) || half || fp8;
     const bool masked = any_masked(jobs);
-    if (mixed || masked) {  // an unsupported pair is reported as such, whatever the residency
+    const bool scaled = any_scaled(jobs);
+    if (mixed || masked || scaled) {  // an unsupported pair is reported as such, whatever the residency
         costa_dtype_t a, b;
         check_jobs(jobs, c->size, a, b);
     }
@@ -2011,6 +2030,8 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
                            "device-resident layouts"
                          : "costa: mixed-precision transforms (A and C of different element types) need "
                            "device-resident layouts");
+    if (!all_dev && scaled)
+        throw error(COSTA_ERR_ARG, "costa: scaled transforms need device-resident layouts");
     if (!all_dev) {
         cp->staged = true;
         std::vector<const elayout*> As, Cs;
@@ -2166,6 +2187,17 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
     std::vector<costa_tri_op_t> ord_lt;
     std::vector<uint64_t> w_lt;
     if (!p.local_tri.empty()) cp->t_local = build_tri_work(p.dtype, p.local_tri, 0, 0, ord_lt, w_lt);
+    // a scaled plan's LOCAL list, its sub-tiles in destination-address order (COSTA_SCALED_ORDER=0,
+    // tuning: list order; DESIGN 3h has both)
+    std::vector<costa_scaled_op_t> ord_ls;
+    std::vector<uint64_t> w_ls;
+    if (!p.local_scaled.empty()) {
+        static const bool by_dst = [] {
+            const char* e = tuning_env("COSTA_SCALED_ORDER");
+            return !e || std::atoi(e) != 0;
+        }();
+        cp->s_local = build_scaled_work(p.src_dtype, p.dtype, p.local_scaled, 0, 0, ord_ls, w_ls, by_dst);
+    }
     // exchange rounds: pack ops go to the round of their first element (every element a round
     // sends is packed by then), unpack ops to the round of their last (every element they read
     // has arrived)
@@ -2183,6 +2215,13 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
         std::vector<int> tr;
         exchange_round_of_tri(p, R, tr);
         for (size_t i = 0; i < p.unpack_tri.size(); ++i) upt[size_t(tr[i])].push_back(p.unpack_tri[i]);
+    }
+    std::vector<std::vector<costa_scaled_op_t>> ups(static_cast<size_t>(R)), ord_us(static_cast<size_t>(R));
+    std::vector<std::vector<uint64_t>> w_us(static_cast<size_t>(R));
+    if (!p.unpack_scaled.empty()) {
+        std::vector<int> sr;
+        exchange_round_of_scaled(p, R, sr);
+        for (size_t i = 0; i < p.unpack_scaled.size(); ++i) ups[size_t(sr[i])].push_back(p.unpack_scaled[i]);
     }
     std::vector<std::vector<costa_tile_op_t>> ord_p(static_cast<size_t>(R)), ord_u(static_cast<size_t>(R));
     std::vector<std::vector<uint64_t>> w_p(static_cast<size_t>(R)), w_u(static_cast<size_t>(R));
@@ -2205,6 +2244,9 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
                                      &sec_u[size_t(r)]);
         if (!upt[size_t(r)].empty())
             x->t_unpack = build_tri_work(p.dtype, upt[size_t(r)], 0, 0, ord_ut[size_t(r)], w_ut[size_t(r)]);
+        if (!ups[size_t(r)].empty())  // (package offsets are relative to the 256-byte aligned buffer)
+            x->s_unpack = build_scaled_work(p.pkg_dtype, p.dtype, ups[size_t(r)], 0, 0, ord_us[size_t(r)],
+                                            w_us[size_t(r)], false);
         cp->rounds.push_back(std::move(x));
     }
     t_work = now() - t0 - t_resid - t_plan;
@@ -2214,9 +2256,17 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
         cp->d_local_tri.upload(ord_lt, dc.main);
         cp->w_local_tri.upload(w_lt, dc.main);
     }
+    if (cp->s_local.n_items) {
+        cp->d_local_sc.upload(ord_ls, dc.main);
+        cp->w_local_sc.upload(w_ls, dc.main);
+    }
     for (int r = 0; r < R; ++r) {
         auto& x = *cp->rounds[size_t(r)];
         const device_section& su = sec_u[size_t(r)];
+        if (x.s_unpack.n_items) {
+            x.d_unpack_sc.upload(ord_us[size_t(r)], dc.main);
+            x.w_unpack_sc.upload(w_us[size_t(r)], dc.main);
+        }
         x.d_pack.upload(ord_p[size_t(r)], dc.main);
         x.w_pack.upload(w_p[size_t(r)], dc.main);
         upload_list(x.d_unpack, ord_u[size_t(r)], su.d_ordered, su.at_ordered, su.n_ordered, dc.main);
@@ -2274,6 +2324,7 @@ namespace {
 // and is also kept on its own, tri_phase_ms())
 enum phase { PH_LOCAL, PH_PACK, PH_EXCHANGE, PH_UNPACK, PH_H2D, PH_D2H, PH_TRI_LOCAL, PH_TRI_UNPACK };
 double g_tri_ms = 0;
+int64_t g_scaled_items = 0;  // sub-tiles run by scaled_kernel (kept beside costa_stats_t)
 
 struct phase_timer {
     device_ctx& dc;
@@ -2393,6 +2444,17 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
     cached_plan& cp = *get_plan(jobs, c, dc);
     const plan& p = *cp.p;
     const size_t E = dtype_size(p.pkg_dtype);  // of the send / receive packages
+    // the vectors of a scaled transform: arguments of this call, read by its LOCAL / UNPACK kernels
+    const void* row_scale = p.scaled ? jobs[0].row_scale : nullptr;
+    const void* col_scale = p.scaled ? jobs[0].col_scale : nullptr;
+    if (p.scaled) {
+        if (!row_scale && !col_scale)
+            throw error(COSTA_ERR_ARG, "costa: a scaled transform without scale vectors (use costa_hip_transform)");
+        for (const void* v : {row_scale, col_scale})
+            if (v && !is_device_ptr(v))
+                throw error(COSTA_ERR_ARG, "costa: the scale vectors of a scaled transform must be "
+                                           "device-resident");
+    }
     if (async && (cp.staged || cp.pipe))
         throw error(COSTA_ERR_ARG,
                     "costa: asynchronous transforms need device-resident layouts (host data is "
@@ -2468,6 +2530,14 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
         tm.stop();
     }
 
+    if (cp.s_local.n_items) {  // the LOCAL list of a scaled plan
+        tm.start(PH_LOCAL, ls);
+        launch_scaled(p.src_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(cp.d_local_sc.p),
+                      static_cast<const uint64_t*>(cp.w_local_sc.p), cp.s_local, nullptr, nullptr,
+                      cp.d_scal.p, row_scale, col_scale, ls);
+        tm.stop();
+    }
+
     if (exchange) {
         dc.send.reserve(size_t(p.send_elems) * E + 256);
         dc.recv.reserve(size_t(p.recv_elems) * E + 256);
@@ -2528,6 +2598,14 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
                            cp.d_scal.p, dc.aux);
                 tm.stop();
             }
+            if (x.s_unpack.n_items) {  // the round's unpack list of a scaled plan
+                HIP_CHECK(hipStreamWaitEvent(dc.aux, dc.ev_moved[size_t(r)], 0));
+                tm.start(PH_UNPACK, dc.aux);
+                launch_scaled(p.pkg_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(x.d_unpack_sc.p),
+                              static_cast<const uint64_t*>(x.w_unpack_sc.p), x.s_unpack, rb, nullptr,
+                              cp.d_scal.p, row_scale, col_scale, dc.aux);
+                tm.stop();
+            }
         }
         // the call ends on main once LOCAL, every unpack and every round of the exchange are done
         HIP_CHECK(hipEventRecord(dc.ev_local, dc.aux));
@@ -2555,7 +2633,8 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
             g_stats.fused_pieces += w.n_tiny;
     };
     g_stats.tri_items += cp.t_local.n_items;
-    if (cp.l_local.n_items() || cp.c_local.n_items || cp.t_local.n_items) {
+    g_scaled_items += cp.s_local.n_items;
+    if (cp.l_local.n_items() || cp.c_local.n_items || cp.t_local.n_items || cp.s_local.n_items) {
         g_stats.local_launches++;
         g_stats.local_bytes += p.local_bytes;
         count_items(cp.l_local);
@@ -2564,8 +2643,10 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
     if (exchange) {
         for (const auto& x : cp.rounds) {
             g_stats.pack_launches += x->l_pack.n_items() || x->c_pack.n_items ? 1 : 0;
-            g_stats.unpack_launches += x->l_unpack.n_items() || x->c_unpack.n_items || x->t_unpack.n_items ? 1 : 0;
+            g_stats.unpack_launches +=
+                x->l_unpack.n_items() || x->c_unpack.n_items || x->t_unpack.n_items || x->s_unpack.n_items ? 1 : 0;
             g_stats.tri_items += x->t_unpack.n_items;
+            g_scaled_items += x->s_unpack.n_items;
             count_items(x->l_pack);
             count_items(x->l_unpack);
             g_stats.convert_items += x->c_pack.n_items + x->c_unpack.n_items;
@@ -2676,6 +2757,51 @@ void execute_tiles_tri(costa_dtype_t dtype, const costa_tri_op_t* ops, int64_t n
                static_cast<const char*>(src_base), static_cast<char*>(dst_base), d_scal.p, dc.main);
     HIP_CHECK(hipStreamSynchronize(dc.main));
     g_stats.tri_items += l.n_items;
+}
+
+void execute_tiles_scaled(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* ops,
+                          int64_t n, const void* src_base, void* dst_base, const void* scalars,
+                          int n_slots, const void* row_scale, const void* col_scale, int device) {
+    std::lock_guard<std::recursive_mutex> lk(g_mutex);
+    if (!scaled_pair(src_dtype, dst_dtype))
+        throw error(COSTA_ERR_ARG, std::string("costa_hip_execute_tiles_scaled: no scaled kernel for ") +
+                                       dtype_name(src_dtype) + " -> " + dtype_name(dst_dtype));
+    if (!row_scale && !col_scale)
+        throw error(COSTA_ERR_ARG, "costa_hip_execute_tiles_scaled: no scale vector (use "
+                                   "costa_hip_execute_tiles_mixed)");
+    device_ctx& dc = ctx(device);
+    for (const void* v : {row_scale, col_scale})
+        if (v && !is_device_ptr(v))
+            throw error(COSTA_ERR_ARG, "costa_hip_execute_tiles_scaled: the scale vectors must be "
+                                       "device-resident");
+    std::vector<costa_scaled_op_t> v(ops, ops + n);
+    for (const auto& t : v)
+        if ((t.op.flags >> COSTA_SLOT_SHIFT) >= uint32_t(std::max(n_slots, 0)))
+            throw error(COSTA_ERR_ARG, "costa_hip_execute_tiles_scaled: scalar slot out of range");
+    std::vector<costa_scaled_op_t> ord;
+    std::vector<uint64_t> w;
+    const scaled_list l = build_scaled_work(src_dtype, dst_dtype, v, reinterpret_cast<uintptr_t>(src_base),
+                                            reinterpret_cast<uintptr_t>(dst_base), ord, w, false);
+    if (!l.n_items) return;
+    dbuf d_ops, d_work, d_scal;
+    d_ops.upload(ord, dc.main);
+    d_work.upload(w, dc.main);
+    const size_t E = dtype_size(compute_dtype(src_dtype, dst_dtype));
+    std::vector<unsigned char> sc(static_cast<const unsigned char*>(scalars),
+                                  static_cast<const unsigned char*>(scalars) + size_t(n_slots) * 2 * E);
+    d_scal.upload(sc, dc.main);
+    launch_scaled(src_dtype, dst_dtype, static_cast<const costa_scaled_op_t*>(d_ops.p),
+                  static_cast<const uint64_t*>(d_work.p), l, static_cast<const char*>(src_base),
+                  static_cast<char*>(dst_base), d_scal.p, row_scale, col_scale, dc.main);
+    HIP_CHECK(hipStreamSynchronize(dc.main));
+    g_scaled_items += l.n_items;
+}
+
+int64_t scaled_items(bool reset) {
+    std::lock_guard<std::recursive_mutex> lk(g_mutex);
+    const int64_t v = g_scaled_items;
+    if (reset) g_scaled_items = 0;
+    return v;
 }
 
 void copy_and_transform(costa_dtype_t dtype, int n_rows, int n_cols, const void* src,

@@ -82,6 +82,12 @@ struct job {
     // (i, j from the first row / column of C's layout), 'A' (the default) all of them
     char uplo = 'A';
     int k = 0;
+    // scaled transforms (costa_hip_transform_scaled): every LOCAL and UNPACK op carries its target
+    // coordinates; the vectors (device arrays of the compute type, either may be null) are arguments
+    // of the call, not part of the plan or of its cache key
+    bool scaled = false;
+    const void* row_scale = nullptr;
+    const void* col_scale = nullptr;
 };
 
 // The three tile-op lists of one rank plus the exchange geometry.  Addresses of pack
@@ -112,6 +118,10 @@ struct plan {
     // triangular transforms: the LOCAL and UNPACK ops of the tiles the mask's diagonal cuts (their
     // pack ops are ordinary dense copies in pack_ops); empty for every other plan
     std::vector<costa_tri_op_t> local_tri, unpack_tri;
+    // scaled transforms: every LOCAL and UNPACK op, in the ordinary plan's order (local_ops and
+    // unpack_ops are then empty; pack_ops and the exchange geometry are the ordinary plan's)
+    bool scaled = false;
+    std::vector<costa_scaled_op_t> local_scaled, unpack_scaled;
     std::vector<int64_t> send_counts, send_displs, recv_counts, recv_displs;  // elements
     int64_t send_elems = 0, recv_elems = 0, local_elems = 0;
     std::vector<scal> slots;
@@ -137,6 +147,10 @@ bool any_masked(const std::vector<job>& jobs);
 // gives at most one ordinary tile (its wholly kept columns) and one edge tile narrower than the
 // band is tall, so an edge tile's dense pack op carries fewer than kTriCut dropped columns.
 constexpr int kTriCut = 256;
+// whether some job of the batch is a scaled one
+bool any_scaled(const std::vector<job>& jobs);
+// the (A, C) pairs of scaled transforms: FLOAT -> FLOAT, DOUBLE -> DOUBLE, half_pair, fp8_pair
+bool scaled_pair(costa_dtype_t src, costa_dtype_t dst);
 // whether some job of the batch converts (A's element type differs from C's)
 bool any_mixed(const std::vector<job>& jobs);
 // whether some job of the batch has a 2-byte element type on either side
@@ -280,6 +294,33 @@ void launch_tri(costa_dtype_t dtype, const costa_tri_op_t* d_ops, const uint64_t
                 void* stream /* hipStream_t */);
 void execute_tiles_tri(costa_dtype_t dtype, const costa_tri_op_t* ops, int64_t n, const void* src_base,
                        void* dst_base, const void* scalars, int n_slots, int device);
+
+// ---- scaled transforms (scaled_kernels.hip) ----
+// One kernel family, scaled_kernel<Es, Ed>, one workgroup per sub-tile of one costa_scaled_op_t; the
+// work items are (op index << 32) | sub-tile.  `row_scale` / `col_scale` are kernel arguments.
+void scaled_subtile(costa_dtype_t src, costa_dtype_t dst, int* bf, int* bs);
+struct scaled_list {
+    int64_t n_items = 0;
+    bool any_transpose = false;
+};
+// `ordered` = the ops with each side's VEC flag set from its actual address (base + offset) and its
+// strip's alignment, `work` = every sub-tile of every op: in list order, or (dst_order) by the
+// address of the sub-tile's first destination element
+scaled_list build_scaled_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
+                              const std::vector<costa_scaled_op_t>& ops, uint64_t src_base,
+                              uint64_t dst_base, std::vector<costa_scaled_op_t>& ordered,
+                              std::vector<uint64_t>& work, bool dst_order);
+void launch_scaled(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* d_ops,
+                   const uint64_t* d_work, const scaled_list& l, const char* src_base, char* dst_base,
+                   const void* d_scalars, const void* row_scale, const void* col_scale,
+                   void* stream /* hipStream_t */);
+void execute_tiles_scaled(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* ops,
+                          int64_t n, const void* src_base, void* dst_base, const void* scalars,
+                          int n_slots, const void* row_scale, const void* col_scale, int device);
+// sub-tiles run by scaled_kernel since the last reset
+int64_t scaled_items(bool reset);
+// ... of every scaled unpack op (plan::unpack_scaled), by the rule of exchange_round_of_ops
+void exchange_round_of_scaled(const struct plan& p, int rounds, std::vector<int>& unpack_round);
 
 // kernel launcher (tile_kernels.hip); `work` and `ops` are device arrays
 // ops small enough for one wavefront each (tiny path): copy mode up to kTinyCopyBytes of

@@ -72,63 +72,7 @@ static_assert((QBF / QWV) * QBS == QNT, "one pass of 16-byte strips");
 constexpr size_t kFp8LdsQ = size_t(QBS) * QPB;
 constexpr size_t kFp8LdsF = size_t(QBS) * QPF * 4;
 
-__device__ __forceinline__ uint32_t f2u(float x) {
-    uint32_t u;
-    __builtin_memcpy(&u, &x, 4);
-    return u;
-}
-__device__ __forceinline__ float u2f(uint32_t u) {
-    float x;
-    __builtin_memcpy(&x, &u, 4);
-    return x;
-}
-
-// The two 1-byte types: raw bits, exact widening, conversion as torch-CPU's .to(float8_*).
-// narrow() rounds to nearest even on the dropped mantissa bits in integers (a carry out of the
-// mantissa moves to the exponent); below the smallest normal the value is brought to the
-// subnormals' fixed point by one exact fp32 addition (the sum's ulp is the subnormal step, so the
-// addition itself rounds to nearest even, the tie below the smallest subnormal to zero).
-template <int MB, int BIAS>
-__device__ __forceinline__ uint32_t round_finite(uint32_t a) {  // |x| as fp32 bits, below the type's overflow
-    constexpr int DROP = 23 - MB;
-    constexpr uint32_t MIN_NORMAL = uint32_t(127 - BIAS + 1) << 23;
-    constexpr uint32_t MAGIC = uint32_t(127 + DROP - BIAS + 1) << 23;  // 2^(subnormal step + 23)
-    if (a < MIN_NORMAL) return f2u(u2f(a) + u2f(MAGIC)) - MAGIC;
-    a += (uint32_t(BIAS - 127) << 23) + ((1u << (DROP - 1)) - 1u) + ((a >> DROP) & 1u);
-    return a >> DROP;
-}
-struct e4m3_t {  // OCP e4m3fn: bias 7, no infinities, NaN = 0x7F / 0xFF, largest finite 448
-    static __device__ __forceinline__ float widen(uint32_t b) {
-        // the 7 magnitude bits read as binary16 (4-bit exponent in the low exponent bits) are the
-        // value / 2^8, subnormals included
-        const uint16_t hb = uint16_t((b & 0x7Fu) << 7);
-        _Float16 h;
-        __builtin_memcpy(&h, &hb, 2);
-        const uint32_t m = (b & 0x7Fu) == 0x7Fu ? 0x7FC00000u : f2u(static_cast<float>(h) * 256.0f);
-        return u2f(m | ((b & 0x80u) << 24));
-    }
-    static __device__ __forceinline__ uint32_t narrow(float x) {
-        const uint32_t u = f2u(x), a = u & 0x7FFFFFFFu, sign = (u >> 24) & 0x80u;
-        // 480 = 1.875 * 2^8 and above (inf, NaN) -> NaN; (464, 480) rounds to the NaN code by itself
-        if (a >= 0x43F00000u) return sign | 0x7Fu;
-        return sign | round_finite<3, 7>(a);
-    }
-};
-struct e5m2_t {  // OCP e5m2: bias 15, the high byte of IEEE binary16
-    static __device__ __forceinline__ float widen(uint32_t b) {
-        const uint16_t hb = uint16_t((b & 0xFFu) << 8);
-        _Float16 h;
-        __builtin_memcpy(&h, &hb, 2);
-        return static_cast<float>(h);
-    }
-    static __device__ __forceinline__ uint32_t narrow(float x) {
-        const uint32_t u = f2u(x), a = u & 0x7FFFFFFFu, sign = (u >> 24) & 0x80u;
-        // NaN; 61440 = 1.875 * 2^15 and above -> +-inf ((57344, 61440) rounds by itself, the tie to inf)
-        if (a >= 0x47700000u) return sign | (a > 0x7F800000u ? 0x7Fu : 0x7Cu);
-        return sign | round_finite<2, 15>(a);
-    }
-};
-
+// (e4m3_t / e5m2_t, the two 1-byte types, and round_finite: tile_device.hpp)
 // a strip of 4 elements: of Q (one dword, element e in byte e) / of fp32 (16 bytes)
 struct fstrip {
     float e[QV];

@@ -60,44 +60,7 @@ constexpr int HPS = HUNITS / HNW;                // store passes
 static_assert(HNT % HLPC == 0 && HBS % HCPP == 0 && HBS % HSW == 0 && HUNITS % HNW == 0, "mapping");
 constexpr size_t kHalfLds = size_t(HBS) * HP * 2;
 
-// the two 2-byte types: raw bits, exact widening, rounding to nearest even
-struct f16_t {
-    static __device__ __forceinline__ float widen(uint16_t b) {
-        _Float16 h;
-        __builtin_memcpy(&h, &b, 2);
-        return static_cast<float>(h);
-    }
-    static __device__ __forceinline__ uint16_t narrow(float x) {
-        const _Float16 h = static_cast<_Float16>(x);  // RNE, +-inf on overflow, subnormals kept
-        uint16_t b;
-        __builtin_memcpy(&b, &h, 2);
-        return b;
-    }
-};
-struct bf16_t {
-    static __device__ __forceinline__ float widen(uint16_t b) {
-        const uint32_t u = uint32_t(b) << 16;
-        float x;
-        __builtin_memcpy(&x, &u, 4);
-        return x;
-    }
-    static __device__ __forceinline__ uint16_t narrow(float x) {
-#ifdef COSTA_HALF_BF16_INT  // (tuning builds: the integer form of the same rounding)
-        uint32_t u;
-        __builtin_memcpy(&u, &x, 4);
-        if ((u & 0x7FFFFFFFu) > 0x7F800000u) return uint16_t((u >> 16) | 0x40u);  // NaN stays NaN
-        // round to nearest even on the 16 dropped bits; a carry out of the mantissa moves to the
-        // exponent (the finite maximum goes to inf), subnormals round like everything else
-        return uint16_t((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-#else
-        const __bf16 h = static_cast<__bf16>(x);  // v_cvt_pk_bf16_f32: RNE, +-inf on overflow, subnormals kept
-        uint16_t b;
-        __builtin_memcpy(&b, &h, 2);
-        return b;
-#endif
-    }
-};
-
+// (f16_t / bf16_t, the two 2-byte types: tile_device.hpp)
 // a strip of 4 elements of H (8 bytes) / of fp32 (16 bytes)
 struct hstrip {
     uint16_t e[HV];

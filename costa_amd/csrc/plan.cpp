@@ -88,6 +88,17 @@ bool any_masked(const std::vector<job>& jobs) {
     return false;
 }
 
+bool any_scaled(const std::vector<job>& jobs) {
+    for (const job& jb : jobs)
+        if (jb.scaled) return true;
+    return false;
+}
+
+bool scaled_pair(costa_dtype_t src, costa_dtype_t dst) {
+    return (src == dst && (src == COSTA_FLOAT || src == COSTA_DOUBLE)) || half_pair(src, dst) ||
+           fp8_pair(src, dst);
+}
+
 bool any_mixed(const std::vector<job>& jobs) {
     for (const job& jb : jobs)
         if (jb.A && jb.C && jb.A->dtype != jb.C->dtype) return true;
@@ -352,6 +363,20 @@ std::vector<job_params> check_jobs(const std::vector<job>& jobs, int n_ranks, co
     if (jobs.size() > 0xFFFF) throw error(COSTA_ERR_ARG, "costa::transform: too many layout pairs");
     src_dtype = jobs[0].A->dtype;
     dtype = jobs[0].C->dtype;
+    if (any_scaled(jobs)) {  // scaled transforms: their own set of pairs, one unmasked layout pair
+        if (!scaled_pair(src_dtype, dtype))
+            throw error(COSTA_ERR_ARG,
+                        std::string("costa::transform_scaled: no scaled transform for ") +
+                            dtype_name(src_dtype) + " (A) -> " + dtype_name(dtype) +
+                            " (C): the pairs are FLOAT -> FLOAT, DOUBLE -> DOUBLE, and HALF, BFLOAT16, "
+                            "FP8_E4M3 or FP8_E5M2 with itself or FLOAT");
+        if (jobs.size() > 1)
+            throw error(COSTA_ERR_ARG, "costa::transform_scaled: batches of scaled layout pairs are "
+                                       "not supported");
+        if (any_masked(jobs))
+            throw error(COSTA_ERR_ARG, "costa::transform_scaled: a scaled transform takes no "
+                                       "triangular mask");
+    }
     // mixed precision: convert(A) in C's type; only the 2:1 pairs of one kind convert
     // (half precision: H -> H, FLOAT -> H, H -> FLOAT, computed in fp32; FP8: the same three shapes)
     const bool pair_ok =
@@ -587,6 +612,27 @@ std::unique_ptr<plan> make_plan(const std::vector<job>& jobs, int rank, int n_ra
     for (auto& op : p->unpack_ops) p->unpack_bytes += op_alg_bytes(op, EP, EC);
     for (auto& t : p->local_tri) p->local_bytes += op_alg_bytes(t, EC);  // kept elements only
     for (auto& t : p->unpack_tri) p->unpack_bytes += op_alg_bytes(t, EC);
+    if (any_scaled(jobs)) {
+        // a scaled plan is the ordinary plan with every LOCAL and UNPACK op moved, in order and
+        // with its locality hint, to the scaled lists next to its target coordinates
+        // (tile_op.hpp scaled_op); the pack list and the exchange geometry stay as they are
+        p->scaled = true;
+        auto move = [&](std::vector<costa_tile_op_t>& ops, const std::vector<const side_tile*>& at,
+                        std::vector<costa_scaled_op_t>& out) {
+            out.reserve(ops.size());
+            for (size_t i = 0; i < ops.size(); ++i) {
+                const side_tile& m = *at[i];
+                const job& jb = jobs[size_t(m.tag)];
+                const tag_info& ti = tags[size_t(m.tag)];
+                out.push_back(scaled_op(ops[i], ti.a_cm, ti.transpose,
+                                        m.rows.start - jb.C->rows_split.front(),
+                                        m.cols.start - jb.C->cols_split.front()));
+            }
+            ops.clear();
+        };
+        move(p->local_ops, at_local, p->local_scaled);
+        move(p->unpack_ops, at_unpack, p->unpack_scaled);
+    }
     return p;
 }
 

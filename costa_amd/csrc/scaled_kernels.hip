@@ -1,0 +1,574 @@
+// Kernels of scaled transforms for CDNA4 (gfx950): tile ops with row / column scale vectors,
+//   C(i, j) = beta*C(i, j) + alpha * s_ij(op(A)(i, j)),     s_ij(x) = (x * r[i]) * c[j]
+// (costa_hip.h, "scaled transforms").  An op is a costa_scaled_op_t: a costa_tile_op_t plus the
+// target coordinates (row0, col0) of its source element (0, 0); with COSTA_SCALED_F_ROWS the op's
+// fast index f walks target rows (i = row0 + f, j = col0 + s), else columns (i = row0 + s,
+// j = col0 + f).  With w() the exact widening of a stored element to the compute type Tc (fp32; fp64
+// for the DOUBLE pair), cvt() the conversion Tc -> C's type and g() tile_kernel's scale<Tc> (same
+// branches, contraction off), an op computes for its source element x and old destination value y
+//   cvt(g(s_ij(w(x)), w(y)))          (FLOAT -> H: w(cvt_H(x)) in place of w(x))
+// in copy mode at dst(f, s), in transpose mode at dst(s, f).  The two products of s_ij are two
+// separately rounded multiplications, r first; a NULL vector's product is skipped (wave-uniform).
+// Scale kind BITCOPY is cvt(s_ij(w(x))): never a byte copy.  w() and cvt() are the device functions
+// of half_kernel and fp8_kernel (tile_device.hpp).
+//
+// One kernel family, scaled_kernel<Es, Ed> (Es / Ed: the element codecs of the two sides, Tc =
+// Ed::ct), driven like tri_kernel by a device array of ops and (op << 32) | sub-tile work items, with
+// r and c as kernel arguments.  One workgroup of 256 threads runs one 64 x 64 sub-tile: the
+// transposes are staged in the compute type (below), and 64 x 64 keeps that tile at 17 KiB (fp32) /
+// 33 KiB (fp64) -- 128 x 128 would take 66 / 132 KiB, one workgroup per CU -- and a lane at 4 strips
+// per side.  A lane's unit of work is a strip of 4 elements along the source's fast dimension: one
+// dword on a 1-byte side, 8 bytes on a 2-byte side, 16 bytes on fp32, two 16-byte accesses on fp64,
+// so consecutive lanes touch consecutive addresses on both sides.
+//   copy mode       no LDS.  All source strips, all old destination strips (AXPBY) and the scale
+//                   values are requested before the first use.  The scale along f (the destination's
+//                   fast index) is one strip per lane, the same for its 4 passes; the scale along s
+//                   one value per strip.  Every lane stores exactly the elements it loaded, so an op
+//                   whose source and destination coincide (in-place equilibration) is safe; the
+//                   data pointers carry no __restrict__.
+//   transpose mode  the sub-tile is staged in LDS in the compute type for every pair, Q -> Q
+//                   included: the scaling happens after the exchange (the strip load of the scale
+//                   along the destination's fast index wants the transposed arrangement), in Tc, so
+//                   fp8_kernel's byte staging would only move the widening behind the v_perm block
+//                   transpose at the price of a second staging scheme; one scheme serves 14 pairs.
+//                   Rows s, pitch 64 + 4 elements of fp32 (68 dwords) or 64 + 2 of fp64 (132 dwords):
+//                   both are 4 mod 64 dwords, one 16-byte slot further per row.  Reads: lane l of a
+//                   wavefront reads the strip of row l with ds_read_b128 (fp64: two), banks
+//                   (a / 4) mod 64; each of the instruction's 16-lane groups holds 16 rows that
+//                   differ mod 16, so their slots (17 l + q) mod 16 resp. (33 l + 2 q) mod 16 are all
+//                   distinct: conflict-free.  Writes: ds_write_b128, banks (a / 4) mod 32, groups of
+//                   8 consecutive lanes: fp32 lanes write 8 consecutive 16-byte strips of one row =
+//                   32 distinct banks, conflict-free; fp64 lanes write two 16-byte halves 32 bytes
+//                   apart, so lanes l and l + 4 of a group meet on a bank: 2-way on the fp64 writes
+//                   (accepted: 2 x 4 write instructions per lane and sub-tile against 64 KiB of HBM
+//                   traffic).  4 lanes then exchange their 4 x 4 block with lane_transpose (fp64:
+//                   the low and high words separately), so every lane stores a strip along the
+//                   destination's fast dimension; there the scale along s is the strip load and
+//                   the scale along f one value per strip.
+// Scale loads use the default cache policy (every sub-tile of a row or column band reads them
+// again); the data uses non-temporal accesses as elsewhere.  A scale strip is one (fp64: two) 16-byte
+// load where its address is 16-byte aligned (row0 / col0 + the sub-tile's origin a multiple of 4 on
+// an aligned vector) and element-wise otherwise.
+// Whole sub-tiles with both VEC flags take the FULL path, where every guard folds away; sub-tile
+// remainders and sides off their strip's alignment (VEC flag clear) take the guarded, element-wise
+// form of the same loads and stores: same values.  No scratch.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+#include <type_traits>
+#include <utility>
+
+#include "engine.hpp"
+#include "tile_device.hpp"
+
+#pragma clang fp contract(off)
+
+namespace costa {
+namespace engine {
+namespace {
+
+#ifndef COSTA_SCALED_NT  // (overridden in tuning builds: 1024 threads on 128 x 128)
+#define COSTA_SCALED_NT 256
+#define COSTA_SCALED_BF 64
+#define COSTA_SCALED_BS 64
+#endif
+constexpr int SNT = COSTA_SCALED_NT, SBF = COSTA_SCALED_BF, SBS = COSTA_SCALED_BS;  // threads, sub-tile (source fast x slow)
+constexpr int SV = 4;                         // elements of a strip
+constexpr int SLPC = SBF / SV;                // lanes per source column (load)
+constexpr int SCPP = SNT / SLPC;              // source columns per load pass
+constexpr int SPL = SBS / SCPP;               // load passes
+constexpr int SNW = SNT / 64;                 // wavefronts
+constexpr int SSW = 64;                       // s values of one store unit
+constexpr int SQG = SBF / SV;                 // f slots (store units) per s chunk
+constexpr int SUNITS = (SBS / SSW) * SQG;     // store units: 64 s x one f slot
+constexpr int SPS = SUNITS / SNW;             // store passes
+static_assert(SQG % SNW == 0 && SNT % SLPC == 0 && SBS % SCPP == 0 && SBS % SSW == 0 && SUNITS % SNW == 0, "mapping");
+
+// ---- element codecs: storage type st, compute type ct, w() and cvt() ----
+struct f32_e {
+    using st = float;
+    using ct = float;
+    static __device__ __forceinline__ float widen(float x) { return x; }
+    static __device__ __forceinline__ float narrow(float x) { return x; }
+};
+struct f64_e {
+    using st = double;
+    using ct = double;
+    static __device__ __forceinline__ double widen(double x) { return x; }
+    static __device__ __forceinline__ double narrow(double x) { return x; }
+};
+template <typename H>  // f16_t / bf16_t
+struct h_e {
+    using st = uint16_t;
+    using ct = float;
+    static __device__ __forceinline__ float widen(uint16_t b) { return H::widen(b); }
+    static __device__ __forceinline__ uint16_t narrow(float x) { return H::narrow(x); }
+};
+template <typename Q>  // e4m3_t / e5m2_t
+struct q_e {
+    using st = uint8_t;
+    using ct = float;
+    static __device__ __forceinline__ float widen(uint8_t b) { return Q::widen(b); }
+    static __device__ __forceinline__ uint8_t narrow(float x) { return uint8_t(Q::narrow(x)); }
+};
+template <typename H>  // the FLOAT source of a FLOAT -> H pair: rounded to H first
+struct f32_via {
+    using st = float;
+    using ct = float;
+    static __device__ __forceinline__ float widen(float x) { return H::widen(H::narrow(x)); }
+};
+
+// ---- strips of 4 stored elements ----
+template <typename S>
+struct strip {
+    S e[SV];
+};
+typedef uint32_t u32x2s __attribute__((ext_vector_type(2)));
+
+// one vector access (fp64: two) where `vec_ok` (the side is aligned to the strip) and the strip is
+// whole, else element by element; elements past n stay 0
+template <typename S>
+__device__ __forceinline__ strip<S> load_strip(const S* p, int n, bool vec_ok) {
+    strip<S> out{};
+    if (vec_ok && n >= SV) {
+        if constexpr (sizeof(S) == 1) {
+            const uint32_t v = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p));
+            __builtin_memcpy(&out, &v, 4);
+        } else if constexpr (sizeof(S) == 2) {
+            const u32x2s v = __builtin_nontemporal_load(reinterpret_cast<const u32x2s*>(p));
+            __builtin_memcpy(&out, &v, 8);
+        } else if constexpr (sizeof(S) == 4) {
+            const raw16 r = ld16(p);
+            __builtin_memcpy(&out, &r, 16);
+        } else {
+            const raw16 a = ld16(p), b = ld16(p + 2);
+            __builtin_memcpy(&out.e[0], &a, 16);
+            __builtin_memcpy(&out.e[2], &b, 16);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < SV; ++k)
+            if (k < n) out.e[k] = p[k];
+    }
+    return out;
+}
+template <typename S>
+__device__ __forceinline__ void store_strip(S* p, const strip<S>& in, int n, bool vec_ok) {
+    if (vec_ok && n >= SV) {
+        if constexpr (sizeof(S) == 1) {
+            uint32_t v;
+            __builtin_memcpy(&v, &in, 4);
+            __builtin_nontemporal_store(v, reinterpret_cast<uint32_t*>(p));
+        } else if constexpr (sizeof(S) == 2) {
+            u32x2s v;
+            __builtin_memcpy(&v, &in, 8);
+            __builtin_nontemporal_store(v, reinterpret_cast<u32x2s*>(p));
+        } else if constexpr (sizeof(S) == 4) {
+            raw16 r;
+            __builtin_memcpy(&r, &in, 16);
+            st16<true>(p, r);
+        } else {
+            raw16 a, b;
+            __builtin_memcpy(&a, &in.e[0], 16);
+            __builtin_memcpy(&b, &in.e[2], 16);
+            st16<true>(p, a);
+            st16<true>(p + 2, b);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < SV; ++k)
+            if (k < n) p[k] = in.e[k];
+    }
+}
+
+// a strip of a scale vector (default cache policy): 16-byte loads where the address allows, else
+// element by element; elements past n stay 0 and are never used
+template <typename C>
+__device__ __forceinline__ void load_scale4(C (&out)[SV], const C* v, int n) {
+#pragma unroll
+    for (int k = 0; k < SV; ++k) out[k] = C(0);
+    if (n >= SV && (reinterpret_cast<uintptr_t>(v) & 15u) == 0) {
+        constexpr int NQ = int(sizeof(C)) * SV / 16;
+        raw16 r[NQ];
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) r[i] = *(reinterpret_cast<const raw16*>(v) + i);
+        __builtin_memcpy(&out[0], &r[0], sizeof(C) * SV);
+    } else {
+#pragma unroll
+        for (int k = 0; k < SV; ++k)
+            if (k < n) out[k] = v[k];
+    }
+}
+
+// a strip of the staged tile (compute type; 16-byte aligned)
+template <typename C>
+__device__ __forceinline__ void lds_put(C* p, const C (&w)[SV]) {
+    constexpr int NQ = int(sizeof(C)) * SV / 16;
+    raw16 r[NQ];
+    __builtin_memcpy(&r[0], &w[0], sizeof(C) * SV);
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) *(reinterpret_cast<raw16*>(p) + i) = r[i];
+}
+template <typename C>
+__device__ __forceinline__ void lds_get(C (&w)[SV], const C* p) {
+    constexpr int NQ = int(sizeof(C)) * SV / 16;
+    raw16 r[NQ];
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) r[i] = *(reinterpret_cast<const raw16*>(p) + i);
+    __builtin_memcpy(&w[0], &r[0], sizeof(C) * SV);
+}
+
+// the 4 x 4 block of 4 lanes (lane_transpose; fp64: low and high words separately)
+__device__ __forceinline__ void transpose4(float (&v)[SV], int lane) {
+    vec<float> in;
+#pragma unroll
+    for (int e = 0; e < SV; ++e) in.e[e] = v[e];
+    const vec<float> out = lane_transpose(in, lane);
+#pragma unroll
+    for (int e = 0; e < SV; ++e) v[e] = out.e[e];
+}
+__device__ __forceinline__ void transpose4(double (&v)[SV], int lane) {
+    vec<uint32_t> lo, hi;
+#pragma unroll
+    for (int e = 0; e < SV; ++e) {
+        uint64_t u;
+        __builtin_memcpy(&u, &v[e], 8);
+        lo.e[e] = uint32_t(u);
+        hi.e[e] = uint32_t(u >> 32);
+    }
+    const vec<uint32_t> tl = lane_transpose(lo, lane), th = lane_transpose(hi, lane);
+#pragma unroll
+    for (int e = 0; e < SV; ++e) {
+        const uint64_t u = uint64_t(tl.e[e]) | uint64_t(th.e[e]) << 32;
+        __builtin_memcpy(&v[e], &u, 8);
+    }
+}
+
+template <typename C>
+struct sshape {
+    static constexpr int P = SBF + 16 / int(sizeof(C));  // LDS row pitch (16 bytes of pad)
+    static constexpr size_t lds_bytes = size_t(SBS) * P * sizeof(C);
+};
+
+// One sub-tile.  FULL: a whole 64 x 64 sub-tile with both VEC flags, every guard folds away.
+template <typename Es, typename Ed, bool FULL>
+__device__ __forceinline__ void run_scaled(const costa_scaled_op_t& sop, int f0, int s0, int tf_, int ts_,
+                                           const char* src_base, char* dst_base, typename Ed::ct alpha,
+                                           typename Ed::ct beta, const typename Ed::ct* rs,
+                                           const typename Ed::ct* cs, typename Ed::ct* tile) {
+    using C = typename Ed::ct;
+    using Ss = typename Es::st;
+    using Sd = typename Ed::st;
+    static_assert(std::is_same<typename Es::ct, C>::value, "one compute type");
+    constexpr int P = sshape<C>::P;
+    const costa_tile_op_t& op = sop.op;
+    const int tf = FULL ? SBF : tf_;
+    const int ts = FULL ? SBS : ts_;
+    const uint32_t flags = op.flags;
+    const uint32_t kind = (flags & COSTA_SCALE_MASK) >> COSTA_SCALE_SHIFT;
+    const bool vs = FULL || (flags & COSTA_TILE_VEC_SRC);
+    const bool vd = FULL || (flags & COSTA_TILE_VEC_DST);
+    const int64_t lds = op.lds, ldd = op.ldd;
+    // the vectors indexed along f and along s, at the sub-tile's origin (wave-uniform)
+    const bool frow = flags & COSTA_SCALED_F_ROWS;
+    const C* vf = frow ? rs : cs;
+    const C* vsl = frow ? cs : rs;
+    if (vf) vf += int64_t(frow ? sop.row0 : sop.col0) + f0;
+    if (vsl) vsl += int64_t(frow ? sop.col0 : sop.row0) + s0;
+    // s_ij(x) = (x * r[i]) * c[j]: two rounded products, r first; a NULL vector is skipped
+    auto sx = [&](C x, C fv, C sv) {
+        if (frow) {
+            if (vf) x = x * fv;
+            if (vsl) x = x * sv;
+        } else {
+            if (vsl) x = x * sv;
+            if (vf) x = x * fv;
+        }
+        return x;
+    };
+    const Ss* src = reinterpret_cast<const Ss*>(src_base + op.src) + int64_t(s0) * lds + f0;
+
+    // ---- load phase: lane -> (strip along f, column s); all loads issued first
+    const int lf = (int(threadIdx.x) % SLPC) * SV;
+    const int c0 = int(threadIdx.x) / SLPC;
+    const int nf_lane = FULL ? SV : tf - lf;  // elements of this lane's strip inside the sub-tile
+    strip<Ss> x[SPL];
+#pragma unroll
+    for (int k = 0; k < SPL; ++k) {
+        const int s = c0 + k * SCPP;
+        x[k] = strip<Ss>{};
+        if (FULL || (nf_lane > 0 && s < ts)) x[k] = load_strip(src + s * lds + lf, nf_lane, vs);
+    }
+
+    if (!(flags & COSTA_TILE_TRANSPOSE)) {
+        // ---- copy mode: dst(f, s), no LDS
+        Sd* dst = reinterpret_cast<Sd*>(dst_base + op.dst) + int64_t(s0) * ldd + f0;
+        strip<Sd> y[SPL];  // beta != 0: every old value is requested before the first store
+#pragma unroll
+        for (int k = 0; k < SPL; ++k) {
+            const int s = c0 + k * SCPP;
+            y[k] = strip<Sd>{};
+            if (kind == COSTA_SCALE_AXPBY && (FULL || (nf_lane > 0 && s < ts)))
+                y[k] = load_strip(dst + s * ldd + lf, nf_lane, vd);
+        }
+        // the scale along f: one strip, the same for every pass; along s: one value per pass
+        C fv[SV], sv[SPL];
+#pragma unroll
+        for (int e = 0; e < SV; ++e) fv[e] = C(0);
+        if (vf && (FULL || nf_lane > 0)) load_scale4(fv, vf + lf, nf_lane);
+#pragma unroll
+        for (int k = 0; k < SPL; ++k) {
+            const int s = c0 + k * SCPP;
+            sv[k] = C(0);
+            if (vsl && (FULL || s < ts)) sv[k] = vsl[s];
+        }
+#pragma unroll
+        for (int k = 0; k < SPL; ++k) {
+            const int s = c0 + k * SCPP;
+            if (!FULL && (nf_lane <= 0 || s >= ts)) continue;
+            strip<Sd> o;
+#pragma unroll
+            for (int e = 0; e < SV; ++e)
+                o.e[e] = Ed::narrow(scale<C>(sx(Es::widen(x[k].e[e]), fv[e], sv[k]), Ed::widen(y[k].e[e]),
+                                             kind, false, alpha, beta));
+            store_strip(dst + s * ldd + lf, o, nf_lane, vd);
+        }
+        return;
+    }
+
+    // ---- transpose mode: dst(s, f) through LDS, staged in the compute type
+    Sd* dst = reinterpret_cast<Sd*>(dst_base + op.dst) + int64_t(f0) * ldd + s0;
+    const int lane = int(threadIdx.x) % 64, wave = int(threadIdx.x) / 64;
+    // store unit k of this lane: 64 s values of one f slot; after the lane exchange lane
+    // (base + j) stores f = q*4 + j for s = sc*64 + base .. + 3
+    const int j = lane & (SV - 1);
+    auto unit = [&](int k, int& f, int& sb, int& n_s) {
+        const int u = wave + SNW * k;
+        const int sc = SBS == SSW ? 0 : u / SQG, q = SBS == SSW ? u : u % SQG;
+        f = q * SV + j;
+        sb = sc * SSW + (lane - j);
+        n_s = FULL ? SV : ts - sb;
+        return FULL || (f < tf && n_s > 0);
+    };
+    // beta != 0: the old destination values are requested now, with the source loads in flight
+    strip<Sd> old[SPS];
+#pragma unroll
+    for (int k = 0; k < SPS; ++k) {
+        int f, sb, n_s;
+        old[k] = strip<Sd>{};
+        if (kind == COSTA_SCALE_AXPBY && unit(k, f, sb, n_s)) old[k] = load_strip(dst + f * ldd + sb, n_s, vd);
+    }
+    // the scale along s (the destination's fast index): one strip per s chunk (a 64 x 64 sub-tile
+    // has one: the same strip for every pass); along f: one value per pass
+    constexpr int NSC = SBS / SSW;
+    C sv[NSC][SV], fv[SPS];
+#pragma unroll
+    for (int sc = 0; sc < NSC; ++sc) {
+        const int sb = sc * SSW + (lane - j);
+#pragma unroll
+        for (int e = 0; e < SV; ++e) sv[sc][e] = C(0);
+        if (vsl && (FULL || ts - sb > 0)) load_scale4(sv[sc], vsl + sb, FULL ? SV : ts - sb);
+    }
+#pragma unroll
+    for (int k = 0; k < SPS; ++k) {
+        int f, sb, n_s;
+        fv[k] = C(0);
+        if (vf && unit(k, f, sb, n_s)) fv[k] = vf[f];
+    }
+#pragma unroll
+    for (int k = 0; k < SPL; ++k) {
+        const int s = c0 + k * SCPP;
+        if (FULL || (nf_lane > 0 && s < ts)) {  // partial strips: the tail is w(0), never stored
+            C w[SV];
+#pragma unroll
+            for (int e = 0; e < SV; ++e) w[e] = Es::widen(x[k].e[e]);
+            lds_put(tile + s * P + lf, w);
+        }
+    }
+    __syncthreads();
+
+    C y[SPS][SV];
+#pragma unroll
+    for (int k = 0; k < SPS; ++k) {
+        const int u = wave + SNW * k;
+        const int sc = SBS == SSW ? 0 : u / SQG, q = SBS == SSW ? u : u % SQG;
+        const int s = sc * SSW + lane;
+#pragma unroll
+        for (int e = 0; e < SV; ++e) y[k][e] = C(0);
+        if (FULL || (s < ts && q * SV < tf)) lds_get(y[k], tile + s * P + q * SV);
+    }
+#pragma unroll
+    for (int k = 0; k < SPS; ++k) {
+        transpose4(y[k], lane);  // (every lane takes part in the exchange)
+        int f, sb, n_s;
+        if (!unit(k, f, sb, n_s)) continue;
+        // (SNW * k / SQG: compile-time; the units of one pass lie in one s chunk)
+        constexpr int per_chunk = SQG / SNW;
+        const C(&svk)[SV] = sv[SBS == SSW ? 0 : k / per_chunk];
+        strip<Sd> o;
+#pragma unroll
+        for (int e = 0; e < SV; ++e)
+            o.e[e] = Ed::narrow(scale<C>(sx(y[k][e], fv[k], svk[e]), Ed::widen(old[k].e[e]), kind, false,
+                                         alpha, beta));
+        store_strip(dst + f * ldd + sb, o, n_s, vd);
+    }
+}
+
+template <typename Es, typename Ed>
+__global__ __launch_bounds__(SNT) void scaled_kernel(const costa_scaled_op_t* __restrict__ ops,
+                                                     const uint64_t* __restrict__ work,
+                                                     const char* src_base, char* dst_base,
+                                                     const typename Ed::ct* __restrict__ scalars,
+                                                     const typename Ed::ct* __restrict__ rs,
+                                                     const typename Ed::ct* __restrict__ cs) {
+    using C = typename Ed::ct;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    C* tile = reinterpret_cast<C*>(smem);
+    // which sub-tile of which op (wave-uniform: scalar loads)
+    const uint64_t w = work[blockIdx.x];
+    const costa_scaled_op_t sop = ops[w >> 32];
+    const costa_tile_op_t& op = sop.op;
+    const uint32_t sub = uint32_t(w);
+    const int nbf = (op.nf + SBF - 1) / SBF;
+    const int f0 = int(sub % uint32_t(nbf)) * SBF;
+    const int s0 = int(sub / uint32_t(nbf)) * SBS;
+    const int tf = min(SBF, op.nf - f0);
+    const int ts = min(SBS, op.ns - s0);
+    const uint32_t slot = op.flags >> COSTA_SLOT_SHIFT;
+    const C alpha = scalars[2 * slot];
+    const C beta = scalars[2 * slot + 1];
+    const uint32_t vec_both = COSTA_TILE_VEC_SRC | COSTA_TILE_VEC_DST;
+    if (tf == SBF && ts == SBS && (op.flags & vec_both) == vec_both)
+        run_scaled<Es, Ed, true>(sop, f0, s0, tf, ts, src_base, dst_base, alpha, beta, rs, cs, tile);
+    else
+        run_scaled<Es, Ed, false>(sop, f0, s0, tf, ts, src_base, dst_base, alpha, beta, rs, cs, tile);
+}
+
+template <typename Es, typename Ed>
+void launch_pair(const costa_scaled_op_t* d_ops, const uint64_t* d_work, const scaled_list& l,
+                 const char* src_base, char* dst_base, const void* d_scalars, const void* rs,
+                 const void* cs, hipStream_t stream) {
+    using C = typename Ed::ct;
+    const int64_t max_grid = 1LL << 30;
+    // copy-only lists need no LDS tile: more workgroups per CU
+    const size_t lds = l.any_transpose ? sshape<C>::lds_bytes : 0;
+    if (sshape<C>::lds_bytes > 64 * 1024) {  // (tuning builds: over the default dynamic-LDS limit)
+        static const bool once = [] {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&scaled_kernel<Es, Ed>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, int(sshape<C>::lds_bytes));
+            return true;
+        }();
+        (void)once;
+    }
+    for (int64_t off = 0; off < l.n_items; off += max_grid) {
+        const int64_t m = std::min(max_grid, l.n_items - off);
+        hipLaunchKernelGGL((scaled_kernel<Es, Ed>), dim3(unsigned(m)), dim3(SNT), lds, stream, d_ops,
+                           d_work + off, src_base, dst_base, static_cast<const C*>(d_scalars),
+                           static_cast<const C*>(rs), static_cast<const C*>(cs));
+    }
+}
+
+// N: f16_t / bf16_t / e4m3_t / e5m2_t; ROUND: a FLOAT source is rounded to N first (the half pairs)
+template <typename N, template <typename> class narrow_e, bool ROUND>
+void launch_narrow(bool src_f, bool dst_f, const costa_scaled_op_t* d_ops,
+                   const uint64_t* d_work, const scaled_list& l, const char* src_base, char* dst_base,
+                   const void* d_scalars, const void* rs, const void* cs, hipStream_t s) {
+    using src_e = typename std::conditional<ROUND, f32_via<N>, f32_e>::type;
+    if (src_f)
+        launch_pair<src_e, narrow_e<N>>(d_ops, d_work, l, src_base, dst_base, d_scalars, rs, cs, s);
+    else if (dst_f)
+        launch_pair<narrow_e<N>, f32_e>(d_ops, d_work, l, src_base, dst_base, d_scalars, rs, cs, s);
+    else
+        launch_pair<narrow_e<N>, narrow_e<N>>(d_ops, d_work, l, src_base, dst_base, d_scalars, rs, cs, s);
+}
+
+// bytes a side must be aligned to for vector accesses: its strip of 4 elements, 16 at most
+uint64_t strip_align(costa_dtype_t t) { return std::min<uint64_t>(16, 4 * dtype_size(t)); }
+
+}  // namespace
+
+void scaled_subtile(costa_dtype_t src, costa_dtype_t dst, int* bf, int* bs) {
+    if (!scaled_pair(src, dst))
+        throw error(COSTA_ERR_ARG, std::string("costa: no scaled kernel for ") + dtype_name(src) + " -> " +
+                                       dtype_name(dst));
+    *bf = SBF;
+    *bs = SBS;
+}
+
+scaled_list build_scaled_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
+                              const std::vector<costa_scaled_op_t>& ops, uint64_t src_base,
+                              uint64_t dst_base, std::vector<costa_scaled_op_t>& ordered,
+                              std::vector<uint64_t>& work, bool dst_order) {
+    const int64_t bf = SBF, bs = SBS;
+    const uint64_t ES = dtype_size(src_dtype), ED = dtype_size(dst_dtype);
+    const uint64_t AS = strip_align(src_dtype), AD = strip_align(dst_dtype);
+    scaled_list l;
+    ordered.clear();
+    work.clear();
+    ordered.reserve(ops.size());
+    for (const costa_scaled_op_t& in : ops) {
+        if (in.op.nf <= 0 || in.op.ns <= 0) continue;
+        if (in.op.lds < 0 || in.op.ldd < 0) throw error(COSTA_ERR_ARG, "costa: negative leading dimension");
+        if (in.row0 < 0 || in.col0 < 0) throw error(COSTA_ERR_ARG, "costa: negative target coordinate");
+        costa_scaled_op_t t = in;
+        costa_tile_op_t& op = t.op;
+        op.flags &= ~uint32_t(COSTA_TILE_VEC_SRC | COSTA_TILE_VEC_DST);
+        if ((src_base + op.src) % AS == 0 && (uint64_t(op.lds) * ES) % AS == 0) op.flags |= COSTA_TILE_VEC_SRC;
+        if ((dst_base + op.dst) % AD == 0 && (uint64_t(op.ldd) * ED) % AD == 0) op.flags |= COSTA_TILE_VEC_DST;
+        const uint64_t idx = ordered.size();
+        const int64_t nbf = (int64_t(op.nf) + bf - 1) / bf, nbs = (int64_t(op.ns) + bs - 1) / bs;
+        if (idx >> 32 || (nbf * nbs) >> 32)
+            throw error(COSTA_ERR_ARG, "costa: scaled list too long for its work items");
+        ordered.push_back(t);
+        if (op.flags & COSTA_TILE_TRANSPOSE) l.any_transpose = true;
+        for (int64_t q = 0; q < nbf * nbs; ++q) work.push_back(idx << 32 | uint64_t(q));
+    }
+    if (dst_order && work.size() > 1) {
+        // sub-tiles by the address of their first destination element (stable), as the ordinary
+        // LOCAL list of a triangular plan (engine.cpp build_work dst_order)
+        std::vector<std::pair<uint64_t, uint64_t>> key(work.size());
+        for (size_t x = 0; x < key.size(); ++x) {
+            const costa_tile_op_t& op = ordered[size_t(work[x] >> 32)].op;
+            const uint64_t q = work[x] & 0xFFFFFFFFull, nbf = uint64_t((op.nf + bf - 1) / bf);
+            const int64_t f0 = int64_t(q % nbf) * bf, s0 = int64_t(q / nbf) * bs;
+            const int64_t at = op.flags & COSTA_TILE_TRANSPOSE ? f0 * op.ldd + s0 : s0 * op.ldd + f0;
+            key[x] = {op.dst + uint64_t(at) * ED, work[x]};
+        }
+        std::stable_sort(key.begin(), key.end(),
+                         [](const auto& a, const auto& b) { return a.first < b.first; });
+        for (size_t x = 0; x < key.size(); ++x) work[x] = key[x].second;
+    }
+    l.n_items = int64_t(work.size());
+    return l;
+}
+
+void launch_scaled(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* d_ops,
+                   const uint64_t* d_work, const scaled_list& l, const char* src_base, char* dst_base,
+                   const void* d_scalars, const void* rs, const void* cs, void* stream) {
+    if (l.n_items <= 0) return;
+    if (!scaled_pair(src_dtype, dst_dtype))
+        throw error(COSTA_ERR_ARG, std::string("costa: no scaled kernel for ") + dtype_name(src_dtype) +
+                                       " -> " + dtype_name(dst_dtype));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool src_f = src_dtype == COSTA_FLOAT, dst_f = dst_dtype == COSTA_FLOAT;
+    const costa_dtype_t nt = src_f ? dst_dtype : src_dtype;  // the narrow type of a half / FP8 pair
+    if (src_dtype == COSTA_DOUBLE)
+        launch_pair<f64_e, f64_e>(d_ops, d_work, l, src_base, dst_base, d_scalars, rs, cs, s);
+    else if (src_f && dst_f)
+        launch_pair<f32_e, f32_e>(d_ops, d_work, l, src_base, dst_base, d_scalars, rs, cs, s);
+    else if (nt == COSTA_HALF)
+        launch_narrow<f16_t, h_e, true>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, rs, cs, s);
+    else if (nt == COSTA_BFLOAT16)
+        launch_narrow<bf16_t, h_e, true>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, rs, cs, s);
+    else if (nt == COSTA_FP8_E4M3)
+        launch_narrow<e4m3_t, q_e, false>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, rs, cs, s);
+    else
+        launch_narrow<e5m2_t, q_e, false>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, rs, cs, s);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        throw error(COSTA_ERR_HIP, std::string("scaled kernel launch failed: ") + hipGetErrorString(e));
+}
+
+}  // namespace engine
+}  // namespace costa

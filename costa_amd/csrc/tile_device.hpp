@@ -1,6 +1,8 @@
 // Device helpers shared by the tile kernels (tile_kernels.hip) and the converting kernels
 // (convert_kernels.hip): element arithmetic in the reference's rounding order, 16-byte vector
-// accesses, the cross-lane V x V transpose.  Everything is internal to the including file.
+// accesses, the cross-lane V x V transpose, and the 2-byte / 1-byte element types' widening and
+// rounding (half_kernels.hip, fp8_kernels.hip, scaled_kernels.hip).  Everything is internal to the
+// including file.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -288,6 +290,102 @@ __device__ __forceinline__ vec<T> lane_transpose(const vec<T>& in, int lane) {
     }
     return out;
 }
+
+// ---- narrow element types: shared by half_kernels.hip, fp8_kernels.hip and scaled_kernels.hip ----
+// the two 2-byte types: raw bits, exact widening, rounding to nearest even
+struct f16_t {
+    static __device__ __forceinline__ float widen(uint16_t b) {
+        _Float16 h;
+        __builtin_memcpy(&h, &b, 2);
+        return static_cast<float>(h);
+    }
+    static __device__ __forceinline__ uint16_t narrow(float x) {
+        const _Float16 h = static_cast<_Float16>(x);  // RNE, +-inf on overflow, subnormals kept
+        uint16_t b;
+        __builtin_memcpy(&b, &h, 2);
+        return b;
+    }
+};
+struct bf16_t {
+    static __device__ __forceinline__ float widen(uint16_t b) {
+        const uint32_t u = uint32_t(b) << 16;
+        float x;
+        __builtin_memcpy(&x, &u, 4);
+        return x;
+    }
+    static __device__ __forceinline__ uint16_t narrow(float x) {
+#ifdef COSTA_HALF_BF16_INT  // (tuning builds: the integer form of the same rounding)
+        uint32_t u;
+        __builtin_memcpy(&u, &x, 4);
+        if ((u & 0x7FFFFFFFu) > 0x7F800000u) return uint16_t((u >> 16) | 0x40u);  // NaN stays NaN
+        // round to nearest even on the 16 dropped bits; a carry out of the mantissa moves to the
+        // exponent (the finite maximum goes to inf), subnormals round like everything else
+        return uint16_t((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+#else
+        const __bf16 h = static_cast<__bf16>(x);  // v_cvt_pk_bf16_f32: RNE, +-inf on overflow, subnormals kept
+        uint16_t b;
+        __builtin_memcpy(&b, &h, 2);
+        return b;
+#endif
+    }
+};
+
+__device__ __forceinline__ uint32_t f2u(float x) {
+    uint32_t u;
+    __builtin_memcpy(&u, &x, 4);
+    return u;
+}
+__device__ __forceinline__ float u2f(uint32_t u) {
+    float x;
+    __builtin_memcpy(&x, &u, 4);
+    return x;
+}
+
+// The two 1-byte types: raw bits, exact widening, conversion as torch-CPU's .to(float8_*).
+// narrow() rounds to nearest even on the dropped mantissa bits in integers (a carry out of the
+// mantissa moves to the exponent); below the smallest normal the value is brought to the
+// subnormals' fixed point by one exact fp32 addition (the sum's ulp is the subnormal step, so the
+// addition itself rounds to nearest even, the tie below the smallest subnormal to zero).
+template <int MB, int BIAS>
+__device__ __forceinline__ uint32_t round_finite(uint32_t a) {  // |x| as fp32 bits, below the type's overflow
+    constexpr int DROP = 23 - MB;
+    constexpr uint32_t MIN_NORMAL = uint32_t(127 - BIAS + 1) << 23;
+    constexpr uint32_t MAGIC = uint32_t(127 + DROP - BIAS + 1) << 23;  // 2^(subnormal step + 23)
+    if (a < MIN_NORMAL) return f2u(u2f(a) + u2f(MAGIC)) - MAGIC;
+    a += (uint32_t(BIAS - 127) << 23) + ((1u << (DROP - 1)) - 1u) + ((a >> DROP) & 1u);
+    return a >> DROP;
+}
+struct e4m3_t {  // OCP e4m3fn: bias 7, no infinities, NaN = 0x7F / 0xFF, largest finite 448
+    static __device__ __forceinline__ float widen(uint32_t b) {
+        // the 7 magnitude bits read as binary16 (4-bit exponent in the low exponent bits) are the
+        // value / 2^8, subnormals included
+        const uint16_t hb = uint16_t((b & 0x7Fu) << 7);
+        _Float16 h;
+        __builtin_memcpy(&h, &hb, 2);
+        const uint32_t m = (b & 0x7Fu) == 0x7Fu ? 0x7FC00000u : f2u(static_cast<float>(h) * 256.0f);
+        return u2f(m | ((b & 0x80u) << 24));
+    }
+    static __device__ __forceinline__ uint32_t narrow(float x) {
+        const uint32_t u = f2u(x), a = u & 0x7FFFFFFFu, sign = (u >> 24) & 0x80u;
+        // 480 = 1.875 * 2^8 and above (inf, NaN) -> NaN; (464, 480) rounds to the NaN code by itself
+        if (a >= 0x43F00000u) return sign | 0x7Fu;
+        return sign | round_finite<3, 7>(a);
+    }
+};
+struct e5m2_t {  // OCP e5m2: bias 15, the high byte of IEEE binary16
+    static __device__ __forceinline__ float widen(uint32_t b) {
+        const uint16_t hb = uint16_t((b & 0xFFu) << 8);
+        _Float16 h;
+        __builtin_memcpy(&h, &hb, 2);
+        return static_cast<float>(h);
+    }
+    static __device__ __forceinline__ uint32_t narrow(float x) {
+        const uint32_t u = f2u(x), a = u & 0x7FFFFFFFu, sign = (u >> 24) & 0x80u;
+        // NaN; 61440 = 1.875 * 2^15 and above -> +-inf ((57344, 61440) rounds by itself, the tie to inf)
+        if (a >= 0x47700000u) return sign | (a > 0x7F800000u ? 0x7Fu : 0x7Cu);
+        return sign | round_finite<2, 15>(a);
+    }
+};
 
 }  // namespace
 }  // namespace engine

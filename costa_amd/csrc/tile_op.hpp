@@ -93,6 +93,19 @@ COSTA_HD inline costa_tri_op_t tri_op(const costa_tile_op_t& op, bool src_cm, bo
     return t;
 }
 
+// The op of a scaled transform.  `op` is the tile's ordinary op; its source element (0, 0) sits at
+// target (C) position (r0, c0) counted from the first row and column of C's matrix.  As in tri_op(),
+// the source's fast index f walks target rows when src_cm != transpose (COSTA_SCALED_F_ROWS).
+COSTA_HD inline costa_scaled_op_t scaled_op(const costa_tile_op_t& op, bool src_cm, bool transpose, int r0,
+                                            int c0) {
+    costa_scaled_op_t t{};
+    t.op = op;
+    t.row0 = r0;
+    t.col0 = c0;
+    if (src_cm != transpose) t.op.flags |= COSTA_SCALED_F_ROWS;
+    return t;
+}
+
 // kept elements of an edge op
 COSTA_HD inline int64_t tri_kept(const costa_tri_op_t& t) {
     const bool le = t.op.flags & COSTA_TRI_LE;

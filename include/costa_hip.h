@@ -127,6 +127,20 @@ typedef struct {
     int32_t pad; /* 0 */
 } costa_tri_op_t; /* 48 bytes */
 
+/* ---- tile op of a scaled transform ("scaled transforms" below): a tile op whose source value x
+ * is replaced by (x * r[i]) * c[j], (i, j) being the element's target coordinates.  (row0, col0)
+ * are the target coordinates of the op's source element (f, s) = (0, 0), counted from the first
+ * row and column of C's matrix; with COSTA_SCALED_F_ROWS set the op's fast index f walks target
+ * rows and s target columns (i = row0 + f, j = col0 + s), else the other way round (i = row0 + s,
+ * j = col0 + f) -- the planner sets it when the source's ordering is column-major != the job
+ * transposes.  COSTA_SCALE_BITCOPY of a scaled op means cvt(s_ij(x)), never a byte copy. */
+#define COSTA_SCALED_F_ROWS 0x80u /* flag bit 7 of op.flags */
+typedef struct {
+    costa_tile_op_t op;
+    int32_t row0;
+    int32_t col0;
+} costa_scaled_op_t; /* 48 bytes */
+
 /* ---- library ---- */
 const char* costa_hip_last_error(void);
 int costa_hip_version(void); /* major*10000 + minor*100 + patch */
@@ -158,6 +172,8 @@ void costa_hip_layout_destroy(costa_layout_t layout);
 int costa_hip_layout_reorder_ranks(costa_layout_t layout, const int* reordering, int n);
 /* number of local blocks / the i-th block (global intervals, data pointer, ld) */
 int costa_hip_layout_num_blocks(costa_layout_t layout);
+/* rows (*m) and columns (*n) of the matrix the layout describes (the extent of its splits) */
+int costa_hip_layout_shape(costa_layout_t layout, int* m, int* n);
 int costa_hip_layout_block(costa_layout_t layout, int i, int* row_start, int* row_end,
                            int* col_start, int* col_end, void** data, int* ld);
 
@@ -277,6 +293,47 @@ int costa_hip_transform_tri_async(costa_layout_t A, costa_layout_t C, char trans
                                   const void* alpha, const void* beta, costa_comm_t comm,
                                   void* stream);
 
+/* ---- scaled transforms (MI355X-native): row / column scale vectors fused into the tile kernels ----
+ * With m x n the matrix C's layout describes and i, j counted from its first row and column (the
+ * origin costa_hip_transform_tri documents):
+ *   C(i, j) = beta*C(i, j) + alpha * s_ij(op(A)(i, j)),      s_ij(x) = (x * r[i]) * c[j]
+ * `row_scale` (r, m elements) and `col_scale` (c, n elements) are DEVICE arrays of the compute type
+ * (float; double for the COSTA_DOUBLE pair), replicated on every rank.  Either may be NULL: its
+ * multiplication is then skipped (not replaced by a multiplication by 1).  Both NULL is
+ * COSTA_ERR_ARG ("use costa_hip_transform"); a host pointer for a vector is COSTA_ERR_ARG with
+ * "device-resident" in the message.  The vectors are read during the call; for the _async form
+ * they must stay valid until the stream has passed the call.  Their addresses and values are not
+ * part of the plan: one cached plan serves every vector, present or absent.
+ *
+ * Bit-level definition: the ordinary transform of the same (A, C) pair whose arithmetic reads
+ * s_ij(x) wherever it would read x.  x is the source value as the pair delivers it to its
+ * arithmetic: w(A) for 2-byte (H) and 1-byte (Q) sources, w(cvt_H(A)) for COSTA_FLOAT -> H (the
+ * package keeps holding H), the unrounded A for COSTA_FLOAT -> Q and COSTA_FLOAT -> COSTA_FLOAT.
+ * The two products are two separately rounded multiplications in the compute type, r first, no
+ * fma; then the unchanged scale branches (ZERO, ALPHA, AXPBY) and one cvt() at the store.  Scale
+ * kind BITCOPY (copy mode, alpha = 1, beta = 0) means cvt(s_ij(x)) here, never a byte copy.  'C'
+ * is 'T' (real types only).  Bytes of C that no tile writes keep their bits.
+ *
+ * Accepted (A, C) pairs -- every pair costa_hip_transform accepts whose compute type is real
+ * COSTA_FLOAT, plus COSTA_DOUBLE -> COSTA_DOUBLE: COSTA_FLOAT -> COSTA_FLOAT, the six half pairs
+ * (H -> H, COSTA_FLOAT -> H, H -> COSTA_FLOAT), the six FP8 pairs, COSTA_DOUBLE -> COSTA_DOUBLE.
+ * Everything else (complex, COSTA_INT32, COSTA_FLOAT <-> COSTA_DOUBLE, and the pairs
+ * costa_hip_transform refuses) is COSTA_ERR_ARG with a message naming both types.
+ * Device-resident layouts only (COSTA_ERR_ARG with "device-resident" otherwise); blocking and
+ * _async; any communicator size (the exchange is the ordinary plan's: only LOCAL and UNPACK ops
+ * scale).  No batches, no triangular mask, no host staging.
+ *
+ * In place: A and C may be the SAME layout over the same device buffer when trans is 'N':
+ * A <- diag(r) * A * diag(c) (p?laqge).  Every op is then a LOCAL copy-mode op whose source and
+ * destination coincide, and every lane of the kernel stores exactly the elements it loaded (the
+ * kernel's data pointers carry no __restrict__).  Device-resident layouts, one rank. */
+int costa_hip_transform_scaled(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                               const void* beta, const void* row_scale, const void* col_scale,
+                               costa_comm_t comm);
+int costa_hip_transform_scaled_async(costa_layout_t A, costa_layout_t C, char trans,
+                                     const void* alpha, const void* beta, const void* row_scale,
+                                     const void* col_scale, costa_comm_t comm, void* stream);
+
 /* ---- stream-ordered variants (MI355X-native; no reference counterpart) ----
  * Enqueue the transform and return.  Layouts must be device-resident.  `stream` (a hipStream_t,
  * may be NULL) is joined at entry and made to wait for the result, so work queued on it after
@@ -330,6 +387,24 @@ int costa_hip_tri_cut(void);
  * (*bs) dimension */
 int costa_hip_tri_subtile(costa_dtype_t dtype, int* bf, int* bs);
 
+/* scaled ops (costa_scaled_op_t) of one accepted pair ("scaled transforms" above) in ONE launch of
+ * scaled_kernel: offsets and leading dimensions of each side count in that side's elements / bytes,
+ * `scalars` = n_slots (alpha, beta) pairs of the compute type (host), `row_scale` / `col_scale`
+ * device arrays of the compute type indexed by the ops' target coordinates (either may be NULL,
+ * not both).  The VEC flags are recomputed from each side's actual address: a side takes vector
+ * accesses when it is aligned to its strip of 4 elements (4 bytes on a 1-byte side, 8 on a 2-byte
+ * side, 16 on fp32 and -- two accesses -- on fp64). */
+int costa_hip_execute_tiles_scaled(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
+                                   const costa_scaled_op_t* ops, int64_t n, const void* src_base,
+                                   void* dst_base, const void* scalars, int n_slots,
+                                   const void* row_scale, const void* col_scale, int device);
+/* the sub-tile one workgroup of scaled_kernel runs for an accepted pair: elements along the
+ * source's fast (*bf) and slow (*bs) dimension */
+int costa_hip_scaled_subtile(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, int* bf, int* bs);
+/* sub-tiles run by scaled_kernel since the last reset (scaled transforms and
+ * costa_hip_execute_tiles_scaled); kept beside costa_stats_t, whose layout does not change */
+int costa_hip_scaled_items(int64_t* items, int reset);
+
 /* ---- plan inspection (host only, never touches a GPU) ----
  * Plans the transform for rank `rank` of `nranks` and copies the three descriptor
  * lists out.  Offsets of pack destinations / unpack sources are byte offsets into the
@@ -375,6 +450,23 @@ int costa_hip_plan_export_tri(costa_layout_t A, costa_layout_t C, char trans, ch
                               costa_tri_op_t* local_tri, costa_tri_op_t* unpack_tri,
                               int64_t* send_counts, int64_t* send_displs, int64_t* recv_counts,
                               int64_t* recv_displs, void* scalars);
+
+/* The plan of a scaled transform (costa_hip_transform_scaled): tile set, order, pack list, package
+ * type, counts, displacements and scalars are the ordinary plan's (costa_hip_plan_export), byte for
+ * byte; every LOCAL and UNPACK op is in local_scaled / unpack_scaled with its target coordinates
+ * (the ordinary op plus COSTA_SCALED_F_ROWS where it applies), and the ordinary local / unpack
+ * lists are empty (base.n_local = base.n_unpack = 0).  `scalars` are of the compute type. */
+typedef struct {
+    costa_plan_info_t base;
+    int64_t n_local_scaled;
+    int64_t n_unpack_scaled;
+} costa_scaled_plan_info_t;
+int costa_hip_plan_export_scaled(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                                 const void* beta, int rank, int nranks,
+                                 costa_scaled_plan_info_t* info, costa_tile_op_t* pack_ops,
+                                 costa_scaled_op_t* local_scaled, costa_scaled_op_t* unpack_scaled,
+                                 int64_t* send_counts, int64_t* send_displs, int64_t* recv_counts,
+                                 int64_t* recv_displs, void* scalars);
 
 /* ---- measurement ----
  * With profiling on, every kernel launch and exchange is bracketed by HIP events on
