@@ -36,6 +36,7 @@ __all__ = [
     "plan_export", "set_profiling", "get_stats", "release_caches", "TILE_OP_DTYPE",
     "ScaledOp", "SCALED_OP_DTYPE", "SCALED_F_ROWS", "transform_scaled", "execute_tiles_scaled",
     "plan_export_scaled", "scaled_subtile", "scaled_items",
+    "transform_amax", "layout_amax", "execute_tiles_amax", "amax_items",
 ]
 
 FLOAT, DOUBLE, CFLOAT, CDOUBLE, INT32 = 0, 1, 2, 3, 4
@@ -260,6 +261,13 @@ def lib():
         "costa_hip_execute_tiles_scaled": (i, [i, i, C.POINTER(ScaledOp), i64, vp, vp, vp, i, vp, vp, i]),
         "costa_hip_scaled_subtile": (i, [i, i, C.POINTER(i), C.POINTER(i)]),
         "costa_hip_scaled_items": (i, [C.POINTER(i64), i]),
+        "costa_hip_transform_amax": (i, [vp, vp, c, vp, vp, vp, vp, vp, vp, vp]),
+        "costa_hip_transform_amax_async": (i, [vp, vp, c, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "costa_hip_layout_amax": (i, [vp, vp, vp, vp]),
+        "costa_hip_layout_amax_async": (i, [vp, vp, vp, vp, vp]),
+        "costa_hip_execute_tiles_amax": (i, [i, i, C.POINTER(ScaledOp), i64, vp, vp, vp, i, vp, vp, vp, vp,
+                                             i]),
+        "costa_hip_amax_items": (i, [C.POINTER(i64), i]),
         "costa_hip_plan_export_scaled": (i, [vp, vp, c, vp, vp, i, i, C.POINTER(ScaledPlanInfo), vp, vp,
                                              vp, vp, vp, vp, vp, vp]),
         "costa_hip_plan_export": (i, [i, C.POINTER(vp), C.POINTER(vp), C.c_char_p, vp, vp, i, i,
@@ -276,7 +284,14 @@ def lib():
         "costa_hip_work_export": (i, [i, vp, i64, i, i, vp, i64, vp, i64, C.POINTER(i64)]),
     }
     for name, (res, args) in sig.items():
-        f = getattr(L, name)
+        try:
+            f = getattr(L, name)
+        except AttributeError:
+            # an older build selected with COSTA_LIB for an A/B run lacks the newer entry points:
+            # calling one raises AttributeError; the package's own library must have them all
+            if os.environ.get("COSTA_LIB"):
+                continue
+            raise
         f.restype = res
         f.argtypes = args
     _lib = L
@@ -814,6 +829,81 @@ def scaled_items(reset: bool = False) -> int:
     """Sub-tiles run by the scaled kernel since the last reset."""
     v = C.c_int64(0)
     _check(lib().costa_hip_scaled_items(C.byref(v), int(reset)))
+    return v.value
+
+
+# ------------------------------------------------------------------ amax outputs
+def transform_amax(A: Layout, Cl: Layout, comm: Comm, trans: str = "N", alpha=1, beta=0,
+                   row_scale=None, col_scale=None, row_amax=None, col_amax=None, stream=None):
+    """``transform_scaled`` with the same arguments (here both scales may be None: both products are
+    skipped) that also updates ``row_amax[i]`` / ``col_amax[j]`` (m / n elements of the compute
+    type, at least one given) with the abs-max, taken as an unsigned maximum of bit patterns, over the
+    elements (i, j) of C this rank writes; x is the source value before the scales and alpha / beta
+    (costa_hip_transform_amax; costa_hip.h, "amax outputs").  The update accumulates: initialise the
+    vectors, normally with zeros; entries must be non-negative on entry.  Amax vectors are torch
+    CUDA tensors, checked like the scale tensors (ValueError), or raw device addresses (unchecked).
+    With several ranks each rank's vectors cover its own part of C: max-reduce them across ranks."""
+    if not isinstance(A, Layout) or not isinstance(Cl, Layout):
+        raise CostaError(1, "costa: batches of scaled layout pairs are not supported")
+    code = _scalar_code(A.dtype, Cl.dtype)
+    m, n = Cl.shape()
+    rp = _scale_arg(row_scale, code, m, "row_scale")
+    cp = _scale_arg(col_scale, code, n, "col_scale")
+    ra = _scale_arg(row_amax, code, m, "row_amax")
+    ca = _scale_arg(col_amax, code, n, "col_amax")
+    ab, bb = _scalar_bytes(code, alpha), _scalar_bytes(code, beta)
+    args = (A.handle, Cl.handle, _chr(trans), ab, bb, C.c_void_p(rp), C.c_void_p(cp), C.c_void_p(ra),
+            C.c_void_p(ca), comm.handle)
+    if stream is None:
+        _check(lib().costa_hip_transform_amax(*args))
+    else:
+        s = getattr(stream, "cuda_stream", stream) or 0
+        _check(lib().costa_hip_transform_amax_async(*args, C.c_void_p(s)))
+
+
+def layout_amax(A: Layout, comm: Comm, row_amax=None, col_amax=None, stream=None):
+    """Update ``row_amax`` / ``col_amax`` (rows / columns of the matrix A's layout describes; float32,
+    float64 for DOUBLE layouts; at least one given) with the abs-max of A's local blocks, whatever
+    their padding and ordering: a reduce-only pass that writes nothing else (costa_hip_layout_amax).
+    FLOAT, DOUBLE, HALF, BFLOAT16 and FP8 layouts on the device.  The vectors accumulate and are
+    checked as in ``transform_amax``; with ``stream`` the call is stream-ordered."""
+    if not isinstance(A, Layout):
+        raise CostaError(1, "costa: layout_amax takes one layout")
+    code = DOUBLE if A.dtype == DOUBLE else FLOAT
+    m, n = A.shape()
+    ra = _scale_arg(row_amax, code, m, "row_amax")
+    ca = _scale_arg(col_amax, code, n, "col_amax")
+    if stream is None:
+        _check(lib().costa_hip_layout_amax(A.handle, C.c_void_p(ra), C.c_void_p(ca), comm.handle))
+    else:
+        s = getattr(stream, "cuda_stream", stream) or 0
+        _check(lib().costa_hip_layout_amax_async(A.handle, C.c_void_p(ra), C.c_void_p(ca), comm.handle,
+                                                 C.c_void_p(s)))
+
+
+def execute_tiles_amax(src_dtype, dst_dtype, ops: np.ndarray, scalars: np.ndarray, src_base=0,
+                       dst_base=0, row_scale=None, col_scale=None, row_amax=None, col_amax=None,
+                       device: int = 0):
+    """``execute_tiles_scaled`` plus the amax outputs: device arrays of the compute type indexed by the
+    ops' target coordinates (at least one); the scales may both be None
+    (costa_hip_execute_tiles_amax)."""
+    sc_, dc_ = element_code(src_dtype), element_code(dst_dtype)
+    ops = np.ascontiguousarray(ops, dtype=SCALED_OP_DTYPE)
+    sc = np.ascontiguousarray(scalars, dtype=_NP[_scalar_code(sc_, dc_)]).reshape(-1)
+    assert sc.size % 2 == 0
+    _check(lib().costa_hip_execute_tiles_amax(sc_, dc_, ops.ctypes.data_as(C.POINTER(ScaledOp)),
+                                              ops.size, C.c_void_p(_ptr(src_base)),
+                                              C.c_void_p(_ptr(dst_base)), sc.ctypes.data, sc.size // 2,
+                                              C.c_void_p(_ptr(row_scale)), C.c_void_p(_ptr(col_scale)),
+                                              C.c_void_p(_ptr(row_amax)), C.c_void_p(_ptr(col_amax)),
+                                              device))
+
+
+def amax_items(reset: bool = False) -> int:
+    """Sub-tiles run by the amax instantiations of the scaled kernel and by the reduce-only kernel of
+    ``layout_amax`` since the last reset."""
+    v = C.c_int64(0)
+    _check(lib().costa_hip_amax_items(C.byref(v), int(reset)))
     return v.value
 
 

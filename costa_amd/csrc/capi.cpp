@@ -507,6 +507,83 @@ int costa_hip_scaled_items(int64_t* items, int reset) {
     });
 }
 
+namespace {
+// the one job of costa_hip_transform_amax: a scaled job (the scaled plan, unchanged) with outputs
+std::vector<job> make_amax_job(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                               const void* beta, const void* row_scale, const void* col_scale,
+                               void* row_amax, void* col_amax) {
+    auto jobs = make_scaled_job(A, C, trans, alpha, beta, row_scale, col_scale);
+    jobs[0].row_amax = row_amax;
+    jobs[0].col_amax = col_amax;
+    return jobs;
+}
+void check_amax_vectors(const void* row_amax, const void* col_amax) {
+    if (!row_amax && !col_amax)
+        throw costa::engine::error(COSTA_ERR_ARG, "costa_hip_transform_amax: both amax vectors are NULL (use "
+                                                  "costa_hip_transform_scaled or costa_hip_transform)");
+}
+}  // namespace
+
+int costa_hip_transform_amax(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                             const void* beta, const void* row_scale, const void* col_scale,
+                             void* row_amax, void* col_amax, costa_comm_t comm) {
+    return gpu_guarded([&] {
+        if (!comm || !alpha || !beta) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        auto jobs = make_amax_job(A, C, trans, alpha, beta, row_scale, col_scale, row_amax, col_amax);
+        costa_dtype_t a, c;  // an unsupported pair is reported first
+        costa::engine::check_jobs(jobs, costa::engine::comm_size(comm->c), a, c);
+        check_amax_vectors(row_amax, col_amax);
+        costa::engine::transform(jobs, comm->c);
+    });
+}
+
+int costa_hip_transform_amax_async(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                                   const void* beta, const void* row_scale, const void* col_scale,
+                                   void* row_amax, void* col_amax, costa_comm_t comm, void* stream) {
+    return gpu_guarded([&] {
+        if (!comm || !alpha || !beta) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        auto jobs = make_amax_job(A, C, trans, alpha, beta, row_scale, col_scale, row_amax, col_amax);
+        costa_dtype_t a, c;
+        costa::engine::check_jobs(jobs, costa::engine::comm_size(comm->c), a, c);
+        check_amax_vectors(row_amax, col_amax);
+        costa::engine::transform(jobs, comm->c, stream, true);
+    });
+}
+
+int costa_hip_layout_amax(costa_layout_t A, void* row_amax, void* col_amax, costa_comm_t comm) {
+    return gpu_guarded([&] {
+        if (!A || !comm) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::layout_amax(A->e, row_amax, col_amax, comm->c, nullptr, false);
+    });
+}
+
+int costa_hip_layout_amax_async(costa_layout_t A, void* row_amax, void* col_amax, costa_comm_t comm,
+                                void* stream) {
+    return gpu_guarded([&] {
+        if (!A || !comm) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::layout_amax(A->e, row_amax, col_amax, comm->c, stream, true);
+    });
+}
+
+int costa_hip_execute_tiles_amax(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
+                                 const costa_scaled_op_t* ops, int64_t n, const void* src_base,
+                                 void* dst_base, const void* scalars, int n_slots, const void* row_scale,
+                                 const void* col_scale, void* row_amax, void* col_amax, int device) {
+    return gpu_guarded([&] {
+        if (n < 0 || (n > 0 && (!ops || !scalars)))
+            throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::execute_tiles_amax(src_dtype, dst_dtype, ops, n, src_base, dst_base, scalars,
+                                          n_slots, row_scale, col_scale, row_amax, col_amax, device);
+    });
+}
+
+int costa_hip_amax_items(int64_t* items, int reset) {
+    return guarded([&] {
+        if (!items) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        *items = costa::engine::amax_items(reset != 0);
+    });
+}
+
 int costa_hip_plan_export_scaled(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
                                  const void* beta, int rank, int nranks,
                                  costa_scaled_plan_info_t* info, costa_tile_op_t* pack_ops,

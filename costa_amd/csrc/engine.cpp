@@ -104,6 +104,7 @@ struct device_ctx {
     std::vector<hipEvent_t> free_events;  // timing events ready for reuse
     std::deque<timed> pending;            // recorded phase brackets not yet read
     dbuf send, recv;
+    dbuf amax_ops, amax_work;  // the op and work lists of costa_hip_layout_amax calls
     explicit device_ctx(int dev) : device(dev) {
         HIP_CHECK(hipSetDevice(dev));
         // blocking streams: they order after work on the legacy default stream
@@ -2325,6 +2326,7 @@ namespace {
 enum phase { PH_LOCAL, PH_PACK, PH_EXCHANGE, PH_UNPACK, PH_H2D, PH_D2H, PH_TRI_LOCAL, PH_TRI_UNPACK };
 double g_tri_ms = 0;
 int64_t g_scaled_items = 0;  // sub-tiles run by scaled_kernel (kept beside costa_stats_t)
+int64_t g_amax_items = 0;    // ... by its AMAX instantiations and by amax_kernel (likewise)
 
 struct phase_timer {
     device_ctx& dc;
@@ -2447,12 +2449,20 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
     // the vectors of a scaled transform: arguments of this call, read by its LOCAL / UNPACK kernels
     const void* row_scale = p.scaled ? jobs[0].row_scale : nullptr;
     const void* col_scale = p.scaled ? jobs[0].col_scale : nullptr;
+    // ... and its amax outputs, updated by the same kernels (costa_hip_transform_amax)
+    void* row_amax = p.scaled ? jobs[0].row_amax : nullptr;
+    void* col_amax = p.scaled ? jobs[0].col_amax : nullptr;
+    const bool amax = row_amax || col_amax;
     if (p.scaled) {
-        if (!row_scale && !col_scale)
+        if (!row_scale && !col_scale && !amax)
             throw error(COSTA_ERR_ARG, "costa: a scaled transform without scale vectors (use costa_hip_transform)");
         for (const void* v : {row_scale, col_scale})
             if (v && !is_device_ptr(v))
                 throw error(COSTA_ERR_ARG, "costa: the scale vectors of a scaled transform must be "
+                                           "device-resident");
+        for (const void* v : {row_amax, col_amax})
+            if (v && !is_device_ptr(v))
+                throw error(COSTA_ERR_ARG, "costa: the amax vectors of a scaled transform must be "
                                            "device-resident");
     }
     if (async && (cp.staged || cp.pipe))
@@ -2534,7 +2544,7 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
         tm.start(PH_LOCAL, ls);
         launch_scaled(p.src_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(cp.d_local_sc.p),
                       static_cast<const uint64_t*>(cp.w_local_sc.p), cp.s_local, nullptr, nullptr,
-                      cp.d_scal.p, row_scale, col_scale, ls);
+                      cp.d_scal.p, row_scale, col_scale, row_amax, col_amax, ls);
         tm.stop();
     }
 
@@ -2603,7 +2613,7 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
                 tm.start(PH_UNPACK, dc.aux);
                 launch_scaled(p.pkg_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(x.d_unpack_sc.p),
                               static_cast<const uint64_t*>(x.w_unpack_sc.p), x.s_unpack, rb, nullptr,
-                              cp.d_scal.p, row_scale, col_scale, dc.aux);
+                              cp.d_scal.p, row_scale, col_scale, row_amax, col_amax, dc.aux);
                 tm.stop();
             }
         }
@@ -2634,6 +2644,7 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
     };
     g_stats.tri_items += cp.t_local.n_items;
     g_scaled_items += cp.s_local.n_items;
+    if (amax) g_amax_items += cp.s_local.n_items;
     if (cp.l_local.n_items() || cp.c_local.n_items || cp.t_local.n_items || cp.s_local.n_items) {
         g_stats.local_launches++;
         g_stats.local_bytes += p.local_bytes;
@@ -2647,6 +2658,7 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
                 x->l_unpack.n_items() || x->c_unpack.n_items || x->t_unpack.n_items || x->s_unpack.n_items ? 1 : 0;
             g_stats.tri_items += x->t_unpack.n_items;
             g_scaled_items += x->s_unpack.n_items;
+            if (amax) g_amax_items += x->s_unpack.n_items;
             count_items(x->l_pack);
             count_items(x->l_unpack);
             g_stats.convert_items += x->c_pack.n_items + x->c_unpack.n_items;
@@ -2759,25 +2771,24 @@ void execute_tiles_tri(costa_dtype_t dtype, const costa_tri_op_t* ops, int64_t n
     g_stats.tri_items += l.n_items;
 }
 
-void execute_tiles_scaled(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* ops,
-                          int64_t n, const void* src_base, void* dst_base, const void* scalars,
-                          int n_slots, const void* row_scale, const void* col_scale, int device) {
+namespace {
+// costa_hip_execute_tiles_scaled (`who`, no amax vector) and costa_hip_execute_tiles_amax
+void run_scaled_tiles(const std::string& who, costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
+                      const costa_scaled_op_t* ops, int64_t n, const void* src_base, void* dst_base,
+                      const void* scalars, int n_slots, const void* row_scale, const void* col_scale,
+                      void* row_amax, void* col_amax, int device) {
     std::lock_guard<std::recursive_mutex> lk(g_mutex);
-    if (!scaled_pair(src_dtype, dst_dtype))
-        throw error(COSTA_ERR_ARG, std::string("costa_hip_execute_tiles_scaled: no scaled kernel for ") +
-                                       dtype_name(src_dtype) + " -> " + dtype_name(dst_dtype));
-    if (!row_scale && !col_scale)
-        throw error(COSTA_ERR_ARG, "costa_hip_execute_tiles_scaled: no scale vector (use "
-                                   "costa_hip_execute_tiles_mixed)");
     device_ctx& dc = ctx(device);
     for (const void* v : {row_scale, col_scale})
         if (v && !is_device_ptr(v))
-            throw error(COSTA_ERR_ARG, "costa_hip_execute_tiles_scaled: the scale vectors must be "
-                                       "device-resident");
+            throw error(COSTA_ERR_ARG, who + ": the scale vectors must be device-resident");
+    for (const void* v : {row_amax, col_amax})
+        if (v && !is_device_ptr(v))
+            throw error(COSTA_ERR_ARG, who + ": the amax vectors must be device-resident");
     std::vector<costa_scaled_op_t> v(ops, ops + n);
     for (const auto& t : v)
         if ((t.op.flags >> COSTA_SLOT_SHIFT) >= uint32_t(std::max(n_slots, 0)))
-            throw error(COSTA_ERR_ARG, "costa_hip_execute_tiles_scaled: scalar slot out of range");
+            throw error(COSTA_ERR_ARG, who + ": scalar slot out of range");
     std::vector<costa_scaled_op_t> ord;
     std::vector<uint64_t> w;
     const scaled_list l = build_scaled_work(src_dtype, dst_dtype, v, reinterpret_cast<uintptr_t>(src_base),
@@ -2792,9 +2803,110 @@ void execute_tiles_scaled(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, cons
     d_scal.upload(sc, dc.main);
     launch_scaled(src_dtype, dst_dtype, static_cast<const costa_scaled_op_t*>(d_ops.p),
                   static_cast<const uint64_t*>(d_work.p), l, static_cast<const char*>(src_base),
-                  static_cast<char*>(dst_base), d_scal.p, row_scale, col_scale, dc.main);
+                  static_cast<char*>(dst_base), d_scal.p, row_scale, col_scale, row_amax, col_amax, dc.main);
     HIP_CHECK(hipStreamSynchronize(dc.main));
     g_scaled_items += l.n_items;
+    if (row_amax || col_amax) g_amax_items += l.n_items;
+}
+}  // namespace
+
+void execute_tiles_scaled(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* ops,
+                          int64_t n, const void* src_base, void* dst_base, const void* scalars,
+                          int n_slots, const void* row_scale, const void* col_scale, int device) {
+    if (!scaled_pair(src_dtype, dst_dtype))
+        throw error(COSTA_ERR_ARG, std::string("costa_hip_execute_tiles_scaled: no scaled kernel for ") +
+                                       dtype_name(src_dtype) + " -> " + dtype_name(dst_dtype));
+    if (!row_scale && !col_scale)
+        throw error(COSTA_ERR_ARG, "costa_hip_execute_tiles_scaled: no scale vector (use "
+                                   "costa_hip_execute_tiles_mixed)");
+    run_scaled_tiles("costa_hip_execute_tiles_scaled", src_dtype, dst_dtype, ops, n, src_base, dst_base,
+                     scalars, n_slots, row_scale, col_scale, nullptr, nullptr, device);
+}
+
+void execute_tiles_amax(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* ops,
+                        int64_t n, const void* src_base, void* dst_base, const void* scalars, int n_slots,
+                        const void* row_scale, const void* col_scale, void* row_amax, void* col_amax,
+                        int device) {
+    if (!scaled_pair(src_dtype, dst_dtype))
+        throw error(COSTA_ERR_ARG, std::string("costa_hip_execute_tiles_amax: no scaled kernel for ") +
+                                       dtype_name(src_dtype) + " -> " + dtype_name(dst_dtype));
+    if (!row_amax && !col_amax)
+        throw error(COSTA_ERR_ARG, "costa_hip_execute_tiles_amax: no amax vector (use "
+                                   "costa_hip_execute_tiles_scaled)");
+    run_scaled_tiles("costa_hip_execute_tiles_amax", src_dtype, dst_dtype, ops, n, src_base, dst_base,
+                     scalars, n_slots, row_scale, col_scale, row_amax, col_amax, device);
+}
+
+// ---------------------------------------------------------------- costa_hip_layout_amax
+std::vector<costa_scaled_op_t> layout_amax_ops(const elayout& L) {
+    std::vector<costa_scaled_op_t> ops;
+    if (L.rows_split.empty() || L.cols_split.empty()) return ops;
+    const int r0 = L.rows_split.front(), c0 = L.cols_split.front();
+    const bool col_major = L.ordering == 'C' || L.ordering == 'c';
+    ops.reserve(L.blocks.size());
+    for (const eblock& b : L.blocks) {
+        if (!b.rows.non_empty() || !b.cols.non_empty()) continue;
+        costa_scaled_op_t t{};
+        t.op.src = reinterpret_cast<uintptr_t>(b.data);
+        t.op.nf = col_major ? b.rows.length() : b.cols.length();
+        t.op.ns = col_major ? b.cols.length() : b.rows.length();
+        t.op.lds = b.ld;
+        t.op.flags = col_major ? COSTA_SCALED_F_ROWS : 0u;
+        t.row0 = b.rows.start - r0;
+        t.col0 = b.cols.start - c0;
+        if (t.op.lds < t.op.nf) throw error(COSTA_ERR_ARG, "costa: a block's leading dimension is below its extent");
+        ops.push_back(t);
+    }
+    return ops;
+}
+
+void layout_amax(const elayout& L, void* row_amax, void* col_amax, comm* c, void* user_stream, bool async) {
+    std::lock_guard<std::recursive_mutex> lk(g_mutex);
+    if (!c) throw error(COSTA_ERR_ARG, "costa: null communicator");
+    if (!amax_dtype(L.dtype))
+        throw error(COSTA_ERR_ARG, std::string("costa_hip_layout_amax: no amax of ") + dtype_name(L.dtype) +
+                                       " (real floating-point element types only)");
+    if (!row_amax && !col_amax)
+        throw error(COSTA_ERR_ARG, "costa_hip_layout_amax: both amax vectors are NULL");
+    device_ctx& dc = ctx(c->device);
+    if (!layout_on_device(L))
+        throw error(COSTA_ERR_ARG, "costa_hip_layout_amax: needs a device-resident layout");
+    for (const void* v : {row_amax, col_amax})
+        if (v && !is_device_ptr(v))
+            throw error(COSTA_ERR_ARG, "costa_hip_layout_amax: the amax vectors must be device-resident");
+    std::vector<costa_scaled_op_t> ord;
+    std::vector<uint64_t> w;
+    // (a source-only list: the destination side of build_scaled_work sees offset 0, ld 0)
+    const scaled_list l = build_scaled_work(L.dtype, L.dtype, layout_amax_ops(L), 0, 0, ord, w, false);
+    hipStream_t user = static_cast<hipStream_t>(user_stream);
+    if (user) {
+        HIP_CHECK(hipEventRecord(dc.ev_user, user));
+        HIP_CHECK(hipStreamWaitEvent(dc.main, dc.ev_user, 0));
+    }
+    if (l.n_items) {
+        // the context's own lists: uploads and launches are ordered on main, so a list still read by
+        // an earlier asynchronous call is overwritten only after that call's kernel
+        dc.amax_ops.upload(ord, dc.main);
+        dc.amax_work.upload(w, dc.main);
+        launch_amax(L.dtype, static_cast<const costa_scaled_op_t*>(dc.amax_ops.p),
+                    static_cast<const uint64_t*>(dc.amax_work.p), l.n_items, row_amax, col_amax, dc.main);
+        g_amax_items += l.n_items;
+    }
+    if (async) {
+        if (user) {
+            HIP_CHECK(hipEventRecord(dc.ev_done, dc.main));
+            HIP_CHECK(hipStreamWaitEvent(user, dc.ev_done, 0));
+        }
+        return;
+    }
+    HIP_CHECK(hipStreamSynchronize(dc.main));
+}
+
+int64_t amax_items(bool reset) {
+    std::lock_guard<std::recursive_mutex> lk(g_mutex);
+    const int64_t v = g_amax_items;
+    if (reset) g_amax_items = 0;
+    return v;
 }
 
 int64_t scaled_items(bool reset) {

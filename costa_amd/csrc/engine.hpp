@@ -88,6 +88,10 @@ struct job {
     bool scaled = false;
     const void* row_scale = nullptr;
     const void* col_scale = nullptr;
+    // amax outputs (costa_hip_transform_amax): device arrays updated by the LOCAL / UNPACK kernels of
+    // a scaled job; arguments of the call like the scales (with one of them both scales may be null)
+    void* row_amax = nullptr;
+    void* col_amax = nullptr;
 };
 
 // The three tile-op lists of one rank plus the exchange geometry.  Addresses of pack
@@ -310,15 +314,36 @@ scaled_list build_scaled_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
                               const std::vector<costa_scaled_op_t>& ops, uint64_t src_base,
                               uint64_t dst_base, std::vector<costa_scaled_op_t>& ordered,
                               std::vector<uint64_t>& work, bool dst_order);
+// (row_amax / col_amax: the amax outputs, device arrays of the compute type's unsigned integer; with
+// one of them the list runs on the AMAX instantiation, with neither on today's kernels)
 void launch_scaled(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* d_ops,
                    const uint64_t* d_work, const scaled_list& l, const char* src_base, char* dst_base,
-                   const void* d_scalars, const void* row_scale, const void* col_scale,
-                   void* stream /* hipStream_t */);
+                   const void* d_scalars, const void* row_scale, const void* col_scale, void* row_amax,
+                   void* col_amax, void* stream /* hipStream_t */);
 void execute_tiles_scaled(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* ops,
                           int64_t n, const void* src_base, void* dst_base, const void* scalars,
                           int n_slots, const void* row_scale, const void* col_scale, int device);
 // sub-tiles run by scaled_kernel since the last reset
 int64_t scaled_items(bool reset);
+// ---- amax outputs (costa_hip.h, "amax outputs") ----
+// costa_hip_execute_tiles_scaled plus the two outputs; the scales may both be null
+void execute_tiles_amax(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* ops,
+                        int64_t n, const void* src_base, void* dst_base, const void* scalars,
+                        int n_slots, const void* row_scale, const void* col_scale, void* row_amax,
+                        void* col_amax, int device);
+// the element types costa_hip_layout_amax reduces: FLOAT, DOUBLE, the 2-byte and the 1-byte types
+bool amax_dtype(costa_dtype_t t);
+// one source-only op per local block of L (host only): src = the block's address, nf x ns its extent
+// along its fast and slow index, (row0, col0) from the first row / column of L's matrix,
+// COSTA_SCALED_F_ROWS where the fast index walks rows (ordering 'C')
+std::vector<costa_scaled_op_t> layout_amax_ops(const elayout& L);
+// the reduce-only kernel (amax_kernel<Es>) over such ops and their work items (build_scaled_work)
+void launch_amax(costa_dtype_t dtype, const costa_scaled_op_t* d_ops, const uint64_t* d_work,
+                 int64_t n_items, void* row_amax, void* col_amax, void* stream /* hipStream_t */);
+void layout_amax(const elayout& L, void* row_amax, void* col_amax, struct comm* c, void* user_stream,
+                 bool async);
+// sub-tiles run by the AMAX instantiations of scaled_kernel and by amax_kernel since the last reset
+int64_t amax_items(bool reset);
 // ... of every scaled unpack op (plan::unpack_scaled), by the rule of exchange_round_of_ops
 void exchange_round_of_scaled(const struct plan& p, int rounds, std::vector<int>& unpack_round);
 

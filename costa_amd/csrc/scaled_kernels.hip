@@ -52,6 +52,32 @@
 // Whole sub-tiles with both VEC flags take the FULL path, where every guard folds away; sub-tile
 // remainders and sides off their strip's alignment (VEC flag clear) take the guarded, element-wise
 // form of the same loads and stores: same values.  No scratch.
+//
+// amax outputs (costa_hip.h, "amax outputs"): the AMAX instantiations of scaled_kernel also update
+// row_amax / col_amax, device arrays of U (the unsigned integer as wide as Tc), with
+// absbits(w(x)) = the bits of the widened source value with the sign bit cleared, by an unsigned
+// maximum; AMAX = false is the code above, unchanged.  The reduction uses the registers of the load
+// phase, which holds the same elements in copy and transpose mode: lane t has strips x[k] at
+// f = (t % 16) * 4 + e, s = t / 16 + 16 k.
+//   along s   the maximum of a strip's 4 elements, then of the 16 lanes of its DPP row (row_ror 8, 4,
+//             2, 1: every lane of the row ends with the row's maximum): one value per (t / 16, k),
+//             stored to LDS by the row's first lane
+//   along f   the maximum over k per element, then over the wavefront's 4 rows (two xor shuffles):
+//             64 partial maxima per wavefront, stored to LDS by its first row; the 4 wavefronts'
+//             partials meet in the update
+// through one static LDS array of (4 + 1) x 64 U (1.25 KiB; fp64 2.5 KiB), which only these
+// instantiations have, and ONE barrier: transpose mode's own, between staging and reading the tile;
+// in copy mode one after the stores, so no wavefront waits for another before it stores.  Then
+// wavefront 0 updates the 64 consecutive entries along s and wavefront 1 those along f with
+// __hip_atomic_fetch_max (relaxed, agent scope, result unused): one 256-byte (fp64: 512-byte) wave
+// instruction per vector and sub-tile, lanes past the sub-tile's tf / ts off.
+// A lane first reads its entry with a plain load -- requested at the start, with the source loads,
+// so that its latency is not added to the sub-tile's -- and skips the atomic when the entry is
+// already >= its value: entries only grow, so a stale read can only cause a superfluous atomic,
+// never a lost one; every sub-tile but the first few of a row or column band then issues none.  The
+// zero tails of partial strips are harmless as values (0 is the least U) and never index a vector.
+// A NULL vector's reduction is skipped (wave-uniform).  amax_kernel<Es> (costa_hip_layout_amax) is
+// the copy-mode load phase and this reduction, and stores nothing.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -251,12 +277,133 @@ struct sshape {
     static constexpr size_t lds_bytes = size_t(SBS) * P * sizeof(C);
 };
 
+// ---- amax outputs: unsigned maximum of absbits over the load phase's registers ----
+template <typename C>
+struct ubits {
+    using type = uint32_t;
+};
+template <>
+struct ubits<double> {
+    using type = uint64_t;
+};
+template <typename C>
+__device__ __forceinline__ typename ubits<C>::type absbits(C x) {
+    using U = typename ubits<C>::type;
+    U u;
+    __builtin_memcpy(&u, &x, sizeof(U));
+    return u & ~(U(1) << (8 * sizeof(U) - 1));
+}
+// lane (l + N) % 16 of the lane's own DPP row (every lane of the wavefront must be active)
+template <int N>
+__device__ __forceinline__ uint32_t row_ror(uint32_t v) {
+    return uint32_t(__builtin_amdgcn_update_dpp(int(v), int(v), 0x120 + N, 0xf, 0xf, false));
+}
+template <int N>
+__device__ __forceinline__ uint64_t row_ror(uint64_t v) {
+    return uint64_t(row_ror<N>(uint32_t(v))) | uint64_t(row_ror<N>(uint32_t(v >> 32))) << 32;
+}
+template <typename U>
+__device__ __forceinline__ U umax(U a, U b) {
+    return a > b ? a : b;
+}
+template <typename U>
+__device__ __forceinline__ U row_max16(U v) {
+    v = umax(v, row_ror<8>(v));
+    v = umax(v, row_ror<4>(v));
+    v = umax(v, row_ror<2>(v));
+    return umax(v, row_ror<1>(v));
+}
+// entries of the reduction's LDS array: per wavefront its 64 partial maxima along f, then the 64
+// maxima along s
+constexpr int AMAX_LDS = SNW * SBF + SBS;
+// the reduction is mapped to the default shape (a DPP row = the 16 lanes of one source column); a
+// tuning build of another shape refuses amax vectors at the launch
+constexpr bool AMAX_SHAPE = SLPC == 16 && SBF == 64 && SBS == 64 && SNW >= 2;
+
+// The amax update of one sub-tile, in three steps every thread of the workgroup takes outside
+// divergent control flow.  af (along f, tf entries) and as (along s, ts entries) point at the
+// sub-tile's origin; either may be null (wave-uniform).
+//   amax_begin    wavefront 0 (along s) and wavefront 1 (along f) read their 64 entries with plain
+//                 loads, requested with the load phase's own loads: the value is only used to skip
+//                 the atomic, so how old it is does not matter
+//   amax_partial  the load phase's registers reduced into `red` (no barrier); elements outside
+//                 tf x ts are 0 in x
+//   amax_commit   after a barrier between amax_partial and it (the caller's): the two wavefronts
+//                 update the entries their value would raise
+template <typename U>
+struct amax_out {
+    U* v;   // this lane's entry (null: none)
+    U cur;  // its value as read at the start
+};
+template <typename U, bool FULL>
+__device__ __forceinline__ amax_out<U> amax_begin(U* af, U* as, int tf, int ts) {
+    static_assert(AMAX_SHAPE, "the amax reduction is mapped to 64 x 64 sub-tiles of 256 threads");
+    const int lane = int(threadIdx.x) % 64, wave = int(threadIdx.x) / 64;
+    amax_out<U> o{nullptr, U(0)};
+    if (wave == 0 && as && (FULL || lane < ts)) o.v = as + lane;
+    if (wave == 1 && af && (FULL || lane < tf)) o.v = af + lane;
+    if (o.v) o.cur = *o.v;
+    return o;
+}
+template <typename Es>
+__device__ __forceinline__ void amax_partial(const strip<typename Es::st> (&x)[SPL], bool along_f, bool along_s,
+                                             typename ubits<typename Es::ct>::type* red) {
+    using U = typename ubits<typename Es::ct>::type;
+    const int t = int(threadIdx.x), lane = t % 64, wave = t / 64;
+    const int lf = (t % SLPC) * SV, c0 = t / SLPC;
+    U a[SPL][SV];
+#pragma unroll
+    for (int k = 0; k < SPL; ++k)
+#pragma unroll
+        for (int e = 0; e < SV; ++e) a[k][e] = absbits(Es::widen(x[k].e[e]));
+    if (along_s) {
+#pragma unroll
+        for (int k = 0; k < SPL; ++k) {
+            U m = a[k][0];
+#pragma unroll
+            for (int e = 1; e < SV; ++e) m = umax(m, a[k][e]);
+            m = row_max16(m);
+            if (t % SLPC == 0) red[SNW * SBF + c0 + k * SCPP] = m;
+        }
+    }
+    if (along_f) {
+#pragma unroll
+        for (int e = 0; e < SV; ++e) {
+            U m = a[0][e];
+#pragma unroll
+            for (int k = 1; k < SPL; ++k) m = umax(m, a[k][e]);
+            m = umax(m, U(__shfl_xor(m, 16)));
+            m = umax(m, U(__shfl_xor(m, 32)));
+            if (lane < SLPC) red[wave * SBF + lf + e] = m;
+        }
+    }
+}
+template <typename U>
+__device__ __forceinline__ void amax_commit(const amax_out<U>& o, const U* red) {
+    const int lane = int(threadIdx.x) % 64, wave = int(threadIdx.x) / 64;
+    if (!o.v) return;
+    U m;
+    if (wave == 0) {
+        m = red[SNW * SBF + lane];
+    } else {
+        m = red[lane];
+#pragma unroll
+        for (int w = 1; w < SNW; ++w) m = umax(m, red[w * SBF + lane]);
+    }
+    if (m > o.cur) (void)__hip_atomic_fetch_max(o.v, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // One sub-tile.  FULL: a whole 64 x 64 sub-tile with both VEC flags, every guard folds away.
-template <typename Es, typename Ed, bool FULL>
+// AMAX: ra / ca (row_amax / col_amax, either may be null) are updated from the load phase and `red`
+// is the reduction's LDS array; else all three are unused.
+template <typename Es, typename Ed, bool FULL, bool AMAX>
 __device__ __forceinline__ void run_scaled(const costa_scaled_op_t& sop, int f0, int s0, int tf_, int ts_,
                                            const char* src_base, char* dst_base, typename Ed::ct alpha,
                                            typename Ed::ct beta, const typename Ed::ct* rs,
-                                           const typename Ed::ct* cs, typename Ed::ct* tile) {
+                                           const typename Ed::ct* cs, typename Ed::ct* tile,
+                                           typename ubits<typename Ed::ct>::type* ra,
+                                           typename ubits<typename Ed::ct>::type* ca,
+                                           typename ubits<typename Ed::ct>::type* red) {
     using C = typename Ed::ct;
     using Ss = typename Es::st;
     using Sd = typename Ed::st;
@@ -300,6 +447,19 @@ __device__ __forceinline__ void run_scaled(const costa_scaled_op_t& sop, int f0,
         x[k] = strip<Ss>{};
         if (FULL || (nf_lane > 0 && s < ts)) x[k] = load_strip(src + s * lds + lf, nf_lane, vs);
     }
+    // amax outputs: the vectors indexed along f and along s at the sub-tile's origin; their entries
+    // are requested with the source loads (amax_begin)
+    using U = typename ubits<C>::type;
+    [[maybe_unused]] amax_out<U> am{nullptr, U(0)};
+    [[maybe_unused]] U* af = nullptr;
+    [[maybe_unused]] U* as = nullptr;
+    if constexpr (AMAX) {
+        af = frow ? ra : ca;
+        as = frow ? ca : ra;
+        if (af) af += int64_t(frow ? sop.row0 : sop.col0) + f0;
+        if (as) as += int64_t(frow ? sop.col0 : sop.row0) + s0;
+        am = amax_begin<U, FULL>(af, as, tf, ts);
+    }
 
     if (!(flags & COSTA_TILE_TRANSPOSE)) {
         // ---- copy mode: dst(f, s), no LDS
@@ -323,6 +483,7 @@ __device__ __forceinline__ void run_scaled(const costa_scaled_op_t& sop, int f0,
             sv[k] = C(0);
             if (vsl && (FULL || s < ts)) sv[k] = vsl[s];
         }
+        if constexpr (AMAX) amax_partial<Es>(x, af != nullptr, as != nullptr, red);
 #pragma unroll
         for (int k = 0; k < SPL; ++k) {
             const int s = c0 + k * SCPP;
@@ -333,6 +494,10 @@ __device__ __forceinline__ void run_scaled(const costa_scaled_op_t& sop, int f0,
                 o.e[e] = Ed::narrow(scale<C>(sx(Es::widen(x[k].e[e]), fv[e], sv[k]), Ed::widen(y[k].e[e]),
                                              kind, false, alpha, beta));
             store_strip(dst + s * ldd + lf, o, nf_lane, vd);
+        }
+        if constexpr (AMAX) {  // the update last: no wavefront waits for another before it stores
+            __syncthreads();
+            amax_commit(am, red);
         }
         return;
     }
@@ -376,6 +541,7 @@ __device__ __forceinline__ void run_scaled(const costa_scaled_op_t& sop, int f0,
         fv[k] = C(0);
         if (vf && unit(k, f, sb, n_s)) fv[k] = vf[f];
     }
+    if constexpr (AMAX) amax_partial<Es>(x, af != nullptr, as != nullptr, red);  // (before the tile's barrier)
 #pragma unroll
     for (int k = 0; k < SPL; ++k) {
         const int s = c0 + k * SCPP;
@@ -413,16 +579,26 @@ __device__ __forceinline__ void run_scaled(const costa_scaled_op_t& sop, int f0,
                                          alpha, beta));
         store_strip(dst + f * ldd + sb, o, n_s, vd);
     }
+    if constexpr (AMAX) amax_commit(am, red);
 }
 
-template <typename Es, typename Ed>
+// AMAX: ra / ca are row_amax / col_amax (either may be null); else they are unused
+template <typename Es, typename Ed, bool AMAX>
 __global__ __launch_bounds__(SNT) void scaled_kernel(const costa_scaled_op_t* __restrict__ ops,
                                                      const uint64_t* __restrict__ work,
                                                      const char* src_base, char* dst_base,
                                                      const typename Ed::ct* __restrict__ scalars,
                                                      const typename Ed::ct* __restrict__ rs,
-                                                     const typename Ed::ct* __restrict__ cs) {
+                                                     const typename Ed::ct* __restrict__ cs,
+                                                     typename ubits<typename Ed::ct>::type* ra,
+                                                     typename ubits<typename Ed::ct>::type* ca) {
     using C = typename Ed::ct;
+    using U = typename ubits<C>::type;
+    U* red = nullptr;
+    if constexpr (AMAX) {
+        __shared__ U amax_lds[AMAX_LDS];
+        red = amax_lds;
+    }
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     C* tile = reinterpret_cast<C*>(smem);
     // which sub-tile of which op (wave-uniform: scalar loads)
@@ -440,22 +616,81 @@ __global__ __launch_bounds__(SNT) void scaled_kernel(const costa_scaled_op_t* __
     const C beta = scalars[2 * slot + 1];
     const uint32_t vec_both = COSTA_TILE_VEC_SRC | COSTA_TILE_VEC_DST;
     if (tf == SBF && ts == SBS && (op.flags & vec_both) == vec_both)
-        run_scaled<Es, Ed, true>(sop, f0, s0, tf, ts, src_base, dst_base, alpha, beta, rs, cs, tile);
+        run_scaled<Es, Ed, true, AMAX>(sop, f0, s0, tf, ts, src_base, dst_base, alpha, beta, rs, cs, tile, ra,
+                                       ca, red);
     else
-        run_scaled<Es, Ed, false>(sop, f0, s0, tf, ts, src_base, dst_base, alpha, beta, rs, cs, tile);
+        run_scaled<Es, Ed, false, AMAX>(sop, f0, s0, tf, ts, src_base, dst_base, alpha, beta, rs, cs, tile, ra,
+                                        ca, red);
 }
 
-template <typename Es, typename Ed>
-void launch_pair(const costa_scaled_op_t* d_ops, const uint64_t* d_work, const scaled_list& l,
-                 const char* src_base, char* dst_base, const void* d_scalars, const void* rs,
-                 const void* cs, hipStream_t stream) {
+// costa_hip_layout_amax: the copy-mode load phase of scaled_kernel and its amax reduction over ops
+// whose source side alone is used; nothing but the two vectors is written
+template <typename Es>
+__global__ __launch_bounds__(SNT) void amax_kernel(const costa_scaled_op_t* __restrict__ ops,
+                                                   const uint64_t* __restrict__ work, const char* src_base,
+                                                   typename ubits<typename Es::ct>::type* ra,
+                                                   typename ubits<typename Es::ct>::type* ca) {
+    using U = typename ubits<typename Es::ct>::type;
+    using Ss = typename Es::st;
+    __shared__ U red[AMAX_LDS];
+    const uint64_t w = work[blockIdx.x];
+    const costa_scaled_op_t sop = ops[w >> 32];
+    const costa_tile_op_t& op = sop.op;
+    const uint32_t sub = uint32_t(w);
+    const int nbf = (op.nf + SBF - 1) / SBF;
+    const int f0 = int(sub % uint32_t(nbf)) * SBF;
+    const int s0 = int(sub / uint32_t(nbf)) * SBS;
+    const int tf = min(SBF, op.nf - f0);
+    const int ts = min(SBS, op.ns - s0);
+    const bool vs = op.flags & COSTA_TILE_VEC_SRC;
+    const bool frow = op.flags & COSTA_SCALED_F_ROWS;
+    const int64_t lds = op.lds;
+    U* af = frow ? ra : ca;
+    U* as = frow ? ca : ra;
+    if (af) af += int64_t(frow ? sop.row0 : sop.col0) + f0;
+    if (as) as += int64_t(frow ? sop.col0 : sop.row0) + s0;
+    const Ss* src = reinterpret_cast<const Ss*>(src_base + op.src) + int64_t(s0) * lds + f0;
+    const int lf = (int(threadIdx.x) % SLPC) * SV;
+    const int c0 = int(threadIdx.x) / SLPC;
+    strip<Ss> x[SPL];
+    amax_out<U> am;
+    if (tf == SBF && ts == SBS && vs) {
+#pragma unroll
+        for (int k = 0; k < SPL; ++k) x[k] = load_strip(src + (c0 + k * SCPP) * lds + lf, SV, true);
+        am = amax_begin<U, true>(af, as, tf, ts);
+    } else {
+        const int nf_lane = tf - lf;
+#pragma unroll
+        for (int k = 0; k < SPL; ++k) {
+            const int s = c0 + k * SCPP;
+            x[k] = strip<Ss>{};
+            if (nf_lane > 0 && s < ts) x[k] = load_strip(src + s * lds + lf, nf_lane, vs);
+        }
+        am = amax_begin<U, false>(af, as, tf, ts);
+    }
+    amax_partial<Es>(x, af != nullptr, as != nullptr, red);
+    __syncthreads();
+    amax_commit(am, red);
+}
+
+// the vectors of one launch: the scales (read) and the amax outputs (updated); any may be null
+struct scaled_vecs {
+    const void *rs, *cs;
+    void *ra, *ca;
+};
+
+template <typename Es, typename Ed, bool AMAX>
+void launch_inst(const costa_scaled_op_t* d_ops, const uint64_t* d_work, const scaled_list& l,
+                 const char* src_base, char* dst_base, const void* d_scalars, const scaled_vecs& v,
+                 hipStream_t stream) {
     using C = typename Ed::ct;
+    using U = typename ubits<C>::type;
     const int64_t max_grid = 1LL << 30;
     // copy-only lists need no LDS tile: more workgroups per CU
     const size_t lds = l.any_transpose ? sshape<C>::lds_bytes : 0;
     if (sshape<C>::lds_bytes > 64 * 1024) {  // (tuning builds: over the default dynamic-LDS limit)
         static const bool once = [] {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&scaled_kernel<Es, Ed>),
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&scaled_kernel<Es, Ed, AMAX>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, int(sshape<C>::lds_bytes));
             return true;
         }();
@@ -463,24 +698,54 @@ void launch_pair(const costa_scaled_op_t* d_ops, const uint64_t* d_work, const s
     }
     for (int64_t off = 0; off < l.n_items; off += max_grid) {
         const int64_t m = std::min(max_grid, l.n_items - off);
-        hipLaunchKernelGGL((scaled_kernel<Es, Ed>), dim3(unsigned(m)), dim3(SNT), lds, stream, d_ops,
+        hipLaunchKernelGGL((scaled_kernel<Es, Ed, AMAX>), dim3(unsigned(m)), dim3(SNT), lds, stream, d_ops,
                            d_work + off, src_base, dst_base, static_cast<const C*>(d_scalars),
-                           static_cast<const C*>(rs), static_cast<const C*>(cs));
+                           static_cast<const C*>(v.rs), static_cast<const C*>(v.cs), static_cast<U*>(v.ra),
+                           static_cast<U*>(v.ca));
     }
+}
+
+// the AMAX instantiation runs only where an amax vector is given
+template <typename Es, typename Ed>
+void launch_pair(const costa_scaled_op_t* d_ops, const uint64_t* d_work, const scaled_list& l,
+                 const char* src_base, char* dst_base, const void* d_scalars, const scaled_vecs& v,
+                 hipStream_t stream) {
+    if (!v.ra && !v.ca)
+        launch_inst<Es, Ed, false>(d_ops, d_work, l, src_base, dst_base, d_scalars, v, stream);
+    else if constexpr (AMAX_SHAPE)
+        launch_inst<Es, Ed, true>(d_ops, d_work, l, src_base, dst_base, d_scalars, v, stream);
+    else
+        throw error(COSTA_ERR_ARG, "costa: this build's scaled sub-tile has no amax reduction");
 }
 
 // N: f16_t / bf16_t / e4m3_t / e5m2_t; ROUND: a FLOAT source is rounded to N first (the half pairs)
 template <typename N, template <typename> class narrow_e, bool ROUND>
 void launch_narrow(bool src_f, bool dst_f, const costa_scaled_op_t* d_ops,
                    const uint64_t* d_work, const scaled_list& l, const char* src_base, char* dst_base,
-                   const void* d_scalars, const void* rs, const void* cs, hipStream_t s) {
+                   const void* d_scalars, const scaled_vecs& v, hipStream_t s) {
     using src_e = typename std::conditional<ROUND, f32_via<N>, f32_e>::type;
     if (src_f)
-        launch_pair<src_e, narrow_e<N>>(d_ops, d_work, l, src_base, dst_base, d_scalars, rs, cs, s);
+        launch_pair<src_e, narrow_e<N>>(d_ops, d_work, l, src_base, dst_base, d_scalars, v, s);
     else if (dst_f)
-        launch_pair<narrow_e<N>, f32_e>(d_ops, d_work, l, src_base, dst_base, d_scalars, rs, cs, s);
+        launch_pair<narrow_e<N>, f32_e>(d_ops, d_work, l, src_base, dst_base, d_scalars, v, s);
     else
-        launch_pair<narrow_e<N>, narrow_e<N>>(d_ops, d_work, l, src_base, dst_base, d_scalars, rs, cs, s);
+        launch_pair<narrow_e<N>, narrow_e<N>>(d_ops, d_work, l, src_base, dst_base, d_scalars, v, s);
+}
+
+template <typename Es>
+void launch_amax_of(const costa_scaled_op_t* d_ops, const uint64_t* d_work, int64_t n_items, void* ra,
+                    void* ca, hipStream_t stream) {
+    if constexpr (AMAX_SHAPE) {
+        using U = typename ubits<typename Es::ct>::type;
+        const int64_t max_grid = 1LL << 30;
+        for (int64_t off = 0; off < n_items; off += max_grid) {
+            const int64_t m = std::min(max_grid, n_items - off);
+            hipLaunchKernelGGL((amax_kernel<Es>), dim3(unsigned(m)), dim3(SNT), 0, stream, d_ops, d_work + off,
+                               static_cast<const char*>(nullptr), static_cast<U*>(ra), static_cast<U*>(ca));
+        }
+    } else {
+        throw error(COSTA_ERR_ARG, "costa: this build's scaled sub-tile has no amax reduction");
+    }
 }
 
 // bytes a side must be aligned to for vector accesses: its strip of 4 elements, 16 at most
@@ -545,8 +810,10 @@ scaled_list build_scaled_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
 
 void launch_scaled(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* d_ops,
                    const uint64_t* d_work, const scaled_list& l, const char* src_base, char* dst_base,
-                   const void* d_scalars, const void* rs, const void* cs, void* stream) {
+                   const void* d_scalars, const void* rs, const void* cs, void* row_amax, void* col_amax,
+                   void* stream) {
     if (l.n_items <= 0) return;
+    const scaled_vecs v{rs, cs, row_amax, col_amax};
     if (!scaled_pair(src_dtype, dst_dtype))
         throw error(COSTA_ERR_ARG, std::string("costa: no scaled kernel for ") + dtype_name(src_dtype) +
                                        " -> " + dtype_name(dst_dtype));
@@ -554,20 +821,44 @@ void launch_scaled(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa
     const bool src_f = src_dtype == COSTA_FLOAT, dst_f = dst_dtype == COSTA_FLOAT;
     const costa_dtype_t nt = src_f ? dst_dtype : src_dtype;  // the narrow type of a half / FP8 pair
     if (src_dtype == COSTA_DOUBLE)
-        launch_pair<f64_e, f64_e>(d_ops, d_work, l, src_base, dst_base, d_scalars, rs, cs, s);
+        launch_pair<f64_e, f64_e>(d_ops, d_work, l, src_base, dst_base, d_scalars, v, s);
     else if (src_f && dst_f)
-        launch_pair<f32_e, f32_e>(d_ops, d_work, l, src_base, dst_base, d_scalars, rs, cs, s);
+        launch_pair<f32_e, f32_e>(d_ops, d_work, l, src_base, dst_base, d_scalars, v, s);
     else if (nt == COSTA_HALF)
-        launch_narrow<f16_t, h_e, true>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, rs, cs, s);
+        launch_narrow<f16_t, h_e, true>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, v, s);
     else if (nt == COSTA_BFLOAT16)
-        launch_narrow<bf16_t, h_e, true>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, rs, cs, s);
+        launch_narrow<bf16_t, h_e, true>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, v, s);
     else if (nt == COSTA_FP8_E4M3)
-        launch_narrow<e4m3_t, q_e, false>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, rs, cs, s);
+        launch_narrow<e4m3_t, q_e, false>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, v, s);
     else
-        launch_narrow<e5m2_t, q_e, false>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, rs, cs, s);
+        launch_narrow<e5m2_t, q_e, false>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, v, s);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
         throw error(COSTA_ERR_HIP, std::string("scaled kernel launch failed: ") + hipGetErrorString(e));
+}
+
+bool amax_dtype(costa_dtype_t t) {
+    return t == COSTA_FLOAT || t == COSTA_DOUBLE || dtype_is_half(t) || dtype_is_fp8(t);
+}
+
+void launch_amax(costa_dtype_t dtype, const costa_scaled_op_t* d_ops, const uint64_t* d_work,
+                 int64_t n_items, void* row_amax, void* col_amax, void* stream) {
+    if (n_items <= 0) return;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    switch (dtype) {
+    case COSTA_FLOAT: launch_amax_of<f32_e>(d_ops, d_work, n_items, row_amax, col_amax, s); break;
+    case COSTA_DOUBLE: launch_amax_of<f64_e>(d_ops, d_work, n_items, row_amax, col_amax, s); break;
+    case COSTA_HALF: launch_amax_of<h_e<f16_t>>(d_ops, d_work, n_items, row_amax, col_amax, s); break;
+    case COSTA_BFLOAT16: launch_amax_of<h_e<bf16_t>>(d_ops, d_work, n_items, row_amax, col_amax, s); break;
+    case COSTA_FP8_E4M3: launch_amax_of<q_e<e4m3_t>>(d_ops, d_work, n_items, row_amax, col_amax, s); break;
+    case COSTA_FP8_E5M2: launch_amax_of<q_e<e5m2_t>>(d_ops, d_work, n_items, row_amax, col_amax, s); break;
+    default:
+        throw error(COSTA_ERR_ARG, std::string("costa_hip_layout_amax: no amax of ") + dtype_name(dtype) +
+                                       " (real floating-point element types only)");
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+        throw error(COSTA_ERR_HIP, std::string("amax kernel launch failed: ") + hipGetErrorString(e));
 }
 
 }  // namespace engine

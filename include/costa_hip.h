@@ -334,6 +334,67 @@ int costa_hip_transform_scaled_async(costa_layout_t A, costa_layout_t C, char tr
                                      const void* alpha, const void* beta, const void* row_scale,
                                      const void* col_scale, costa_comm_t comm, void* stream);
 
+/* ---- amax outputs (MI355X-native): row / column abs-max fused into the scaled kernels ----
+ * The statistic per-channel quantisation needs (row_scale = 448 / amax), taken from a distributed
+ * matrix without leaving the device: only the layout knows which global row and column an element
+ * of a padded local buffer belongs to.
+ *
+ * Definition.  Tc is the real compute type (float; double for the COSTA_DOUBLE pair) and U the
+ * unsigned integer of its width.  absbits(x) is the bits of x with the sign bit cleared: no
+ * arithmetic, so denormals are not flushed and -0 becomes +0.  An amax vector is a DEVICE array of
+ * Tc, and an update over a set of elements x is
+ *   v[k] <- the value whose bits are  umax(bits(v[k]), absbits(x)),   compared as U.
+ * For non-NaN values that is the exact maximum of |x|.  A NaN outranks everything, so the entry
+ * becomes a NaN (which payload is not specified).  umax is associative and commutative: the result
+ * does not depend on the order the kernels run in.  The update ACCUMULATES: the caller initialises
+ * the vector, normally to zeros, and several calls may update the same vector.  On entry every
+ * entry must have a clear sign bit (a non-negative value, +0, +inf or a NaN without the sign bit):
+ * an entry with the sign bit set compares above every |x| and would stay.  An amax vector must not
+ * overlap a scale vector or a layout's data.
+ *
+ * Fused form, costa_hip_transform_amax: computes exactly what costa_hip_transform_scaled computes
+ * with the same arguments, except that BOTH scale vectors may be NULL here: the result is then the
+ * scaled definition with both products skipped -- it still runs through scaled_kernel, and scale
+ * kind BITCOPY still means cvt(x).  In addition, for every element (i, j) of C's matrix that this
+ * rank writes (its LOCAL and UNPACK ops), row_amax[i] (m elements) and col_amax[j] (n elements) are
+ * updated with x, the value the scaled section defines as "the source value as the pair delivers it
+ * to its arithmetic": w(A) for H / Q sources, w(cvt_H(A)) for COSTA_FLOAT -> H (the package holds
+ * H, an UNPACK op has nothing else), the unrounded A otherwise -- before the scale products and
+ * before alpha / beta.  Either amax vector may be NULL; both NULL is COSTA_ERR_ARG ("use
+ * costa_hip_transform_scaled or costa_hip_transform").  A host pointer for an amax vector is
+ * COSTA_ERR_ARG with "device-resident" in the message.  Accepted pairs, refusals and their messages
+ * are those of scaled transforms; device-resident layouts only, any communicator size, no batches,
+ * no triangular mask.  The plan is the scaled plan: the amax addresses are not part of it, and one
+ * cached plan serves scaled and amax calls alike.  Calls without an amax vector launch exactly the
+ * kernels they launched before this section existed.
+ * Several ranks: each rank's vectors hold the maxima over that rank's OWN part of C; the caller
+ * max-reduces them across ranks (for non-NaN data an ordinary floating-point max all-reduce).
+ * In place (A and C the same layout, 'N') works as for scaled transforms; the amax is that of the
+ * matrix BEFORE scaling (the kernel holds x in registers before it stores).
+ * For the _async form the vectors must stay valid until the stream has passed the call.
+ *
+ * Reduce-only form, costa_hip_layout_amax: updates row_amax / col_amax with w(a) for every element
+ * a of the layout's local blocks; the vectors are indexed by the rows and columns of A's matrix,
+ * from the origin of costa_hip_layout_shape.  The widening is exact and no pair is involved.
+ * Nothing is written except the vectors; there is no exchange and no plan: the communicator
+ * supplies the device and the call ordering (calls run in order with the transforms of the
+ * process).  Element types COSTA_FLOAT, COSTA_DOUBLE (vectors of double), COSTA_HALF,
+ * COSTA_BFLOAT16, COSTA_FP8_E4M3, COSTA_FP8_E5M2; complex types and COSTA_INT32 are COSTA_ERR_ARG
+ * naming the type.  Device-resident layouts only; either vector may be NULL, not both.
+ *
+ * Two recipes.  Delayed scaling: costa_hip_transform_amax with the previous
+ * step's scales and this step's amax outputs, one pass.  Current scaling: costa_hip_layout_amax,
+ * the scales computed from the vectors on the device, then costa_hip_transform_scaled. */
+int costa_hip_transform_amax(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                             const void* beta, const void* row_scale, const void* col_scale,
+                             void* row_amax, void* col_amax, costa_comm_t comm);
+int costa_hip_transform_amax_async(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                                   const void* beta, const void* row_scale, const void* col_scale,
+                                   void* row_amax, void* col_amax, costa_comm_t comm, void* stream);
+int costa_hip_layout_amax(costa_layout_t A, void* row_amax, void* col_amax, costa_comm_t comm);
+int costa_hip_layout_amax_async(costa_layout_t A, void* row_amax, void* col_amax, costa_comm_t comm,
+                                void* stream);
+
 /* ---- stream-ordered variants (MI355X-native; no reference counterpart) ----
  * Enqueue the transform and return.  Layouts must be device-resident.  `stream` (a hipStream_t,
  * may be NULL) is joined at entry and made to wait for the result, so work queued on it after
@@ -404,6 +465,19 @@ int costa_hip_scaled_subtile(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, i
 /* sub-tiles run by scaled_kernel since the last reset (scaled transforms and
  * costa_hip_execute_tiles_scaled); kept beside costa_stats_t, whose layout does not change */
 int costa_hip_scaled_items(int64_t* items, int reset);
+/* costa_hip_execute_tiles_scaled plus the amax outputs ("amax outputs" above): `row_amax` /
+ * `col_amax` are device arrays of the compute type indexed by the ops' target coordinates (either
+ * may be NULL, not both) and updated with every op's source values; the scales may both be NULL */
+int costa_hip_execute_tiles_amax(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
+                                 const costa_scaled_op_t* ops, int64_t n, const void* src_base,
+                                 void* dst_base, const void* scalars, int n_slots,
+                                 const void* row_scale, const void* col_scale, void* row_amax,
+                                 void* col_amax, int device);
+/* sub-tiles run by the AMAX instantiations of scaled_kernel (amax transforms and
+ * costa_hip_execute_tiles_amax) and by the reduce-only kernel of costa_hip_layout_amax since the
+ * last reset; kept beside costa_stats_t.  costa_hip_scaled_items keeps counting every scaled_kernel
+ * sub-tile, those of the AMAX instantiations included */
+int costa_hip_amax_items(int64_t* items, int reset);
 
 /* ---- plan inspection (host only, never touches a GPU) ----
  * Plans the transform for rank `rank` of `nranks` and copies the three descriptor
