@@ -232,6 +232,10 @@ def lib():
         "costa_hip_comm_self": (i, [i, C.POINTER(vp)]),
         "costa_hip_comm_unique_id": (i, [C.c_char_p]),
         "costa_hip_comm_create": (i, [C.c_char_p, i, i, i, C.POINTER(vp)]),
+        "costa_hip_comm_emulated": (i, [i, i, i, C.POINTER(vp)]),
+        "costa_hip_comm_emulate": (i, [vp, i, i, vp]),
+        "costa_hip_exchange_rounds": (i, []),
+        "costa_hip_round_range": (i, [i64, i, i, i, C.POINTER(i64), C.POINTER(i64)]),
         "costa_hip_comm_rank": (i, [vp]),
         "costa_hip_comm_size": (i, [vp]),
         "costa_hip_comm_destroy": (None, [vp]),
@@ -429,6 +433,23 @@ def custom_layout(rowblocks, colblocks, rowsplit, colsplit, owners, localblocks,
 
 
 # ------------------------------------------------------------------ communicators
+EMULATE_PACK, EMULATE_UNPACK, EMULATE_LOCAL = 1, 2, 3
+EMULATE_PARTS = {"pack": EMULATE_PACK, "unpack": EMULATE_UNPACK, "local": EMULATE_LOCAL}
+
+
+def exchange_rounds() -> int:
+    """Parts a peer's package of at least 16 MiB is exchanged in (costa_hip_exchange_rounds)."""
+    return lib().costa_hip_exchange_rounds()
+
+
+def round_range(count: int, elem_bytes: int, rounds: int, round: int) -> tuple:
+    """Element range [lo, hi) that round ``round`` of ``rounds`` moves of a package of ``count``
+    elements of ``elem_bytes`` bytes (costa_hip_round_range; host only)."""
+    lo, hi = C.c_int64(), C.c_int64()
+    _check(lib().costa_hip_round_range(count, elem_bytes, rounds, round, C.byref(lo), C.byref(hi)))
+    return lo.value, hi.value
+
+
 class Comm:
     """One rank per GPU.  ``Comm.self(device)`` for a single rank; for several ranks one rank
     calls ``Comm.unique_id()``, the caller broadcasts the 128 bytes, and every rank calls
@@ -455,6 +476,21 @@ class Comm:
         h = C.c_void_p()
         _check(lib().costa_hip_comm_create(uid, nranks, rank, device, C.byref(h)))
         return Comm(h.value)
+
+    @staticmethod
+    def emulated(rank: int, nranks: int, device: int = 0) -> "Comm":
+        """Test mode: rank ``rank`` of ``nranks`` without RCCL, planned like an RCCL communicator of
+        that size; ``emulate`` selects the part its transforms launch (costa_hip.h, "test modes")."""
+        h = C.c_void_p()
+        _check(lib().costa_hip_comm_emulated(rank, nranks, device, C.byref(h)))
+        return Comm(h.value)
+
+    def emulate(self, part, round: int = -1, buffer=None):
+        """The part the next transforms on this emulated communicator launch: ``"pack"`` /
+        ``"unpack"`` round ``round`` (-1: every round) into / from the package ``buffer``, or
+        ``"local"``."""
+        code = EMULATE_PARTS.get(part, part) if isinstance(part, str) else int(part)
+        _check(lib().costa_hip_comm_emulate(self._h, code, round, C.c_void_p(_ptr(buffer))))
 
     @property
     def handle(self):

@@ -311,6 +311,35 @@ int costa_hip_comm_create(const unsigned char id[128], int nranks, int rank, int
     });
 }
 
+int costa_hip_comm_emulated(int rank, int nranks, int device, costa_comm_t* out) {
+    return gpu_guarded([&] {
+        if (!out) throw costa::engine::error(COSTA_ERR_ARG, "null output handle");
+        auto h = std::make_unique<costa_comm_s>();
+        h->c = costa::engine::comm_emulated(rank, nranks, device);
+        *out = h.release();
+    });
+}
+
+int costa_hip_comm_emulate(costa_comm_t comm, int part, int round, void* buffer) {
+    return gpu_guarded([&] {
+        if (!comm) throw costa::engine::error(COSTA_ERR_ARG, "null communicator");
+        costa::engine::comm_emulate(comm->c, part, round, buffer);
+    });
+}
+
+int costa_hip_exchange_rounds(void) { return costa::engine::exchange_rounds(); }
+
+int costa_hip_round_range(int64_t count, int elem_bytes, int rounds, int round, int64_t* lo,
+                          int64_t* hi) {
+    return guarded([&] {
+        if (!lo || !hi) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        if (count < 0 || elem_bytes < 1 || rounds < 1 || round < 0)
+            throw costa::engine::error(COSTA_ERR_ARG, "costa_hip_round_range: negative count or round, "
+                                                      "or no element size or rounds");
+        costa::engine::round_range(count, size_t(elem_bytes), rounds, round, *lo, *hi);
+    });
+}
+
 int costa_hip_comm_rank(costa_comm_t comm) { return comm ? costa::engine::comm_rank(comm->c) : -1; }
 int costa_hip_comm_size(costa_comm_t comm) { return comm ? costa::engine::comm_size(comm->c) : -1; }
 void costa_hip_comm_destroy(costa_comm_t comm) {

@@ -153,6 +153,14 @@ device_ctx& ctx(int device) {
 struct comm {
     int rank = 0, size = 1, device = 0;
     ncclComm_t nccl = nullptr;
+    // rank emulation (test mode, comm_emulated): planned like an RCCL communicator of `size` ranks;
+    // a transform launches only the selected part (comm_emulate) against the caller's package
+    bool emulated = false;
+    int part = 0;   // 0 = none selected yet, else COSTA_EMULATE_PACK / _UNPACK / _LOCAL
+    int round = -1; // of PACK / UNPACK: 0 .. exchange_rounds() - 1, or -1 = every round in order
+    void* buffer = nullptr;  // the caller's send (PACK) / receive (UNPACK) package
+    // whether its plans have exchange rounds and package lists
+    bool exchanges() const { return nccl != nullptr || emulated; }
     ~comm() {
         if (nccl) (void)ncclCommDestroy(nccl);
     }
@@ -211,6 +219,45 @@ comm* comm_create(const unsigned char* id, int nranks, int rank, int device) {
     return c;
 }
 
+namespace {
+bool is_device_ptr(const void* p);
+}
+
+comm* comm_emulated(int rank, int nranks, int device) {
+    if (nranks < 1 || rank < 0 || rank >= nranks) throw error(COSTA_ERR_ARG, "costa: bad rank/size");
+    comm* c = new_comm(device);
+    c->rank = rank;
+    c->size = nranks;
+    c->emulated = true;
+    return c;
+}
+
+void comm_emulate(comm* c, int part, int round, void* buffer) {
+    if (!c) throw error(COSTA_ERR_ARG, "costa: null communicator");
+    if (!c->emulated)
+        throw error(COSTA_ERR_ARG, "costa_hip_comm_emulate: not an emulated communicator "
+                                   "(costa_hip_comm_emulated makes one)");
+    if (part != COSTA_EMULATE_PACK && part != COSTA_EMULATE_UNPACK && part != COSTA_EMULATE_LOCAL)
+        throw error(COSTA_ERR_ARG, "costa_hip_comm_emulate: part is not PACK, UNPACK or LOCAL");
+    if (part == COSTA_EMULATE_LOCAL) {
+        round = -1;
+        buffer = nullptr;
+    } else {
+        if (round < -1 || round >= exchange_rounds())
+            throw error(COSTA_ERR_ARG, "costa_hip_comm_emulate: round is not -1 or below "
+                                       "costa_hip_exchange_rounds()");
+        HIP_CHECK(hipSetDevice(c->device));
+        if (!buffer || !is_device_ptr(buffer))
+            throw error(COSTA_ERR_ARG, "costa_hip_comm_emulate: the package buffer is not a device pointer");
+        if (reinterpret_cast<uintptr_t>(buffer) % 256)
+            throw error(COSTA_ERR_ARG, "costa_hip_comm_emulate: the package buffer is not aligned to "
+                                       "256 bytes");
+    }
+    c->part = part;
+    c->round = round;
+    c->buffer = buffer;
+}
+
 const char* tuning_env(const char* name) {
     static const bool on = [] {
         const char* s = std::getenv("COSTA_TUNING");
@@ -259,8 +306,20 @@ int exchange_rounds() {
     return v;
 }
 
+// (COSTA_ROUND_MIN_BYTES, tuning: another threshold, so that the GPU tests have plans of several
+// rounds at fixture size; every rank must agree)
+size_t round_min_bytes() {
+    static const size_t v = [] {
+        const char* s = tuning_env("COSTA_ROUND_MIN_BYTES");
+        const long long x = s ? std::atoll(s) : 0;
+        return x > 0 ? size_t(x) : kRoundMinBytes;
+    }();
+    return v;
+}
+
 namespace {
-int parts_of(int64_t n, size_t E, int R) { return size_t(n) * E >= kRoundMinBytes ? R : 1; }
+int parts_of(int64_t n, size_t E, int R) { return size_t(n) * E >= round_min_bytes() ? R : 1; }
+}  // namespace
 // element range [lo, hi) of round r of a package of n elements (empty past its parts)
 void round_range(int64_t n, size_t E, int R, int r, int64_t& lo, int64_t& hi) {
     const int parts = parts_of(n, E, R);
@@ -271,6 +330,7 @@ void round_range(int64_t n, size_t E, int R, int r, int64_t& lo, int64_t& hi) {
     lo = n * r / parts;
     hi = n * (r + 1) / parts;
 }
+namespace {
 // round holding element o (0 <= o < n) of a package of n elements
 int round_of(int64_t o, int64_t n, size_t E, int R) {
     const int parts = parts_of(n, E, R);
@@ -2094,7 +2154,7 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
             if (host_pipeline_accepts(hplan->dtype, hplan->pack_ops)) {
                 cp->staged = false;
                 cp->p = std::move(hplan);
-                const int R = c->nccl ? exchange_rounds() : 1;
+                const int R = c->exchanges() ? exchange_rounds() : 1;
                 std::vector<int> pr, ur;
                 exchange_round_of_ops(*cp->p, R, pr, ur);
                 cp->pipe = make_host_pipeline(cp->p->dtype, cp->p->pack_ops, cp->p->local_ops,
@@ -2202,7 +2262,7 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
     // exchange rounds: pack ops go to the round of their first element (every element a round
     // sends is packed by then), unpack ops to the round of their last (every element they read
     // has arrived)
-    const int R = c->nccl ? exchange_rounds() : 1;
+    const int R = c->exchanges() ? exchange_rounds() : 1;
     std::vector<std::vector<costa_tile_op_t>> pk(static_cast<size_t>(R)), up(static_cast<size_t>(R));
     {
         std::vector<int> pr, ur;
@@ -2437,12 +2497,217 @@ void issue_exchange(comm* c, const plan& p, char* sb, char* rb, hipStream_t s, i
     }
     NCCL_CHECK(ncclGroupEnd());
 }
+
+// the vectors of a scaled transform: arguments of the call, read (scales) and updated (amax) by
+// its LOCAL / UNPACK kernels
+struct scaled_args {
+    const void *row_scale = nullptr, *col_scale = nullptr;
+    void *row_amax = nullptr, *col_amax = nullptr;
+    bool amax() const { return row_amax || col_amax; }
+};
+
+// The launch blocks of a transform: LOCAL, one round's PACK, one round's UNPACK.  transform() calls
+// them for an RCCL communicator (on the context's three streams, around issue_exchange) and for the
+// selected part of an emulated one (on main, against the caller's package).
+void launch_local(const cached_plan& cp, const scaled_args& sv, phase_timer& tm, hipStream_t ls) {
+    const plan& p = *cp.p;
+    if (cp.c_local.n_items) {
+        tm.start(PH_LOCAL, ls);
+        launch_convert(p.src_dtype, p.dtype, static_cast<const costa_tile_op_t*>(cp.d_local.p),
+                       static_cast<const uint64_t*>(cp.w_local.p), cp.c_local, nullptr, nullptr,
+                       cp.d_scal.p, ls);
+        tm.stop();
+    }
+    if (cp.l_local.n_items()) {
+        tm.start(PH_LOCAL, ls);
+        launch_tiles(p.dtype,
+                     make_launch(cp.l_local, cp.d_local.p, cp.w_local.p, nullptr, nullptr,
+                                 cp.d_scal.p, cp.tr_local, cp.ax_local),
+                     ls);
+        tm.stop();
+    }
+    if (cp.t_local.n_items) {  // the edge tiles of a triangular plan, behind its ordinary LOCAL list
+        tm.start(PH_TRI_LOCAL, ls);
+        launch_tri(p.dtype, static_cast<const costa_tri_op_t*>(cp.d_local_tri.p),
+                   static_cast<const uint64_t*>(cp.w_local_tri.p), cp.t_local, nullptr, nullptr,
+                   cp.d_scal.p, ls);
+        tm.stop();
+    }
+
+    if (cp.s_local.n_items) {  // the LOCAL list of a scaled plan
+        tm.start(PH_LOCAL, ls);
+        launch_scaled(p.src_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(cp.d_local_sc.p),
+                      static_cast<const uint64_t*>(cp.w_local_sc.p), cp.s_local, nullptr, nullptr,
+                      cp.d_scal.p, sv.row_scale, sv.col_scale, sv.row_amax, sv.col_amax, ls);
+        tm.stop();
+    }
+}
+
+// round x's pack lists into the send package sb, on stream s
+void launch_pack_round(const cached_plan& cp, const cached_plan::xround& x, char* sb, phase_timer& tm,
+                       hipStream_t s) {
+    const plan& p = *cp.p;
+    if (x.c_pack.n_items) {
+        tm.start(PH_PACK, s);
+        launch_convert(p.src_dtype, p.pkg_dtype, static_cast<const costa_tile_op_t*>(x.d_pack.p),
+                       static_cast<const uint64_t*>(x.w_pack.p), x.c_pack, nullptr, sb,
+                       cp.d_scal.p, s);
+        tm.stop();
+    }
+    if (x.l_pack.n_items()) {
+        tm.start(PH_PACK, s);
+        launch_tiles(p.pkg_dtype,
+                     make_launch(x.l_pack, x.d_pack.p, x.w_pack.p, nullptr, sb, cp.d_scal.p,
+                                 false, false),
+                     s);
+        tm.stop();
+    }
+}
+
+// round x's unpack lists from the receive package rb, on stream s; each launch waits for `moved`
+// (the round's exchange; null: the package is already there)
+void launch_unpack_round(const cached_plan& cp, const cached_plan::xround& x, const char* rb,
+                         const scaled_args& sv, phase_timer& tm, hipStream_t s, hipEvent_t moved) {
+    const plan& p = *cp.p;
+    if (x.c_unpack.n_items) {
+        if (moved) HIP_CHECK(hipStreamWaitEvent(s, moved, 0));
+        tm.start(PH_UNPACK, s);
+        launch_convert(p.pkg_dtype, p.dtype, static_cast<const costa_tile_op_t*>(x.d_unpack.p),
+                       static_cast<const uint64_t*>(x.w_unpack.p), x.c_unpack, rb, nullptr,
+                       cp.d_scal.p, s);
+        tm.stop();
+    }
+    if (x.l_unpack.n_items()) {
+        if (moved) HIP_CHECK(hipStreamWaitEvent(s, moved, 0));
+        tm.start(PH_UNPACK, s);
+        launch_tiles(p.dtype,
+                     make_launch(x.l_unpack, x.d_unpack.p, x.w_unpack.p, rb, nullptr,
+                                 cp.d_scal.p, x.tr_unpack, x.ax_unpack),
+                     s);
+        tm.stop();
+    }
+    if (x.t_unpack.n_items) {  // the round's edge tiles, after its ordinary unpack launch
+        if (moved) HIP_CHECK(hipStreamWaitEvent(s, moved, 0));
+        tm.start(PH_TRI_UNPACK, s);
+        launch_tri(p.dtype, static_cast<const costa_tri_op_t*>(x.d_unpack_tri.p),
+                   static_cast<const uint64_t*>(x.w_unpack_tri.p), x.t_unpack, rb, nullptr,
+                   cp.d_scal.p, s);
+        tm.stop();
+    }
+    if (x.s_unpack.n_items) {  // the round's unpack list of a scaled plan
+        if (moved) HIP_CHECK(hipStreamWaitEvent(s, moved, 0));
+        tm.start(PH_UNPACK, s);
+        launch_scaled(p.pkg_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(x.d_unpack_sc.p),
+                      static_cast<const uint64_t*>(x.w_unpack_sc.p), x.s_unpack, rb, nullptr,
+                      cp.d_scal.p, sv.row_scale, sv.col_scale, sv.row_amax, sv.col_amax, s);
+        tm.stop();
+    }
+}
+
+// the statistics of those launches
+void count_items(const plan& p, const work_split& w) {
+    g_stats.tile_items += w.n_large + w.n_medium;
+    g_stats.skew_items += w.n_skew;
+    g_stats.cblock_items += w.n_cblock;
+    g_stats.tiny_items += w.n_tiny;
+    if (!dtype_is_complex(p.dtype) && pieces_in_group_launch(w.n_cblock, w.n_tiny))
+        g_stats.fused_pieces += w.n_tiny;
+}
+
+void count_local(const cached_plan& cp, bool amax) {
+    const plan& p = *cp.p;
+    g_stats.tri_items += cp.t_local.n_items;
+    g_scaled_items += cp.s_local.n_items;
+    if (amax) g_amax_items += cp.s_local.n_items;
+    if (cp.l_local.n_items() || cp.c_local.n_items || cp.t_local.n_items || cp.s_local.n_items) {
+        g_stats.local_launches++;
+        g_stats.local_bytes += p.local_bytes;
+        count_items(p, cp.l_local);
+        g_stats.convert_items += cp.c_local.n_items;
+    }
+}
+
+void count_pack_round(const cached_plan& cp, const cached_plan::xround& x) {
+    g_stats.pack_launches += x.l_pack.n_items() || x.c_pack.n_items ? 1 : 0;
+    count_items(*cp.p, x.l_pack);
+    g_stats.convert_items += x.c_pack.n_items;
+}
+
+void count_unpack_round(const cached_plan& cp, const cached_plan::xround& x, bool amax) {
+    g_stats.unpack_launches +=
+        x.l_unpack.n_items() || x.c_unpack.n_items || x.t_unpack.n_items || x.s_unpack.n_items ? 1 : 0;
+    g_stats.tri_items += x.t_unpack.n_items;
+    g_scaled_items += x.s_unpack.n_items;
+    if (amax) g_amax_items += x.s_unpack.n_items;
+    count_items(*cp.p, x.l_unpack);
+    g_stats.convert_items += x.c_unpack.n_items;
+}
+
+// whether the device allocation around `buffer` has `bytes` bytes from it on (true where the
+// runtime cannot tell)
+bool buffer_holds(const void* buffer, size_t bytes) {
+    hipDeviceptr_t base = nullptr;
+    size_t sz = 0;
+    if (hipMemGetAddressRange(&base, &sz, const_cast<void*>(buffer)) != hipSuccess) {
+        (void)hipGetLastError();
+        return true;
+    }
+    const size_t off = size_t(static_cast<const char*>(buffer) - static_cast<const char*>(base));
+    return off <= sz && sz - off >= bytes;
+}
+
+// The selected part of an emulated communicator (comm_emulate), on main: the same lists and
+// launches as below, the exchange being the caller's copies between the ranks' packages.  The
+// plan's pack_bytes / unpack_bytes are counted with the last round, `transforms` with LOCAL.
+void run_emulated_part(const comm* c, device_ctx& dc, const cached_plan& cp, const scaled_args& sv) {
+    const plan& p = *cp.p;
+    const size_t E = dtype_size(p.pkg_dtype);
+    phase_timer tm(dc, g_profiling);
+    const int R = int(cp.rounds.size());
+    const int r0 = c->round < 0 ? 0 : c->round, r1 = c->round < 0 ? R : c->round + 1;
+    if (c->part == COSTA_EMULATE_LOCAL) {
+        launch_local(cp, sv, tm, dc.main);
+        count_local(cp, sv.amax());
+        g_stats.transforms++;
+    } else if (c->part == COSTA_EMULATE_PACK) {
+        if (!buffer_holds(c->buffer, size_t(p.send_elems) * E))
+            throw error(COSTA_ERR_ARG, "costa: the emulated send package is smaller than the plan's");
+        for (int r = r0; r < r1; ++r) {
+            launch_pack_round(cp, *cp.rounds[size_t(r)], static_cast<char*>(c->buffer), tm, dc.main);
+            count_pack_round(cp, *cp.rounds[size_t(r)]);
+        }
+        if (r1 == R) g_stats.pack_bytes += p.pack_bytes;
+    } else {
+        if (!buffer_holds(c->buffer, size_t(p.recv_elems) * E))
+            throw error(COSTA_ERR_ARG, "costa: the emulated receive package is smaller than the plan's");
+        for (int r = r0; r < r1; ++r) {
+            launch_unpack_round(cp, *cp.rounds[size_t(r)], static_cast<const char*>(c->buffer), sv, tm,
+                                dc.main, nullptr);
+            count_unpack_round(cp, *cp.rounds[size_t(r)], sv.amax());
+        }
+        if (r1 == R) g_stats.unpack_bytes += p.unpack_bytes;
+    }
+    HIP_CHECK(hipStreamSynchronize(dc.main));
+    dc.resolve();
+}
+
 }  // namespace
 
 void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool async) {
     std::lock_guard<std::recursive_mutex> lk(g_mutex);
     if (!c) throw error(COSTA_ERR_ARG, "costa: null communicator");
     device_ctx& dc = ctx(c->device);
+    if (c->emulated) {  // test mode: one part of the transform against the caller's package
+        if (c->part == 0)
+            throw error(COSTA_ERR_ARG, "costa: an emulated communicator with no part selected "
+                                       "(costa_hip_comm_emulate)");
+        if (async)
+            throw error(COSTA_ERR_ARG, "costa: an emulated communicator runs blocking transforms only "
+                                       "(no _async form)");
+        for (const job& j : jobs)
+            if (!layout_on_device(*j.A) || !layout_on_device(*j.C))
+                throw error(COSTA_ERR_ARG, "costa: an emulated communicator needs device-resident layouts");
+    }
     cached_plan& cp = *get_plan(jobs, c, dc);
     const plan& p = *cp.p;
     const size_t E = dtype_size(p.pkg_dtype);  // of the send / receive packages
@@ -2498,6 +2763,8 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
         g_stats.transforms++;
         return;
     }
+    const scaled_args sv{row_scale, col_scale, row_amax, col_amax};
+    if (c->emulated) return run_emulated_part(c, dc, cp, sv);
     phase_timer tm(dc, g_profiling);
 
     // H2D of host-resident data
@@ -2517,36 +2784,7 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
         HIP_CHECK(hipEventRecord(dc.ev_ready, dc.main));
         HIP_CHECK(hipStreamWaitEvent(dc.aux, dc.ev_ready, 0));
     }
-    if (cp.c_local.n_items) {
-        tm.start(PH_LOCAL, ls);
-        launch_convert(p.src_dtype, p.dtype, static_cast<const costa_tile_op_t*>(cp.d_local.p),
-                       static_cast<const uint64_t*>(cp.w_local.p), cp.c_local, nullptr, nullptr,
-                       cp.d_scal.p, ls);
-        tm.stop();
-    }
-    if (cp.l_local.n_items()) {
-        tm.start(PH_LOCAL, ls);
-        launch_tiles(p.dtype,
-                     make_launch(cp.l_local, cp.d_local.p, cp.w_local.p, nullptr, nullptr,
-                                 cp.d_scal.p, cp.tr_local, cp.ax_local),
-                     ls);
-        tm.stop();
-    }
-    if (cp.t_local.n_items) {  // the edge tiles of a triangular plan, behind its ordinary LOCAL list
-        tm.start(PH_TRI_LOCAL, ls);
-        launch_tri(p.dtype, static_cast<const costa_tri_op_t*>(cp.d_local_tri.p),
-                   static_cast<const uint64_t*>(cp.w_local_tri.p), cp.t_local, nullptr, nullptr,
-                   cp.d_scal.p, ls);
-        tm.stop();
-    }
-
-    if (cp.s_local.n_items) {  // the LOCAL list of a scaled plan
-        tm.start(PH_LOCAL, ls);
-        launch_scaled(p.src_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(cp.d_local_sc.p),
-                      static_cast<const uint64_t*>(cp.w_local_sc.p), cp.s_local, nullptr, nullptr,
-                      cp.d_scal.p, row_scale, col_scale, row_amax, col_amax, ls);
-        tm.stop();
-    }
+    launch_local(cp, sv, tm, ls);
 
     if (exchange) {
         dc.send.reserve(size_t(p.send_elems) * E + 256);
@@ -2558,22 +2796,7 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
         const int R = int(cp.rounds.size());
         dc.round_events(size_t(R));
         for (int r = 0; r < R; ++r) {
-            const auto& x = *cp.rounds[size_t(r)];
-            if (x.c_pack.n_items) {
-                tm.start(PH_PACK, dc.main);
-                launch_convert(p.src_dtype, p.pkg_dtype, static_cast<const costa_tile_op_t*>(x.d_pack.p),
-                               static_cast<const uint64_t*>(x.w_pack.p), x.c_pack, nullptr, sb,
-                               cp.d_scal.p, dc.main);
-                tm.stop();
-            }
-            if (x.l_pack.n_items()) {
-                tm.start(PH_PACK, dc.main);
-                launch_tiles(p.pkg_dtype,
-                             make_launch(x.l_pack, x.d_pack.p, x.w_pack.p, nullptr, sb, cp.d_scal.p,
-                                         false, false),
-                             dc.main);
-                tm.stop();
-            }
+            launch_pack_round(cp, *cp.rounds[size_t(r)], sb, tm, dc.main);
             HIP_CHECK(hipEventRecord(dc.ev_packed[size_t(r)], dc.main));
             HIP_CHECK(hipStreamWaitEvent(dc.xch, dc.ev_packed[size_t(r)], 0));
             tm.start(PH_EXCHANGE, dc.xch);
@@ -2581,42 +2804,8 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
             tm.stop();
             HIP_CHECK(hipEventRecord(dc.ev_moved[size_t(r)], dc.xch));
         }
-        for (int r = 0; r < R; ++r) {
-            const auto& x = *cp.rounds[size_t(r)];
-            if (x.c_unpack.n_items) {
-                HIP_CHECK(hipStreamWaitEvent(dc.aux, dc.ev_moved[size_t(r)], 0));
-                tm.start(PH_UNPACK, dc.aux);
-                launch_convert(p.pkg_dtype, p.dtype, static_cast<const costa_tile_op_t*>(x.d_unpack.p),
-                               static_cast<const uint64_t*>(x.w_unpack.p), x.c_unpack, rb, nullptr,
-                               cp.d_scal.p, dc.aux);
-                tm.stop();
-            }
-            if (x.l_unpack.n_items()) {
-                HIP_CHECK(hipStreamWaitEvent(dc.aux, dc.ev_moved[size_t(r)], 0));
-                tm.start(PH_UNPACK, dc.aux);
-                launch_tiles(p.dtype,
-                             make_launch(x.l_unpack, x.d_unpack.p, x.w_unpack.p, rb, nullptr,
-                                         cp.d_scal.p, x.tr_unpack, x.ax_unpack),
-                             dc.aux);
-                tm.stop();
-            }
-            if (x.t_unpack.n_items) {  // the round's edge tiles, after its ordinary unpack launch
-                HIP_CHECK(hipStreamWaitEvent(dc.aux, dc.ev_moved[size_t(r)], 0));
-                tm.start(PH_TRI_UNPACK, dc.aux);
-                launch_tri(p.dtype, static_cast<const costa_tri_op_t*>(x.d_unpack_tri.p),
-                           static_cast<const uint64_t*>(x.w_unpack_tri.p), x.t_unpack, rb, nullptr,
-                           cp.d_scal.p, dc.aux);
-                tm.stop();
-            }
-            if (x.s_unpack.n_items) {  // the round's unpack list of a scaled plan
-                HIP_CHECK(hipStreamWaitEvent(dc.aux, dc.ev_moved[size_t(r)], 0));
-                tm.start(PH_UNPACK, dc.aux);
-                launch_scaled(p.pkg_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(x.d_unpack_sc.p),
-                              static_cast<const uint64_t*>(x.w_unpack_sc.p), x.s_unpack, rb, nullptr,
-                              cp.d_scal.p, row_scale, col_scale, row_amax, col_amax, dc.aux);
-                tm.stop();
-            }
-        }
+        for (int r = 0; r < R; ++r)
+            launch_unpack_round(cp, *cp.rounds[size_t(r)], rb, sv, tm, dc.aux, dc.ev_moved[size_t(r)]);
         // the call ends on main once LOCAL, every unpack and every round of the exchange are done
         HIP_CHECK(hipEventRecord(dc.ev_local, dc.aux));
         HIP_CHECK(hipStreamWaitEvent(dc.main, dc.ev_local, 0));
@@ -2634,34 +2823,11 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
     }
 
     g_stats.transforms++;
-    auto count_items = [&](const work_split& w) {
-        g_stats.tile_items += w.n_large + w.n_medium;
-        g_stats.skew_items += w.n_skew;
-        g_stats.cblock_items += w.n_cblock;
-        g_stats.tiny_items += w.n_tiny;
-        if (!dtype_is_complex(p.dtype) && pieces_in_group_launch(w.n_cblock, w.n_tiny))
-            g_stats.fused_pieces += w.n_tiny;
-    };
-    g_stats.tri_items += cp.t_local.n_items;
-    g_scaled_items += cp.s_local.n_items;
-    if (amax) g_amax_items += cp.s_local.n_items;
-    if (cp.l_local.n_items() || cp.c_local.n_items || cp.t_local.n_items || cp.s_local.n_items) {
-        g_stats.local_launches++;
-        g_stats.local_bytes += p.local_bytes;
-        count_items(cp.l_local);
-        g_stats.convert_items += cp.c_local.n_items;
-    }
+    count_local(cp, amax);
     if (exchange) {
         for (const auto& x : cp.rounds) {
-            g_stats.pack_launches += x->l_pack.n_items() || x->c_pack.n_items ? 1 : 0;
-            g_stats.unpack_launches +=
-                x->l_unpack.n_items() || x->c_unpack.n_items || x->t_unpack.n_items || x->s_unpack.n_items ? 1 : 0;
-            g_stats.tri_items += x->t_unpack.n_items;
-            g_scaled_items += x->s_unpack.n_items;
-            if (amax) g_amax_items += x->s_unpack.n_items;
-            count_items(x->l_pack);
-            count_items(x->l_unpack);
-            g_stats.convert_items += x->c_pack.n_items + x->c_unpack.n_items;
+            count_pack_round(cp, *x);
+            count_unpack_round(cp, *x, amax);
         }
         g_stats.pack_bytes += p.pack_bytes;
         g_stats.unpack_bytes += p.unpack_bytes;

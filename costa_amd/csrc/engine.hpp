@@ -199,6 +199,11 @@ size_t max_message_bytes();
 // parts a peer's package (of at least 16 MiB) is exchanged in, each its own RCCL group, so that
 // pack, exchange and unpack overlap (COSTA_EXCHANGE_ROUNDS, default 4; every rank must agree)
 int exchange_rounds();
+// the threshold in bytes (16 MiB; COSTA_ROUND_MIN_BYTES, a tuning override for the GPU tests)
+size_t round_min_bytes();
+// element range [lo, hi) of round r of R of a package of n elements of E bytes (one part below the
+// threshold; empty at n past its parts)
+void round_range(int64_t n, size_t E, int R, int r, int64_t& lo, int64_t& hi);
 
 // normalise one copy_and_transform call (memory_utils.hpp:339-412) into a tile op
 costa_tile_op_t make_tile_op(int n_rows, int n_cols, uint64_t src, int src_stride, bool src_cm,
@@ -218,6 +223,10 @@ int rccl_version();  // ncclGetVersion of the RCCL this process loaded
 struct comm;
 struct comm* comm_self(int device);
 struct comm* comm_create(const unsigned char* id, int nranks, int rank, int device);
+// rank emulation (test mode, costa_hip.h): a communicator planned like an RCCL one of that rank and
+// size, whose transforms launch one selected part against the caller's package
+struct comm* comm_emulated(int rank, int nranks, int device);
+void comm_emulate(struct comm* c, int part, int round, void* buffer);
 void comm_unique_id(unsigned char* out);
 int comm_rank(const struct comm* c);
 int comm_size(const struct comm* c);

@@ -190,6 +190,45 @@ int costa_hip_comm_rank(costa_comm_t comm);
 int costa_hip_comm_size(costa_comm_t comm);
 void costa_hip_comm_destroy(costa_comm_t comm);
 
+/* ---- test modes: the exchange path of several ranks on one GPU ----
+ * COSTA_LOOPBACK=1 or 2 (environment): a one-rank communicator gets a one-rank RCCL communicator
+ * and routes its own tiles (all, or half of them) through PACK -> ncclSend / ncclRecv to itself
+ * -> UNPACK.  One rank's geometry, one peer, displacement 0.
+ *
+ * Rank emulation: the plans and work lists of rank `rank` of `nranks`, without RCCL.
+ * costa_hip_comm_emulated makes a communicator that is planned exactly like an RCCL communicator
+ * of that rank and size (exchange rounds, pack / unpack lists, plan-cache key).
+ * costa_hip_comm_emulate selects what the following transform calls on it launch:
+ *   COSTA_EMULATE_PACK    round `round`'s pack lists, into `buffer`, the caller's send package;
+ *   COSTA_EMULATE_UNPACK  round `round`'s unpack lists (the triangular and scaled ones included),
+ *                         from `buffer`, the caller's receive package;
+ *   COSTA_EMULATE_LOCAL   the LOCAL lists (`round` and `buffer` are ignored).
+ * `round` is 0 .. costa_hip_exchange_rounds() - 1, or -1 for every round in order.  `buffer` is a
+ * device pointer aligned to 256 bytes that holds the plan's send_elems / recv_elems package
+ * elements (costa_hip_plan_export*), else COSTA_ERR_ARG.  Each call uploads the scalars, launches
+ * the part with the functions every transform uses and synchronises.  The caller is the exchange:
+ * between PACK(r) and UNPACK(r) it copies, for every pair of ranks, the element range
+ * costa_hip_round_range gives for the pair's count, from the sender's package at the pair's send
+ * displacement to the receiver's at its receive displacement (tests/emulated_ranks.py).  Every
+ * transform entry point works; COSTA_ERR_ARG for an emulated communicator with no part selected,
+ * for host-resident layouts, for the _async forms, and from costa_hip_comm_emulate for a
+ * communicator that is not emulated.  Statistics: launches and items are counted per call, the
+ * plan's pack_bytes / unpack_bytes with the last round, `transforms` with LOCAL.
+ *
+ * costa_hip_exchange_rounds: the parts a peer's package of at least 16 MiB is exchanged in
+ * (COSTA_EXCHANGE_ROUNDS, default 4).  costa_hip_round_range: the element range [lo, hi) that
+ * round `round` of `rounds` moves of a package of `count` elements of `elem_bytes` bytes (one part
+ * below the threshold; rounds past the parts are empty at `count`).  Both are host-only.  The
+ * threshold has a tuning override, COSTA_ROUND_MIN_BYTES (read only with COSTA_TUNING=1). */
+#define COSTA_EMULATE_PACK 1
+#define COSTA_EMULATE_UNPACK 2
+#define COSTA_EMULATE_LOCAL 3
+int costa_hip_comm_emulated(int rank, int nranks, int device, costa_comm_t* out);
+int costa_hip_comm_emulate(costa_comm_t comm, int part, int round, void* buffer);
+int costa_hip_exchange_rounds(void);
+int costa_hip_round_range(int64_t count, int elem_bytes, int rounds, int round, int64_t* lo,
+                          int64_t* hi);
+
 /* ---- transforms: sub(C) = beta*sub(C) + alpha*op(sub(A)), op in {'N','T','C'} ----
  * alpha/beta point to ONE element of the layouts' dtype (complex: two reals).
  * Collective over `comm`; blocking (returns after C is complete).
