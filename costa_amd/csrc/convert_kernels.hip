@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "engine.hpp"
+#include "strip_launch.hpp"
 #include "tile_device.hpp"
 
 #pragma clang fp contract(off)
@@ -373,106 +374,37 @@ __global__ __launch_bounds__((cshape<Ts, Td>::NT)) void convert_kernel(const cos
 }
 
 template <typename Ts, typename Td>
-void launch_pair(const costa_tile_op_t* d_ops, const uint64_t* d_work, const convert_list& l,
+void launch_pair(const costa_tile_op_t* d_ops, const uint64_t* d_work, const strip_list& l,
                  const char* src_base, char* dst_base, const void* d_scalars, hipStream_t stream) {
     using S = cshape<Ts, Td>;
-    const int64_t max_grid = 1LL << 30;
-    // copy-only lists need no LDS tile: more workgroups per CU
-    const size_t lds = l.any_transpose ? S::lds_bytes : 0;
-    static const bool once = [] {  // sub-tiles over the default dynamic-LDS limit
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&convert_kernel<Ts, Td>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, int(S::lds_bytes));
-        return true;
-    }();
-    (void)once;
-    for (int64_t off = 0; off < l.n_items; off += max_grid) {
-        const int64_t m = std::min(max_grid, l.n_items - off);
-        hipLaunchKernelGGL((convert_kernel<Ts, Td>), dim3(unsigned(m)), dim3(S::NT), lds, stream, d_ops,
-                           d_work + off, src_base, dst_base, static_cast<const Td*>(d_scalars));
-    }
+    launch_strip<&convert_kernel<Ts, Td>, S::lds_bytes>("convert", S::NT, l, stream, d_ops, d_work, src_base,
+                                                        dst_base, static_cast<const Td*>(d_scalars));
 }
 
-}  // namespace
-
-void convert_subtile(costa_dtype_t src, costa_dtype_t dst, int* bf, int* bs) {
-    if (half_pair(src, dst)) return half_subtile(bf, bs);
-    if (fp8_pair(src, dst)) return fp8_subtile(bf, bs);
-    if (!convertible(src, dst))
-        throw error(COSTA_ERR_ARG, std::string("costa: no converting kernel for ") + dtype_name(src) +
-                                       " -> " + dtype_name(dst));
+void wide_subtile(costa_dtype_t src, costa_dtype_t dst, int* bf, int* bs) {
     const bool cplx = dtype_is_complex(src);
     *bf = cplx ? conv_dims<8>::BF : conv_dims<4>::BF;
     *bs = cplx ? conv_dims<8>::BS : conv_dims<4>::BS;
 }
 
-bool convertible(costa_dtype_t src, costa_dtype_t dst) {
-    return half_pair(src, dst) || fp8_pair(src, dst) || (src == COSTA_FLOAT && dst == COSTA_DOUBLE) || (src == COSTA_DOUBLE && dst == COSTA_FLOAT) ||
-           (src == COSTA_CFLOAT && dst == COSTA_CDOUBLE) || (src == COSTA_CDOUBLE && dst == COSTA_CFLOAT);
-}
-
-convert_list build_convert_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
-                                const std::vector<costa_tile_op_t>& ops, uint64_t src_base,
-                                uint64_t dst_base, std::vector<costa_tile_op_t>& ordered,
-                                std::vector<uint64_t>& work) {
-    int bf = 0, bs = 0;
-    convert_subtile(src_dtype, dst_dtype, &bf, &bs);
-    const uint64_t es = dtype_size(src_dtype), ed = dtype_size(dst_dtype);
-    convert_list l;
-    ordered.clear();
-    work.clear();
-    ordered.reserve(ops.size());
-    for (const costa_tile_op_t& in : ops) {
-        if (in.nf <= 0 || in.ns <= 0) continue;
-        if (in.lds < 0 || in.ldd < 0) throw error(COSTA_ERR_ARG, "costa: negative leading dimension");
-        costa_tile_op_t op = in;
-        op.flags &= ~uint32_t(COSTA_TILE_VEC_SRC | COSTA_TILE_VEC_DST);
-        // a side may use vector accesses when it is aligned to its strip: 16 bytes on the side of
-        // the wider type, 8 on the other (half pairs: 8 on a 2-byte side, 16 on an fp32 side)
-        // (FP8 pairs: 16 on both sides of Q -> Q; with FLOAT, 4 on the 1-byte side, 16 on the fp32 side)
-        uint64_t as = es > ed ? 16 : 8, ad = ed > es ? 16 : 8;
-        if (es == 1 || ed == 1) {
-            as = es == 1 && ed != 1 ? 4 : 16;
-            ad = ed == 1 && es != 1 ? 4 : 16;
-        }
-        if ((src_base + op.src) % as == 0 && (uint64_t(op.lds) * es) % as == 0) op.flags |= COSTA_TILE_VEC_SRC;
-        if ((dst_base + op.dst) % ad == 0 && (uint64_t(op.ldd) * ed) % ad == 0) op.flags |= COSTA_TILE_VEC_DST;
-        if (op.flags & COSTA_TILE_TRANSPOSE) l.any_transpose = true;
-        const uint64_t idx = ordered.size();
-        const uint64_t nbf = (uint64_t(op.nf) + uint64_t(bf) - 1) / uint64_t(bf);
-        const uint64_t nbs = (uint64_t(op.ns) + uint64_t(bs) - 1) / uint64_t(bs);
-        if (idx >> 32 || (nbf * nbs) >> 32)
-            throw error(COSTA_ERR_ARG, "costa: converting list too long for its work items");
-        ordered.push_back(op);
-        for (uint64_t sub = 0; sub < nbf * nbs; ++sub) work.push_back(idx << 32 | sub);
-    }
-    l.n_items = int64_t(work.size());
-    return l;
-}
-
-void launch_convert(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_tile_op_t* d_ops,
-                    const uint64_t* d_work, const convert_list& l, const char* src_base,
-                    char* dst_base, const void* d_scalars, void* stream) {
-    if (l.n_items <= 0) return;
-    if (half_pair(src_dtype, dst_dtype))
-        return launch_half(src_dtype, dst_dtype, d_ops, d_work, l, src_base, dst_base, d_scalars, stream);
-    if (fp8_pair(src_dtype, dst_dtype))
-        return launch_fp8(src_dtype, dst_dtype, d_ops, d_work, l, src_base, dst_base, d_scalars, stream);
+void launch_wide(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_tile_op_t* d_ops,
+                 const uint64_t* d_work, const strip_list& l, const char* src_base, char* dst_base,
+                 const void* d_scalars, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (src_dtype == COSTA_DOUBLE && dst_dtype == COSTA_FLOAT)
+    if (src_dtype == COSTA_DOUBLE)
         launch_pair<double, float>(d_ops, d_work, l, src_base, dst_base, d_scalars, s);
-    else if (src_dtype == COSTA_FLOAT && dst_dtype == COSTA_DOUBLE)
+    else if (src_dtype == COSTA_FLOAT)
         launch_pair<float, double>(d_ops, d_work, l, src_base, dst_base, d_scalars, s);
-    else if (src_dtype == COSTA_CDOUBLE && dst_dtype == COSTA_CFLOAT)
+    else if (src_dtype == COSTA_CDOUBLE)
         launch_pair<cpx<double>, cpx<float>>(d_ops, d_work, l, src_base, dst_base, d_scalars, s);
-    else if (src_dtype == COSTA_CFLOAT && dst_dtype == COSTA_CDOUBLE)
-        launch_pair<cpx<float>, cpx<double>>(d_ops, d_work, l, src_base, dst_base, d_scalars, s);
     else
-        throw error(COSTA_ERR_ARG, std::string("costa: no converting kernel for ") +
-                                       dtype_name(src_dtype) + " -> " + dtype_name(dst_dtype));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        throw error(COSTA_ERR_HIP, std::string("convert kernel launch failed: ") + hipGetErrorString(e));
+        launch_pair<cpx<float>, cpx<double>>(d_ops, d_work, l, src_base, dst_base, d_scalars, s);
 }
+
+}  // namespace
+
+// (reached through the pair table of engine.cpp: wide_pair(src, dst) holds)
+pair_family wide_family() { return {wide_pair, wide_subtile, launch_wide}; }
 
 }  // namespace engine
 }  // namespace costa

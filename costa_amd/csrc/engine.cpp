@@ -10,6 +10,7 @@
 #include <exception>
 #include <thread>
 #include "engine.hpp"
+#include "strip_work.hpp"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -1831,24 +1832,24 @@ struct cached_plan {
     dbuf d_local, w_local, d_scal;
     work_split l_local;                     // how the work list splits over the kernel shapes
     bool tr_local = true, ax_local = true;  // any op of the list transposes / reads C
-    // converting lists of a mixed-precision plan (convert_kernels.hip) have a convert_list instead
+    // converting lists of a mixed-precision plan (convert_kernels.hip) have a strip_list instead
     // of a work_split: LOCAL; PACK of a narrowing pair; UNPACK of a widening pair
-    convert_list c_local;
+    strip_list c_local;
     // edge tiles of a triangular plan (tri_kernels.hip): LOCAL, and UNPACK per exchange round
     dbuf d_local_tri, w_local_tri;
-    tri_list t_local;
+    strip_list t_local;
     // the lists of a scaled plan (scaled_kernels.hip): LOCAL, and UNPACK per exchange round
     dbuf d_local_sc, w_local_sc;
-    scaled_list s_local;
+    strip_list s_local;
     struct xround {  // one exchange round: its pack ops (by their first element) and unpack
                      // ops (by their last element)
         dbuf d_pack, w_pack, d_unpack, w_unpack;
         work_split l_pack, l_unpack;
-        convert_list c_pack, c_unpack;
+        strip_list c_pack, c_unpack;
         dbuf d_unpack_tri, w_unpack_tri;
-        tri_list t_unpack;
+        strip_list t_unpack;
         dbuf d_unpack_sc, w_unpack_sc;
-        scaled_list s_unpack;
+        strip_list s_unpack;
         bool tr_unpack = false, ax_unpack = false;
     };
     std::vector<std::unique_ptr<xround>> rounds;
@@ -2876,6 +2877,69 @@ void execute_tiles(costa_dtype_t dtype, const costa_tile_op_t* ops, int64_t n,
     HIP_CHECK(hipStreamSynchronize(dc.main));
 }
 
+// ---------------------------------------------------------------- converting lists: the pair table
+namespace {
+const pair_family& family_of(costa_dtype_t src, costa_dtype_t dst) {  // every converting pair has one kernel family
+    static const pair_family table[] = {half_family(), fp8_family(), wide_family()};
+    for (const pair_family& f : table)
+        if (f.has(src, dst)) return f;
+    throw error(COSTA_ERR_ARG, std::string("costa: no converting kernel for ") + dtype_name(src) + " -> " +
+                                   dtype_name(dst));
+}
+}  // namespace
+
+void convert_subtile(costa_dtype_t src, costa_dtype_t dst, int* bf, int* bs) {
+    family_of(src, dst).subtile(src, dst, bf, bs);
+}
+
+strip_list build_convert_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
+                              const std::vector<costa_tile_op_t>& ops, uint64_t src_base, uint64_t dst_base,
+                              std::vector<costa_tile_op_t>& ordered, std::vector<uint64_t>& work) {
+    int bf = 0, bs = 0;
+    convert_subtile(src_dtype, dst_dtype, &bf, &bs);
+    const uint64_t es = dtype_size(src_dtype), ed = dtype_size(dst_dtype);
+    return build_strip_work("converting", ops, src_base, dst_base, bf, bs, es, ed,
+                            strip_alignment(strip_family::pair, es, ed), ordered, work);
+}
+
+void launch_convert(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_tile_op_t* d_ops,
+                    const uint64_t* d_work, const strip_list& l, const char* src_base, char* dst_base,
+                    const void* d_scalars, void* stream) {
+    if (l.n_items <= 0) return;
+    family_of(src_dtype, dst_dtype).launch(src_dtype, dst_dtype, d_ops, d_work, l, src_base, dst_base, d_scalars,
+                                           stream);
+}
+
+namespace {
+// One list of a strip kernel family, run to completion (costa_hip_execute_tiles_mixed, _tri, _scaled
+// and _amax; `who` names the entry point): the ops are copied and their slots checked,
+// build(ops, ordered, work) makes the work list, list, work and the n_slots (alpha, beta) pairs of
+// `scalar_size` bytes each go to the device, launch(d_ops, d_work, list, d_scalars, stream) runs
+// them.  Returns the sub-tiles run.
+template <typename Op, typename Build, typename Launch>
+int64_t run_strip_tiles(const std::string& who, const Op* ops, int64_t n, const void* scalars, int n_slots,
+                        size_t scalar_size, int device, Build build, Launch launch) {
+    device_ctx& dc = ctx(device);
+    std::vector<Op> v(ops, ops + n);
+    for (const Op& t : v)
+        if ((tile_of(t).flags >> COSTA_SLOT_SHIFT) >= uint32_t(std::max(n_slots, 0)))
+            throw error(COSTA_ERR_ARG, who + ": scalar slot out of range");
+    std::vector<Op> ord;
+    std::vector<uint64_t> w;
+    const strip_list l = build(v, ord, w);
+    if (!l.n_items) return 0;
+    dbuf d_ops, d_work, d_scal;
+    d_ops.upload(ord, dc.main);
+    d_work.upload(w, dc.main);
+    std::vector<unsigned char> sc(static_cast<const unsigned char*>(scalars),
+                                  static_cast<const unsigned char*>(scalars) + size_t(n_slots) * 2 * scalar_size);
+    d_scal.upload(sc, dc.main);
+    launch(static_cast<const Op*>(d_ops.p), static_cast<const uint64_t*>(d_work.p), l, d_scal.p, dc.main);
+    HIP_CHECK(hipStreamSynchronize(dc.main));
+    return l.n_items;
+}
+}  // namespace
+
 void execute_tiles_mixed(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_tile_op_t* ops,
                          int64_t n, const void* src_base, void* dst_base, const void* scalars,
                          int n_slots, int device) {
@@ -2885,27 +2949,15 @@ void execute_tiles_mixed(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const
                                        dtype_name(src_dtype) + " to " + dtype_name(dst_dtype) +
                                        " (FLOAT <-> DOUBLE, CFLOAT <-> CDOUBLE, and HALF or BFLOAT16 with "
                                        "itself or FLOAT only, and FP8_E4M3 or FP8_E5M2 with itself or FLOAT)");
-    device_ctx& dc = ctx(device);
-    std::vector<costa_tile_op_t> v(ops, ops + n);
-    for (const auto& op : v)
-        if ((op.flags >> COSTA_SLOT_SHIFT) >= uint32_t(std::max(n_slots, 0)))
-            throw error(COSTA_ERR_ARG, "costa_hip_execute_tiles_mixed: scalar slot out of range");
-    std::vector<costa_tile_op_t> ord;
-    std::vector<uint64_t> w;
-    const convert_list l = build_convert_work(src_dtype, dst_dtype, v, reinterpret_cast<uintptr_t>(src_base),
-                                              reinterpret_cast<uintptr_t>(dst_base), ord, w);
-    dbuf d_ops, d_work, d_scal;
-    d_ops.upload(ord, dc.main);
-    d_work.upload(w, dc.main);
-    const size_t E = dtype_size(compute_dtype(src_dtype, dst_dtype));  // (fp32 for half pairs)
-    std::vector<unsigned char> sc(static_cast<const unsigned char*>(scalars),
-                                  static_cast<const unsigned char*>(scalars) + size_t(n_slots) * 2 * E);
-    d_scal.upload(sc, dc.main);
-    launch_convert(src_dtype, dst_dtype, static_cast<const costa_tile_op_t*>(d_ops.p),
-                   static_cast<const uint64_t*>(d_work.p), l, static_cast<const char*>(src_base),
-                   static_cast<char*>(dst_base), d_scal.p, dc.main);
-    HIP_CHECK(hipStreamSynchronize(dc.main));
-    g_stats.convert_items += l.n_items;
+    const uintptr_t sb = reinterpret_cast<uintptr_t>(src_base), db = reinterpret_cast<uintptr_t>(dst_base);
+    g_stats.convert_items += run_strip_tiles(
+        "costa_hip_execute_tiles_mixed", ops, n, scalars, n_slots,
+        dtype_size(compute_dtype(src_dtype, dst_dtype)),  // (fp32 for half pairs)
+        device, [&](const auto& v, auto& ord, auto& w) { return build_convert_work(src_dtype, dst_dtype, v, sb, db, ord, w); },
+        [&](const costa_tile_op_t* d_ops, const uint64_t* d_work, const strip_list& l, const void* d_scal, void* s) {
+            launch_convert(src_dtype, dst_dtype, d_ops, d_work, l, static_cast<const char*>(src_base),
+                           static_cast<char*>(dst_base), d_scal, s);
+        });
 }
 
 void execute_tiles_tri(costa_dtype_t dtype, const costa_tri_op_t* ops, int64_t n, const void* src_base,
@@ -2914,27 +2966,14 @@ void execute_tiles_tri(costa_dtype_t dtype, const costa_tri_op_t* ops, int64_t n
     if (dtype_is_half(dtype) || dtype_is_fp8(dtype))
         throw error(COSTA_ERR_ARG, std::string("costa_hip_execute_tiles_tri: no edge-tile kernel for ") +
                                        dtype_name(dtype));
-    device_ctx& dc = ctx(device);
-    std::vector<costa_tri_op_t> v(ops, ops + n);
-    for (const auto& t : v)
-        if ((t.op.flags >> COSTA_SLOT_SHIFT) >= uint32_t(std::max(n_slots, 0)))
-            throw error(COSTA_ERR_ARG, "costa_hip_execute_tiles_tri: scalar slot out of range");
-    std::vector<costa_tri_op_t> ord;
-    std::vector<uint64_t> w;
-    const tri_list l = build_tri_work(dtype, v, reinterpret_cast<uintptr_t>(src_base),
-                                      reinterpret_cast<uintptr_t>(dst_base), ord, w);
-    if (!l.n_items) return;
-    dbuf d_ops, d_work, d_scal;
-    d_ops.upload(ord, dc.main);
-    d_work.upload(w, dc.main);
-    const size_t E = dtype_size(dtype);
-    std::vector<unsigned char> sc(static_cast<const unsigned char*>(scalars),
-                                  static_cast<const unsigned char*>(scalars) + size_t(n_slots) * 2 * E);
-    d_scal.upload(sc, dc.main);
-    launch_tri(dtype, static_cast<const costa_tri_op_t*>(d_ops.p), static_cast<const uint64_t*>(d_work.p), l,
-               static_cast<const char*>(src_base), static_cast<char*>(dst_base), d_scal.p, dc.main);
-    HIP_CHECK(hipStreamSynchronize(dc.main));
-    g_stats.tri_items += l.n_items;
+    const uintptr_t sb = reinterpret_cast<uintptr_t>(src_base), db = reinterpret_cast<uintptr_t>(dst_base);
+    g_stats.tri_items += run_strip_tiles(
+        "costa_hip_execute_tiles_tri", ops, n, scalars, n_slots, dtype_size(dtype), device,
+        [&](const auto& v, auto& ord, auto& w) { return build_tri_work(dtype, v, sb, db, ord, w); },
+        [&](const costa_tri_op_t* d_ops, const uint64_t* d_work, const strip_list& l, const void* d_scal, void* s) {
+            launch_tri(dtype, d_ops, d_work, l, static_cast<const char*>(src_base), static_cast<char*>(dst_base),
+                       d_scal, s);
+        });
 }
 
 namespace {
@@ -2944,35 +2983,23 @@ void run_scaled_tiles(const std::string& who, costa_dtype_t src_dtype, costa_dty
                       const void* scalars, int n_slots, const void* row_scale, const void* col_scale,
                       void* row_amax, void* col_amax, int device) {
     std::lock_guard<std::recursive_mutex> lk(g_mutex);
-    device_ctx& dc = ctx(device);
+    ctx(device);  // (is_device_ptr needs the device's context)
     for (const void* v : {row_scale, col_scale})
         if (v && !is_device_ptr(v))
             throw error(COSTA_ERR_ARG, who + ": the scale vectors must be device-resident");
     for (const void* v : {row_amax, col_amax})
         if (v && !is_device_ptr(v))
             throw error(COSTA_ERR_ARG, who + ": the amax vectors must be device-resident");
-    std::vector<costa_scaled_op_t> v(ops, ops + n);
-    for (const auto& t : v)
-        if ((t.op.flags >> COSTA_SLOT_SHIFT) >= uint32_t(std::max(n_slots, 0)))
-            throw error(COSTA_ERR_ARG, who + ": scalar slot out of range");
-    std::vector<costa_scaled_op_t> ord;
-    std::vector<uint64_t> w;
-    const scaled_list l = build_scaled_work(src_dtype, dst_dtype, v, reinterpret_cast<uintptr_t>(src_base),
-                                            reinterpret_cast<uintptr_t>(dst_base), ord, w, false);
-    if (!l.n_items) return;
-    dbuf d_ops, d_work, d_scal;
-    d_ops.upload(ord, dc.main);
-    d_work.upload(w, dc.main);
-    const size_t E = dtype_size(compute_dtype(src_dtype, dst_dtype));
-    std::vector<unsigned char> sc(static_cast<const unsigned char*>(scalars),
-                                  static_cast<const unsigned char*>(scalars) + size_t(n_slots) * 2 * E);
-    d_scal.upload(sc, dc.main);
-    launch_scaled(src_dtype, dst_dtype, static_cast<const costa_scaled_op_t*>(d_ops.p),
-                  static_cast<const uint64_t*>(d_work.p), l, static_cast<const char*>(src_base),
-                  static_cast<char*>(dst_base), d_scal.p, row_scale, col_scale, row_amax, col_amax, dc.main);
-    HIP_CHECK(hipStreamSynchronize(dc.main));
-    g_scaled_items += l.n_items;
-    if (row_amax || col_amax) g_amax_items += l.n_items;
+    const uintptr_t sb = reinterpret_cast<uintptr_t>(src_base), db = reinterpret_cast<uintptr_t>(dst_base);
+    const int64_t items = run_strip_tiles(
+        who, ops, n, scalars, n_slots, dtype_size(compute_dtype(src_dtype, dst_dtype)), device,
+        [&](const auto& v, auto& ord, auto& w) { return build_scaled_work(src_dtype, dst_dtype, v, sb, db, ord, w, false); },
+        [&](const costa_scaled_op_t* d_ops, const uint64_t* d_work, const strip_list& l, const void* d_scal, void* s) {
+            launch_scaled(src_dtype, dst_dtype, d_ops, d_work, l, static_cast<const char*>(src_base),
+                          static_cast<char*>(dst_base), d_scal, row_scale, col_scale, row_amax, col_amax, s);
+        });
+    g_scaled_items += items;
+    if (row_amax || col_amax) g_amax_items += items;
 }
 }  // namespace
 
@@ -3043,7 +3070,7 @@ void layout_amax(const elayout& L, void* row_amax, void* col_amax, comm* c, void
     std::vector<costa_scaled_op_t> ord;
     std::vector<uint64_t> w;
     // (a source-only list: the destination side of build_scaled_work sees offset 0, ld 0)
-    const scaled_list l = build_scaled_work(L.dtype, L.dtype, layout_amax_ops(L), 0, 0, ord, w, false);
+    const strip_list l = build_scaled_work(L.dtype, L.dtype, layout_amax_ops(L), 0, 0, ord, w, false);
     hipStream_t user = static_cast<hipStream_t>(user_stream);
     if (user) {
         HIP_CHECK(hipEventRecord(dc.ev_user, user));

@@ -254,56 +254,55 @@ void execute_tiles_mixed(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const
                          int64_t n, const void* src_base, void* dst_base, const void* scalars,
                          int n_slots, int device);
 
-// ---- converting lists (convert_kernels.hip): dst = g(static_cast<dst type>(src)) ----
-// (half pairs -- half_pair() -- go through the same four entry points to half_kernels.hip, with
-// fp32 scalars: dst = cvt(g(w(src), w(dst))), costa_hip.h "Half precision")
-// One kernel family, one workgroup per sub-tile of one op; the work items are
-// (op index << 32) | sub-tile, as for tile_kernel, in list order.  Scale kind BITCOPY of a
-// converting op means "convert only".
-// the sub-tile of a pair: elements along the source's fast (*bf) and slow (*bs) dimension
-void convert_subtile(costa_dtype_t src, costa_dtype_t dst, int* bf, int* bs);
-struct convert_list {
+// ---- the strip kernel families (strip_work.hpp: work lists; strip_launch.hpp: their launch) ----
+// the result of their work-list builders: work items, and whether any listed op transposes (the
+// others need no LDS tile)
+struct strip_list {
     int64_t n_items = 0;
     bool any_transpose = false;
 };
-bool convertible(costa_dtype_t src, costa_dtype_t dst);  // FLOAT <-> DOUBLE, CFLOAT <-> CDOUBLE, half_pair, fp8_pair
+
+// ---- converting lists: dst = g(static_cast<dst type>(src)) ----
+// One kernel family per kind of pair, one workgroup per sub-tile of one op; the work items are
+// (op index << 32) | sub-tile, as for tile_kernel, in list order.  Scale kind BITCOPY of a
+// converting op means "convert only".  The kinds (engine.cpp, pair table): wide_pair -- FLOAT <->
+// DOUBLE, CFLOAT <-> CDOUBLE (convert_kernels.hip); half_pair (half_kernels.hip, fp32 scalars:
+// dst = cvt(g(w(src), w(dst))), costa_hip.h "Half precision"); fp8_pair (fp8_kernels.hip).
+// Each file exports its kind as a pair_family:
+struct pair_family {
+    bool (*has)(costa_dtype_t src, costa_dtype_t dst);
+    // the sub-tile of a pair: elements along the source's fast (*bf) and slow (*bs) dimension
+    void (*subtile)(costa_dtype_t src, costa_dtype_t dst, int* bf, int* bs);
+    void (*launch)(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_tile_op_t* d_ops,
+                   const uint64_t* d_work, const strip_list& l, const char* src_base, char* dst_base,
+                   const void* d_scalars, void* stream /* hipStream_t */);
+};
+bool wide_pair(costa_dtype_t src, costa_dtype_t dst);
+pair_family wide_family(), half_family(), fp8_family();
+// ... and these go to the pair's family (throwing for a pair without one):
+bool convertible(costa_dtype_t src, costa_dtype_t dst);  // wide_pair, half_pair or fp8_pair
+void convert_subtile(costa_dtype_t src, costa_dtype_t dst, int* bf, int* bs);
 // the work list of a converting list: `ordered` = the ops with each side's VEC flag set from its
 // actual address (base + offset) and element size, `work` = every sub-tile of every op
-convert_list build_convert_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
-                                const std::vector<costa_tile_op_t>& ops, uint64_t src_base,
-                                uint64_t dst_base, std::vector<costa_tile_op_t>& ordered,
-                                std::vector<uint64_t>& work);
+strip_list build_convert_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
+                              const std::vector<costa_tile_op_t>& ops, uint64_t src_base,
+                              uint64_t dst_base, std::vector<costa_tile_op_t>& ordered,
+                              std::vector<uint64_t>& work);
 void launch_convert(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_tile_op_t* d_ops,
-                    const uint64_t* d_work, const convert_list& l, const char* src_base,
+                    const uint64_t* d_work, const strip_list& l, const char* src_base,
                     char* dst_base, const void* d_scalars, void* stream /* hipStream_t */);
-
-// ---- half-precision lists (half_kernels.hip), reached through convert_subtile / launch_convert ----
-void half_subtile(int* bf, int* bs);
-void launch_half(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_tile_op_t* d_ops,
-                 const uint64_t* d_work, const convert_list& l, const char* src_base, char* dst_base,
-                 const void* d_scalars, void* stream /* hipStream_t */);
-
-// ---- FP8 lists (fp8_kernels.hip), reached through convert_subtile / launch_convert ----
-void fp8_subtile(int* bf, int* bs);
-void launch_fp8(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_tile_op_t* d_ops,
-                const uint64_t* d_work, const convert_list& l, const char* src_base, char* dst_base,
-                const void* d_scalars, void* stream /* hipStream_t */);
 
 // ---- edge tiles of triangular transforms (tri_kernels.hip) ----
 // One kernel family, tri_kernel<T>, one workgroup per sub-tile of one costa_tri_op_t; the work
 // items are (op index << 32) | (sub-tile << 1) | whole, `whole` meaning every element of the
 // sub-tile is kept.  Sub-tiles without a kept element are not listed.
 void tri_subtile(costa_dtype_t dtype, int* bf, int* bs);
-struct tri_list {
-    int64_t n_items = 0;
-    bool any_transpose = false;
-};
 // `ordered` = the ops with each side's VEC flag set from its actual address (base + offset)
-tri_list build_tri_work(costa_dtype_t dtype, const std::vector<costa_tri_op_t>& ops, uint64_t src_base,
+strip_list build_tri_work(costa_dtype_t dtype, const std::vector<costa_tri_op_t>& ops, uint64_t src_base,
                         uint64_t dst_base, std::vector<costa_tri_op_t>& ordered,
                         std::vector<uint64_t>& work);
 void launch_tri(costa_dtype_t dtype, const costa_tri_op_t* d_ops, const uint64_t* d_work,
-                const tri_list& l, const char* src_base, char* dst_base, const void* d_scalars,
+                const strip_list& l, const char* src_base, char* dst_base, const void* d_scalars,
                 void* stream /* hipStream_t */);
 void execute_tiles_tri(costa_dtype_t dtype, const costa_tri_op_t* ops, int64_t n, const void* src_base,
                        void* dst_base, const void* scalars, int n_slots, int device);
@@ -312,21 +311,17 @@ void execute_tiles_tri(costa_dtype_t dtype, const costa_tri_op_t* ops, int64_t n
 // One kernel family, scaled_kernel<Es, Ed>, one workgroup per sub-tile of one costa_scaled_op_t; the
 // work items are (op index << 32) | sub-tile.  `row_scale` / `col_scale` are kernel arguments.
 void scaled_subtile(costa_dtype_t src, costa_dtype_t dst, int* bf, int* bs);
-struct scaled_list {
-    int64_t n_items = 0;
-    bool any_transpose = false;
-};
 // `ordered` = the ops with each side's VEC flag set from its actual address (base + offset) and its
 // strip's alignment, `work` = every sub-tile of every op: in list order, or (dst_order) by the
 // address of the sub-tile's first destination element
-scaled_list build_scaled_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
-                              const std::vector<costa_scaled_op_t>& ops, uint64_t src_base,
-                              uint64_t dst_base, std::vector<costa_scaled_op_t>& ordered,
-                              std::vector<uint64_t>& work, bool dst_order);
+strip_list build_scaled_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
+                             const std::vector<costa_scaled_op_t>& ops, uint64_t src_base,
+                             uint64_t dst_base, std::vector<costa_scaled_op_t>& ordered,
+                             std::vector<uint64_t>& work, bool dst_order);
 // (row_amax / col_amax: the amax outputs, device arrays of the compute type's unsigned integer; with
 // one of them the list runs on the AMAX instantiation, with neither on today's kernels)
 void launch_scaled(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* d_ops,
-                   const uint64_t* d_work, const scaled_list& l, const char* src_base, char* dst_base,
+                   const uint64_t* d_work, const strip_list& l, const char* src_base, char* dst_base,
                    const void* d_scalars, const void* row_scale, const void* col_scale, void* row_amax,
                    void* col_amax, void* stream /* hipStream_t */);
 void execute_tiles_scaled(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* ops,

@@ -42,6 +42,7 @@
 #include <type_traits>
 
 #include "engine.hpp"
+#include "strip_launch.hpp"
 #include "tile_device.hpp"
 
 #pragma clang fp contract(off)
@@ -411,57 +412,41 @@ __global__ __launch_bounds__(QNT) void fp8_kernel(const costa_tile_op_t* __restr
 }
 
 template <typename Q, bool SRC_F, bool DST_F>
-void launch_qpair(const costa_tile_op_t* d_ops, const uint64_t* d_work, const convert_list& l,
+void launch_qpair(const costa_tile_op_t* d_ops, const uint64_t* d_work, const strip_list& l,
                   const char* src_base, char* dst_base, const void* d_scalars, hipStream_t stream) {
-    const int64_t max_grid = 1LL << 30;
-    // copy-only lists need no LDS tile: more workgroups per CU
-    const size_t lds = !l.any_transpose ? 0 : SRC_F ? kFp8LdsF : kFp8LdsQ;
-    static const bool once = [] {  // the fp32 tile is over the default dynamic-LDS limit
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fp8_kernel<Q, SRC_F, DST_F>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  int(SRC_F ? kFp8LdsF : kFp8LdsQ));
-        return true;
-    }();
-    (void)once;
-    for (int64_t off = 0; off < l.n_items; off += max_grid) {
-        const int64_t m = std::min(max_grid, l.n_items - off);
-        hipLaunchKernelGGL((fp8_kernel<Q, SRC_F, DST_F>), dim3(unsigned(m)), dim3(QNT), lds, stream, d_ops,
-                           d_work + off, src_base, dst_base, static_cast<const float*>(d_scalars));
-    }
+    // (the fp32 tile is over the default dynamic-LDS limit)
+    launch_strip<&fp8_kernel<Q, SRC_F, DST_F>, (SRC_F ? kFp8LdsF : kFp8LdsQ)>(
+        "fp8", QNT, l, stream, d_ops, d_work, src_base, dst_base, static_cast<const float*>(d_scalars));
 }
 
 template <typename Q>
 void launch_q(bool src_f, bool dst_f, const costa_tile_op_t* d_ops, const uint64_t* d_work,
-              const convert_list& l, const char* src_base, char* dst_base, const void* d_scalars,
+              const strip_list& l, const char* src_base, char* dst_base, const void* d_scalars,
               hipStream_t s) {
     if (src_f) launch_qpair<Q, true, false>(d_ops, d_work, l, src_base, dst_base, d_scalars, s);
     else if (dst_f) launch_qpair<Q, false, true>(d_ops, d_work, l, src_base, dst_base, d_scalars, s);
     else launch_qpair<Q, false, false>(d_ops, d_work, l, src_base, dst_base, d_scalars, s);
 }
 
-}  // namespace
-
-void fp8_subtile(int* bf, int* bs) {
+void fp8_subtile(costa_dtype_t, costa_dtype_t, int* bf, int* bs) {
     *bf = QBF;
     *bs = QBS;
 }
 
 void launch_fp8(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_tile_op_t* d_ops,
-                const uint64_t* d_work, const convert_list& l, const char* src_base, char* dst_base,
+                const uint64_t* d_work, const strip_list& l, const char* src_base, char* dst_base,
                 const void* d_scalars, void* stream) {
-    if (l.n_items <= 0) return;
-    if (!fp8_pair(src_dtype, dst_dtype))
-        throw error(COSTA_ERR_ARG, std::string("costa: no FP8 kernel for ") + dtype_name(src_dtype) +
-                                       " -> " + dtype_name(dst_dtype));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool src_f = src_dtype == COSTA_FLOAT, dst_f = dst_dtype == COSTA_FLOAT;
     const costa_dtype_t q = src_f ? dst_dtype : src_dtype;
     if (q == COSTA_FP8_E4M3) launch_q<e4m3_t>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, s);
     else launch_q<e5m2_t>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, s);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        throw error(COSTA_ERR_HIP, std::string("fp8 kernel launch failed: ") + hipGetErrorString(e));
 }
+
+}  // namespace
+
+// (reached through the pair table of engine.cpp: fp8_pair(src, dst) holds)
+pair_family fp8_family() { return {fp8_pair, fp8_subtile, launch_fp8}; }
 
 }  // namespace engine
 }  // namespace costa

@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "engine.hpp"
+#include "strip_launch.hpp"
 #include "tile_device.hpp"
 
 #pragma clang fp contract(off)
@@ -303,50 +304,40 @@ __global__ __launch_bounds__(HNT) void half_kernel(const costa_tile_op_t* __rest
 }
 
 template <typename H, bool SRC_F, bool DST_F>
-void launch_hpair(const costa_tile_op_t* d_ops, const uint64_t* d_work, const convert_list& l,
+void launch_hpair(const costa_tile_op_t* d_ops, const uint64_t* d_work, const strip_list& l,
                   const char* src_base, char* dst_base, const void* d_scalars, hipStream_t stream) {
-    const int64_t max_grid = 1LL << 30;
-    // copy-only lists need no LDS tile: more workgroups per CU
-    const size_t lds = l.any_transpose ? kHalfLds : 0;
-    for (int64_t off = 0; off < l.n_items; off += max_grid) {
-        const int64_t m = std::min(max_grid, l.n_items - off);
-        hipLaunchKernelGGL((half_kernel<H, SRC_F, DST_F>), dim3(unsigned(m)), dim3(HNT), lds, stream, d_ops,
-                           d_work + off, src_base, dst_base, static_cast<const float*>(d_scalars));
-    }
+    launch_strip<&half_kernel<H, SRC_F, DST_F>, kHalfLds>("half", HNT, l, stream, d_ops, d_work, src_base, dst_base,
+                                                          static_cast<const float*>(d_scalars));
 }
 
 template <typename H>
 void launch_h(bool src_f, bool dst_f, const costa_tile_op_t* d_ops, const uint64_t* d_work,
-              const convert_list& l, const char* src_base, char* dst_base, const void* d_scalars,
+              const strip_list& l, const char* src_base, char* dst_base, const void* d_scalars,
               hipStream_t s) {
     if (src_f) launch_hpair<H, true, false>(d_ops, d_work, l, src_base, dst_base, d_scalars, s);
     else if (dst_f) launch_hpair<H, false, true>(d_ops, d_work, l, src_base, dst_base, d_scalars, s);
     else launch_hpair<H, false, false>(d_ops, d_work, l, src_base, dst_base, d_scalars, s);
 }
 
-}  // namespace
-
-void half_subtile(int* bf, int* bs) {
+void half_subtile(costa_dtype_t, costa_dtype_t, int* bf, int* bs) {
     *bf = HBF;
     *bs = HBS;
 }
 
 void launch_half(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_tile_op_t* d_ops,
-                 const uint64_t* d_work, const convert_list& l, const char* src_base, char* dst_base,
+                 const uint64_t* d_work, const strip_list& l, const char* src_base, char* dst_base,
                  const void* d_scalars, void* stream) {
-    if (l.n_items <= 0) return;
-    if (!half_pair(src_dtype, dst_dtype))
-        throw error(COSTA_ERR_ARG, std::string("costa: no half-precision kernel for ") +
-                                       dtype_name(src_dtype) + " -> " + dtype_name(dst_dtype));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const bool src_f = src_dtype == COSTA_FLOAT, dst_f = dst_dtype == COSTA_FLOAT;
     const costa_dtype_t h = src_f ? dst_dtype : src_dtype;
     if (h == COSTA_HALF) launch_h<f16_t>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, s);
     else launch_h<bf16_t>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, s);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        throw error(COSTA_ERR_HIP, std::string("half kernel launch failed: ") + hipGetErrorString(e));
 }
+
+}  // namespace
+
+// (reached through the pair table of engine.cpp: half_pair(src, dst) holds)
+pair_family half_family() { return {half_pair, half_subtile, launch_half}; }
 
 }  // namespace engine
 }  // namespace costa

@@ -62,6 +62,15 @@ bool fp8_pair(costa_dtype_t src, costa_dtype_t dst) {
            (src == COSTA_FLOAT && dtype_is_fp8(dst));
 }
 
+bool wide_pair(costa_dtype_t src, costa_dtype_t dst) {
+    return (src == COSTA_FLOAT && dst == COSTA_DOUBLE) || (src == COSTA_DOUBLE && dst == COSTA_FLOAT) ||
+           (src == COSTA_CFLOAT && dst == COSTA_CDOUBLE) || (src == COSTA_CDOUBLE && dst == COSTA_CFLOAT);
+}
+
+bool convertible(costa_dtype_t src, costa_dtype_t dst) {
+    return half_pair(src, dst) || fp8_pair(src, dst) || wide_pair(src, dst);
+}
+
 const char* dtype_name(costa_dtype_t t) {
     switch (t) {
     case COSTA_FLOAT: return "FLOAT";

@@ -86,6 +86,8 @@
 #include <utility>
 
 #include "engine.hpp"
+#include "strip_launch.hpp"
+#include "strip_work.hpp"
 #include "tile_device.hpp"
 
 #pragma clang fp contract(off)
@@ -680,34 +682,19 @@ struct scaled_vecs {
 };
 
 template <typename Es, typename Ed, bool AMAX>
-void launch_inst(const costa_scaled_op_t* d_ops, const uint64_t* d_work, const scaled_list& l,
+void launch_inst(const costa_scaled_op_t* d_ops, const uint64_t* d_work, const strip_list& l,
                  const char* src_base, char* dst_base, const void* d_scalars, const scaled_vecs& v,
                  hipStream_t stream) {
     using C = typename Ed::ct;
     using U = typename ubits<C>::type;
-    const int64_t max_grid = 1LL << 30;
-    // copy-only lists need no LDS tile: more workgroups per CU
-    const size_t lds = l.any_transpose ? sshape<C>::lds_bytes : 0;
-    if (sshape<C>::lds_bytes > 64 * 1024) {  // (tuning builds: over the default dynamic-LDS limit)
-        static const bool once = [] {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&scaled_kernel<Es, Ed, AMAX>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, int(sshape<C>::lds_bytes));
-            return true;
-        }();
-        (void)once;
-    }
-    for (int64_t off = 0; off < l.n_items; off += max_grid) {
-        const int64_t m = std::min(max_grid, l.n_items - off);
-        hipLaunchKernelGGL((scaled_kernel<Es, Ed, AMAX>), dim3(unsigned(m)), dim3(SNT), lds, stream, d_ops,
-                           d_work + off, src_base, dst_base, static_cast<const C*>(d_scalars),
-                           static_cast<const C*>(v.rs), static_cast<const C*>(v.cs), static_cast<U*>(v.ra),
-                           static_cast<U*>(v.ca));
-    }
+    launch_strip<&scaled_kernel<Es, Ed, AMAX>, sshape<C>::lds_bytes>(
+        "scaled", SNT, l, stream, d_ops, d_work, src_base, dst_base, static_cast<const C*>(d_scalars),
+        static_cast<const C*>(v.rs), static_cast<const C*>(v.cs), static_cast<U*>(v.ra), static_cast<U*>(v.ca));
 }
 
 // the AMAX instantiation runs only where an amax vector is given
 template <typename Es, typename Ed>
-void launch_pair(const costa_scaled_op_t* d_ops, const uint64_t* d_work, const scaled_list& l,
+void launch_pair(const costa_scaled_op_t* d_ops, const uint64_t* d_work, const strip_list& l,
                  const char* src_base, char* dst_base, const void* d_scalars, const scaled_vecs& v,
                  hipStream_t stream) {
     if (!v.ra && !v.ca)
@@ -721,7 +708,7 @@ void launch_pair(const costa_scaled_op_t* d_ops, const uint64_t* d_work, const s
 // N: f16_t / bf16_t / e4m3_t / e5m2_t; ROUND: a FLOAT source is rounded to N first (the half pairs)
 template <typename N, template <typename> class narrow_e, bool ROUND>
 void launch_narrow(bool src_f, bool dst_f, const costa_scaled_op_t* d_ops,
-                   const uint64_t* d_work, const scaled_list& l, const char* src_base, char* dst_base,
+                   const uint64_t* d_work, const strip_list& l, const char* src_base, char* dst_base,
                    const void* d_scalars, const scaled_vecs& v, hipStream_t s) {
     using src_e = typename std::conditional<ROUND, f32_via<N>, f32_e>::type;
     if (src_f)
@@ -737,19 +724,12 @@ void launch_amax_of(const costa_scaled_op_t* d_ops, const uint64_t* d_work, int6
                     void* ca, hipStream_t stream) {
     if constexpr (AMAX_SHAPE) {
         using U = typename ubits<typename Es::ct>::type;
-        const int64_t max_grid = 1LL << 30;
-        for (int64_t off = 0; off < n_items; off += max_grid) {
-            const int64_t m = std::min(max_grid, n_items - off);
-            hipLaunchKernelGGL((amax_kernel<Es>), dim3(unsigned(m)), dim3(SNT), 0, stream, d_ops, d_work + off,
-                               static_cast<const char*>(nullptr), static_cast<U*>(ra), static_cast<U*>(ca));
-        }
+        launch_strip<&amax_kernel<Es>, 0>("amax", SNT, strip_list{n_items, false}, stream, d_ops, d_work,
+                                          static_cast<const char*>(nullptr), static_cast<U*>(ra), static_cast<U*>(ca));
     } else {
         throw error(COSTA_ERR_ARG, "costa: this build's scaled sub-tile has no amax reduction");
     }
 }
-
-// bytes a side must be aligned to for vector accesses: its strip of 4 elements, 16 at most
-uint64_t strip_align(costa_dtype_t t) { return std::min<uint64_t>(16, 4 * dtype_size(t)); }
 
 }  // namespace
 
@@ -761,55 +741,22 @@ void scaled_subtile(costa_dtype_t src, costa_dtype_t dst, int* bf, int* bs) {
     *bs = SBS;
 }
 
-scaled_list build_scaled_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
-                              const std::vector<costa_scaled_op_t>& ops, uint64_t src_base,
-                              uint64_t dst_base, std::vector<costa_scaled_op_t>& ordered,
-                              std::vector<uint64_t>& work, bool dst_order) {
-    const int64_t bf = SBF, bs = SBS;
+strip_list build_scaled_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
+                             const std::vector<costa_scaled_op_t>& ops, uint64_t src_base,
+                             uint64_t dst_base, std::vector<costa_scaled_op_t>& ordered,
+                             std::vector<uint64_t>& work, bool dst_order) {
     const uint64_t ES = dtype_size(src_dtype), ED = dtype_size(dst_dtype);
-    const uint64_t AS = strip_align(src_dtype), AD = strip_align(dst_dtype);
-    scaled_list l;
-    ordered.clear();
-    work.clear();
-    ordered.reserve(ops.size());
-    for (const costa_scaled_op_t& in : ops) {
-        if (in.op.nf <= 0 || in.op.ns <= 0) continue;
-        if (in.op.lds < 0 || in.op.ldd < 0) throw error(COSTA_ERR_ARG, "costa: negative leading dimension");
-        if (in.row0 < 0 || in.col0 < 0) throw error(COSTA_ERR_ARG, "costa: negative target coordinate");
-        costa_scaled_op_t t = in;
-        costa_tile_op_t& op = t.op;
-        op.flags &= ~uint32_t(COSTA_TILE_VEC_SRC | COSTA_TILE_VEC_DST);
-        if ((src_base + op.src) % AS == 0 && (uint64_t(op.lds) * ES) % AS == 0) op.flags |= COSTA_TILE_VEC_SRC;
-        if ((dst_base + op.dst) % AD == 0 && (uint64_t(op.ldd) * ED) % AD == 0) op.flags |= COSTA_TILE_VEC_DST;
-        const uint64_t idx = ordered.size();
-        const int64_t nbf = (int64_t(op.nf) + bf - 1) / bf, nbs = (int64_t(op.ns) + bs - 1) / bs;
-        if (idx >> 32 || (nbf * nbs) >> 32)
-            throw error(COSTA_ERR_ARG, "costa: scaled list too long for its work items");
-        ordered.push_back(t);
-        if (op.flags & COSTA_TILE_TRANSPOSE) l.any_transpose = true;
-        for (int64_t q = 0; q < nbf * nbs; ++q) work.push_back(idx << 32 | uint64_t(q));
+    for (const costa_scaled_op_t& t : ops) {  // (empty ops are skipped unchecked, as by the builder)
+        if (t.op.nf <= 0 || t.op.ns <= 0) continue;
+        if (t.op.lds < 0 || t.op.ldd < 0) throw error(COSTA_ERR_ARG, "costa: negative leading dimension");
+        if (t.row0 < 0 || t.col0 < 0) throw error(COSTA_ERR_ARG, "costa: negative target coordinate");
     }
-    if (dst_order && work.size() > 1) {
-        // sub-tiles by the address of their first destination element (stable), as the ordinary
-        // LOCAL list of a triangular plan (engine.cpp build_work dst_order)
-        std::vector<std::pair<uint64_t, uint64_t>> key(work.size());
-        for (size_t x = 0; x < key.size(); ++x) {
-            const costa_tile_op_t& op = ordered[size_t(work[x] >> 32)].op;
-            const uint64_t q = work[x] & 0xFFFFFFFFull, nbf = uint64_t((op.nf + bf - 1) / bf);
-            const int64_t f0 = int64_t(q % nbf) * bf, s0 = int64_t(q / nbf) * bs;
-            const int64_t at = op.flags & COSTA_TILE_TRANSPOSE ? f0 * op.ldd + s0 : s0 * op.ldd + f0;
-            key[x] = {op.dst + uint64_t(at) * ED, work[x]};
-        }
-        std::stable_sort(key.begin(), key.end(),
-                         [](const auto& a, const auto& b) { return a.first < b.first; });
-        for (size_t x = 0; x < key.size(); ++x) work[x] = key[x].second;
-    }
-    l.n_items = int64_t(work.size());
-    return l;
+    return build_strip_work("scaled", ops, src_base, dst_base, SBF, SBS, ES, ED,
+                            strip_alignment(strip_family::scaled, ES, ED), ordered, work, all_listed(), dst_order);
 }
 
 void launch_scaled(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* d_ops,
-                   const uint64_t* d_work, const scaled_list& l, const char* src_base, char* dst_base,
+                   const uint64_t* d_work, const strip_list& l, const char* src_base, char* dst_base,
                    const void* d_scalars, const void* rs, const void* cs, void* row_amax, void* col_amax,
                    void* stream) {
     if (l.n_items <= 0) return;
@@ -832,9 +779,6 @@ void launch_scaled(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa
         launch_narrow<e4m3_t, q_e, false>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, v, s);
     else
         launch_narrow<e5m2_t, q_e, false>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, v, s);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        throw error(COSTA_ERR_HIP, std::string("scaled kernel launch failed: ") + hipGetErrorString(e));
 }
 
 bool amax_dtype(costa_dtype_t t) {
@@ -856,9 +800,6 @@ void launch_amax(costa_dtype_t dtype, const costa_scaled_op_t* d_ops, const uint
         throw error(COSTA_ERR_ARG, std::string("costa_hip_layout_amax: no amax of ") + dtype_name(dtype) +
                                        " (real floating-point element types only)");
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        throw error(COSTA_ERR_HIP, std::string("amax kernel launch failed: ") + hipGetErrorString(e));
 }
 
 }  // namespace engine

@@ -106,6 +106,14 @@ COSTA_HD inline costa_scaled_op_t scaled_op(const costa_tile_op_t& op, bool src_
     return t;
 }
 
+// the ordinary op inside each op type
+COSTA_HD inline const costa_tile_op_t& tile_of(const costa_tile_op_t& o) { return o; }
+COSTA_HD inline const costa_tile_op_t& tile_of(const costa_tri_op_t& o) { return o.op; }
+COSTA_HD inline const costa_tile_op_t& tile_of(const costa_scaled_op_t& o) { return o.op; }
+COSTA_HD inline costa_tile_op_t& tile_of(costa_tile_op_t& o) { return o; }
+COSTA_HD inline costa_tile_op_t& tile_of(costa_tri_op_t& o) { return o.op; }
+COSTA_HD inline costa_tile_op_t& tile_of(costa_scaled_op_t& o) { return o.op; }
+
 // kept elements of an edge op
 COSTA_HD inline int64_t tri_kept(const costa_tri_op_t& t) {
     const bool le = t.op.flags & COSTA_TRI_LE;

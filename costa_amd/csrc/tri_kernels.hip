@@ -30,6 +30,8 @@
 #include <string>
 
 #include "engine.hpp"
+#include "strip_launch.hpp"
+#include "strip_work.hpp"
 #include "tile_device.hpp"
 
 #pragma clang fp contract(off)
@@ -313,23 +315,12 @@ __global__ __launch_bounds__(kTriNT) void tri_kernel(const costa_tri_op_t* __res
 }
 
 template <typename T>
-void launch_type(const costa_tri_op_t* d_ops, const uint64_t* d_work, const tri_list& l,
+void launch_type(const costa_tri_op_t* d_ops, const uint64_t* d_work, const strip_list& l,
                  const char* src_base, char* dst_base, const void* d_scalars, hipStream_t stream) {
     using S = tshape<T>;
-    const int64_t max_grid = 1LL << 30;
-    // copy-only lists need no LDS tile: more workgroups per CU
-    const size_t lds = l.any_transpose ? S::lds_bytes : 0;
-    static const bool once = [] {  // c128's tile is over the default dynamic-LDS limit
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tri_kernel<T>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, int(S::lds_bytes));
-        return true;
-    }();
-    (void)once;
-    for (int64_t off = 0; off < l.n_items; off += max_grid) {
-        const int64_t m = std::min(max_grid, l.n_items - off);
-        hipLaunchKernelGGL((tri_kernel<T>), dim3(unsigned(m)), dim3(S::NT), lds, stream, d_ops, d_work + off,
-                           src_base, dst_base, static_cast<const T*>(d_scalars));
-    }
+    // (c128's tile is over the default dynamic-LDS limit)
+    launch_strip<&tri_kernel<T>, S::lds_bytes>("tri", S::NT, l, stream, d_ops, d_work, src_base, dst_base,
+                                               static_cast<const T*>(d_scalars));
 }
 
 }  // namespace
@@ -340,51 +331,27 @@ void tri_subtile(costa_dtype_t dtype, int* bf, int* bs) {
     *bs = kTriBS;
 }
 
-tri_list build_tri_work(costa_dtype_t dtype, const std::vector<costa_tri_op_t>& ops, uint64_t src_base,
-                        uint64_t dst_base, std::vector<costa_tri_op_t>& ordered,
-                        std::vector<uint64_t>& work) {
+strip_list build_tri_work(costa_dtype_t dtype, const std::vector<costa_tri_op_t>& ops, uint64_t src_base,
+                          uint64_t dst_base, std::vector<costa_tri_op_t>& ordered,
+                          std::vector<uint64_t>& work) {
     const int64_t bf = kTriBF, bs = kTriBS;
     const uint64_t E = dtype_size(dtype);
-    tri_list l;
-    ordered.clear();
-    work.clear();
-    ordered.reserve(ops.size());
-    for (const costa_tri_op_t& in : ops) {
-        if (in.op.nf <= 0 || in.op.ns <= 0) continue;
-        if (in.op.lds < 0 || in.op.ldd < 0) throw error(COSTA_ERR_ARG, "costa: negative leading dimension");
-        costa_tri_op_t t = in;
-        costa_tile_op_t& op = t.op;
-        op.flags &= ~uint32_t(COSTA_TILE_VEC_SRC | COSTA_TILE_VEC_DST);
-        if ((src_base + op.src) % 16 == 0 && (uint64_t(op.lds) * E) % 16 == 0) op.flags |= COSTA_TILE_VEC_SRC;
-        if ((dst_base + op.dst) % 16 == 0 && (uint64_t(op.ldd) * E) % 16 == 0) op.flags |= COSTA_TILE_VEC_DST;
-        const bool le = op.flags & COSTA_TRI_LE;
+    // a sub-tile is listed when s - f reaches the kept side of the diagonal somewhere in it, whole
+    // when everywhere
+    auto sub_of = [=](const costa_tri_op_t& t, int64_t i, int64_t j) {
+        const bool le = t.op.flags & COSTA_TRI_LE;
         const int64_t d = t.diag;
-        const uint64_t idx = ordered.size();
-        const int64_t nbf = (int64_t(op.nf) + bf - 1) / bf, nbs = (int64_t(op.ns) + bs - 1) / bs;
-        if (idx >> 32 || (nbf * nbs) >> 31)
-            throw error(COSTA_ERR_ARG, "costa: edge-tile list too long for its work items");
-        bool used = false;
-        for (int64_t j = 0; j < nbs; ++j)
-            for (int64_t i = 0; i < nbf; ++i) {
-                // s - f over the sub-tile
-                const int64_t f0 = i * bf, f1 = std::min<int64_t>(op.nf, f0 + bf) - 1;
-                const int64_t s0 = j * bs, s1 = std::min<int64_t>(op.ns, s0 + bs) - 1;
-                const int64_t v_min = s0 - f1, v_max = s1 - f0;
-                if (le ? v_min > d : v_max < d) continue;  // no kept element
-                const bool whole = le ? v_max <= d : v_min >= d;
-                if (!used) {
-                    ordered.push_back(t);
-                    used = true;
-                    if (op.flags & COSTA_TILE_TRANSPOSE) l.any_transpose = true;
-                }
-                work.push_back(idx << 32 | uint64_t(j * nbf + i) << 1 | uint64_t(whole));
-            }
-    }
-    l.n_items = int64_t(work.size());
-    return l;
+        const int64_t f0 = i * bf, f1 = std::min<int64_t>(t.op.nf, f0 + bf) - 1;
+        const int64_t s0 = j * bs, s1 = std::min<int64_t>(t.op.ns, s0 + bs) - 1;
+        const int64_t v_min = s0 - f1, v_max = s1 - f0;
+        if (le ? v_min > d : v_max < d) return strip_sub::skip;
+        return (le ? v_max <= d : v_min >= d) ? strip_sub::whole : strip_sub::listed;
+    };
+    return build_strip_work<true>("edge-tile", ops, src_base, dst_base, kTriBF, kTriBS, E, E,
+                                  strip_alignment(strip_family::tri, E, E), ordered, work, sub_of);
 }
 
-void launch_tri(costa_dtype_t dtype, const costa_tri_op_t* d_ops, const uint64_t* d_work, const tri_list& l,
+void launch_tri(costa_dtype_t dtype, const costa_tri_op_t* d_ops, const uint64_t* d_work, const strip_list& l,
                 const char* src_base, char* dst_base, const void* d_scalars, void* stream) {
     if (l.n_items <= 0) return;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -396,9 +363,6 @@ void launch_tri(costa_dtype_t dtype, const costa_tri_op_t* d_ops, const uint64_t
     case COSTA_INT32: launch_type<int>(d_ops, d_work, l, src_base, dst_base, d_scalars, s); break;
     default: throw error(COSTA_ERR_ARG, "unknown dtype");
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess)
-        throw error(COSTA_ERR_HIP, std::string("tri kernel launch failed: ") + hipGetErrorString(e));
 }
 
 }  // namespace engine

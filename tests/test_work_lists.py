@@ -51,6 +51,10 @@ def test_work_lists_cfg5(tmp_path):
     # the transposing groups' XCD chunk order is a permutation of every launch size
     r = subprocess.run([str(exe), "xcd"], capture_output=True, text=True, timeout=300, env=clean)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr
+    # the strip kernel families' lists (converting, edge-tile, scaled): VEC flags by the alignment
+    # table, every listed sub-tile once, tri's sub-tiles against a brute-force scan, dst_order sorted
+    r = subprocess.run([str(exe), "strip"], capture_output=True, text=True, timeout=300, env=clean)
+    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr
 
 
 TUNING = {"COSTA_TINY_SORT": "0", "COSTA_FORCE_SQ": "1", "COSTA_LARGE_SORT": "0", "COSTA_XCD_BANDS": "0",

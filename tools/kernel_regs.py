@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""VGPR / SGPR / scratch / LDS of every costa kernel in libcosta_amd.so (gfx950 code object
-metadata), one line each: python tools/kernel_regs.py [lib] > before.txt"""
+"""VGPR / SGPR / scratch / static LDS (group_segment_fixed_size; dynamic LDS is the launch's) of
+every costa kernel in libcosta_amd.so (gfx950 code object metadata), one line each: python tools/kernel_regs.py [lib] > before.txt"""
 import os
 import re
 import shutil
@@ -26,5 +26,6 @@ with tempfile.TemporaryDirectory() as td:
                 continue
             dm = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
             dm = dm.replace("costa::engine::(anonymous namespace)::", "").split("(costa_tile_op_t")[0]
-            rows.append(f"v{g('vgpr_count'):>4} s{g('sgpr_count'):>4} scr{g('private_segment_fixed_size'):>4} {dm}")
-        print("\n".join(sorted(rows, key=lambda r: r.split(None, 3)[3])))
+            rows.append(f"v{g('vgpr_count'):>4} s{g('sgpr_count'):>4} scr{g('private_segment_fixed_size'):>4} "
+                        f"lds{g('group_segment_fixed_size'):>6} {dm}")
+        print("\n".join(sorted(rows, key=lambda r: r.split(None, 4)[4])))

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "tile_op.hpp"
 
 using namespace costa;
 using namespace costa::engine;
@@ -619,8 +620,158 @@ static int digest() {
     return 0;
 }
 
+// ---- `work_check strip`: the work lists of the strip kernel families (strip_work.hpp) against their
+// rules, restated here.  Bytes a side must be aligned to for its VEC flag, per (source, destination)
+// element size:
+struct want_align {
+    uint64_t es, ed, as, ad;
+};
+static const want_align kPairAlign[] = {{4, 8, 8, 16},  {8, 4, 16, 8}, {8, 16, 8, 16}, {16, 8, 16, 8},  // 2:1 pairs
+                                        {2, 2, 8, 8},   {4, 2, 16, 8}, {2, 4, 8, 16},                   // half pairs
+                                        {1, 1, 16, 16}, {4, 1, 16, 4}, {1, 4, 4, 16}};                  // FP8 pairs
+static uint64_t scaled_align(uint64_t e) { return e == 1 ? 4 : e == 2 ? 8 : 16; }
+
+template <typename Op>
+static std::vector<Op> strip_ops(int bf, int bs, uint64_t es, uint64_t ed, int so, int d_o, bool tr) {
+    const int shp[][2] = {{1, 1}, {3, 5}, {bf + 1, bs + 1}, {2 * bf - 1, 7}, {7, 2 * bs - 1}, {0, 3}};
+    std::vector<Op> v;
+    uint64_t sa = 4096, da = uint64_t(1) << 24;
+    for (auto& s : shp) {
+        Op t{};
+        costa_tile_op_t& op = tile_of(t);
+        op.nf = s[0], op.ns = s[1];
+        op.lds = (s[0] + 15) / 16 * 16 + (so & 1);
+        op.ldd = ((tr ? s[1] : s[0]) + 15) / 16 * 16 + (d_o & 1);
+        op.src = sa + so * es, op.dst = da + d_o * ed;
+        op.flags = (tr ? COSTA_TILE_TRANSPOSE : 0u) | COSTA_TILE_VEC_SRC;  // (a stale flag: must be recomputed)
+        v.push_back(t);
+        sa += 1 << 20, da -= 1 << 20;  // destinations descend: dst_order has something to sort
+    }
+    return v;
+}
+
+// what every list must satisfy; `listed(op, sub)`: 0 = not listed, 1 = listed, 2 = listed as whole
+template <typename Op, typename Listed>
+static bool check_strip(const std::string& name, const std::vector<Op>& in, const std::vector<Op>& ord,
+                        const std::vector<uint64_t>& work, const strip_list& l, int bf, int bs, uint64_t es,
+                        uint64_t ed, uint64_t as, uint64_t ad, uint64_t src_base, uint64_t dst_base, int shift,
+                        Listed listed, bool dst_order) {
+    auto fail = [&](const char* what) { std::printf("FAIL strip %s: %s\n", name.c_str(), what); return false; };
+    std::map<uint64_t, int> want;  // item -> times seen
+    size_t k = 0;
+    bool tr = false;
+    for (const Op& t : in) {
+        const costa_tile_op_t& op = tile_of(t);
+        if (op.nf <= 0 || op.ns <= 0) continue;
+        const int64_t nbf = (op.nf + bf - 1) / bf, nbs = (op.ns + bs - 1) / bs;
+        bool any = false;
+        for (int64_t q = 0; q < nbf * nbs; ++q)
+            if (const int c = listed(t, int(q % nbf), int(q / nbf))) {
+                want[uint64_t(k) << 32 | uint64_t(q) << shift | uint64_t(shift && c == 2)] = 0;
+                any = true;
+            }
+        if (!any) continue;
+        if (k >= ord.size()) return fail("an op is missing");
+        const costa_tile_op_t& o = tile_of(ord[k]);
+        const uint32_t vec = COSTA_TILE_VEC_SRC | COSTA_TILE_VEC_DST;
+        if (o.src != op.src || o.dst != op.dst || o.nf != op.nf || o.ns != op.ns || (o.flags & ~vec) != (op.flags & ~vec))
+            return fail("ordered is not the listed ops in list order");
+        const bool vs = (src_base + op.src) % as == 0 && (uint64_t(op.lds) * es) % as == 0;
+        const bool vd = (dst_base + op.dst) % ad == 0 && (uint64_t(op.ldd) * ed) % ad == 0;
+        if (bool(o.flags & COSTA_TILE_VEC_SRC) != vs || bool(o.flags & COSTA_TILE_VEC_DST) != vd)
+            return fail("a VEC flag off the alignment table");
+        tr |= bool(op.flags & COSTA_TILE_TRANSPOSE);
+        ++k;
+    }
+    if (k != ord.size() || l.n_items != int64_t(work.size()) || l.any_transpose != tr) return fail("list summary");
+    uint64_t last_key = 0, last_item = 0;
+    for (size_t x = 0; x < work.size(); ++x) {
+        auto it = want.find(work[x]);
+        if (it == want.end() || it->second++) return fail("an item not expected, or listed twice");
+        uint64_t key = 0;
+        if (dst_order) {
+            const costa_tile_op_t& o = tile_of(ord[size_t(work[x] >> 32)]);
+            const int64_t q = int64_t((work[x] & 0xFFFFFFFFull) >> shift), nbf = (o.nf + bf - 1) / bf;
+            const int64_t f0 = q % nbf * bf, s0 = q / nbf * bs;
+            key = o.dst + uint64_t(o.flags & COSTA_TILE_TRANSPOSE ? f0 * o.ldd + s0 : s0 * o.ldd + f0) * ed;
+        }
+        if (x && (key < last_key || (key == last_key && work[x] < last_item)))
+            return fail(dst_order ? "not in destination-address order (stable)" : "not in list order");
+        last_key = key, last_item = work[x];
+    }
+    if (work.size() != want.size()) return fail("a sub-tile is missing");
+    return true;
+}
+
+static bool check_strips() {
+    const costa_dtype_t all[] = {COSTA_FLOAT, COSTA_DOUBLE, COSTA_CFLOAT, COSTA_CDOUBLE, COSTA_INT32,
+                                 COSTA_HALF,  COSTA_BFLOAT16, COSTA_FP8_E4M3, COSTA_FP8_E5M2};
+    auto every = [](const auto&, int, int) { return 1; };
+    for (costa_dtype_t a : all)
+        for (costa_dtype_t c : all)
+            for (int tr = 0; tr < 2; ++tr)
+                for (int so = 0; so < 4; ++so)
+                    for (int d_o = 0; d_o < 4; ++d_o) {
+                        const uint64_t es = dtype_size(a), ed = dtype_size(c), sb = so == 3 ? 2 : 0, db = d_o == 2 ? 4 : 0;
+                        const std::string name = std::string(dtype_name(a)) + " -> " + dtype_name(c) + (tr ? " T" : " N") +
+                                                 " +" + std::to_string(so) + " +" + std::to_string(d_o);
+                        std::vector<uint64_t> work;
+                        int bf, bs;
+                        if (convertible(a, c)) {
+                            const want_align* w = nullptr;
+                            for (const want_align& x : kPairAlign)
+                                if (x.es == es && x.ed == ed) w = &x;
+                            if (!w) return false;
+                            convert_subtile(a, c, &bf, &bs);
+                            const auto ops = strip_ops<costa_tile_op_t>(bf, bs, es, ed, so, d_o, tr);
+                            std::vector<costa_tile_op_t> ord;
+                            const strip_list l = build_convert_work(a, c, ops, sb, db, ord, work);
+                            if (!check_strip("pair " + name, ops, ord, work, l, bf, bs, es, ed, w->as, w->ad, sb, db, 0, every, false))
+                                return false;
+                        }
+                        if (scaled_pair(a, c))
+                            for (int by_dst = 0; by_dst < 2; ++by_dst) {
+                                scaled_subtile(a, c, &bf, &bs);
+                                auto ops = strip_ops<costa_scaled_op_t>(bf, bs, es, ed, so, d_o, tr);
+                                ops[1].op.dst = ops[3].op.dst;  // (a tie for the stable sort)
+                                std::vector<costa_scaled_op_t> ord;
+                                const strip_list l = build_scaled_work(a, c, ops, sb, db, ord, work, by_dst);
+                                if (!check_strip("scaled " + name, ops, ord, work, l, bf, bs, es, ed, scaled_align(es),
+                                                 scaled_align(ed), sb, db, 0, every, by_dst))
+                                    return false;
+                            }
+                        if (a == c && !dtype_is_half(a) && !dtype_is_fp8(a))
+                            for (int le = 0; le < 2; ++le)
+                                for (int diag : {-(1 << 30), -130, -64, -3, 0, 1, 5, 63, 70, 1 << 30}) {
+                                    tri_subtile(a, &bf, &bs);
+                                    auto ops = strip_ops<costa_tri_op_t>(bf, bs, es, ed, so, d_o, tr);
+                                    for (auto& t : ops) t.diag = diag, t.op.flags |= le ? COSTA_TRI_LE : 0u;
+                                    // brute force: a sub-tile is listed when an element of it is kept,
+                                    // whole when all are
+                                    auto scan = [&](const costa_tri_op_t& t, int i, int j) {
+                                        int64_t kept = 0, n = 0;
+                                        for (int s = j * bs; s < std::min(t.op.ns, (j + 1) * bs); ++s)
+                                            for (int f = i * bf; f < std::min(t.op.nf, (i + 1) * bf); ++f, ++n)
+                                                kept += le ? s - f <= diag : s - f >= diag;
+                                        return kept == 0 ? 0 : kept == n ? 2 : 1;
+                                    };
+                                    std::vector<costa_tri_op_t> ord;
+                                    const strip_list l = build_tri_work(a, ops, sb, db, ord, work);
+                                    if (!check_strip("tri " + name + (le ? " LE " : " GE ") + std::to_string(diag), ops, ord,
+                                                     work, l, bf, bs, es, ed, 16, 16, sb, db, 1, scan, false))
+                                        return false;
+                                }
+                    }
+    return true;
+}
+
 int main(int argc, char** argv) {
     if (argc > 1 && std::string(argv[1]) == "digest") return digest();
+    if (argc > 1 && std::string(argv[1]) == "strip") {
+        if (!check_strips()) return 1;
+        std::printf("ok\n");
+        return 0;
+    }
     if (argc > 1 && std::string(argv[1]) == "time") {  // build_work on cfg 5's 'N' list (host cost)
         const int n = 16384;
         auto LA = layout(splits(0xC5A1, 8, 96, n), splits(0xC5A2, 8, 96, n), uint64_t(1) << 40);
