@@ -298,6 +298,22 @@ def test_plan_cache_reuse(gpu):
     assert r1[0].tobytes() == r2[0].tobytes()
     s = gpu.get_stats()
     assert s["transforms"] == 2
+    # one pair of buffers and layouts kept across two calls: the second is a hit, and right
+    a, c = case.inputs(0, 0)
+    da, dc = dev(a), dev(c)
+    A, C = case.layout_A(0, 0, da.data_ptr()), case.layout_C(0, 0, dc.data_ptr())
+    op, alpha, beta = case.effective(0)
+    exp = case.expected()[0][0]
+    comm = gpu.Comm.self(0)
+    gpu.transform(A, C, comm, op, alpha, beta)
+    s1 = gpu.get_stats()
+    assert host(dc, oracle.NP[case.dtype]).tobytes() == exp.tobytes()
+    dc.copy_(dev(c))
+    gpu.transform(A, C, comm, op, alpha, beta)
+    s2 = gpu.get_stats()
+    assert (s2["plan_hits"] - s1["plan_hits"], s2["plan_misses"] - s1["plan_misses"]) == (1, 0)
+    assert host(dc, oracle.NP[case.dtype]).tobytes() == exp.tobytes()
+    assert r1[0].tobytes() == exp.tobytes()
 
 
 @pytest.mark.parametrize("dtype,lda,ldc", [(1, 16385, 16385), (1, 16384, 16387), (0, 16386, 16385),
