@@ -37,6 +37,8 @@ __all__ = [
     "ScaledOp", "SCALED_OP_DTYPE", "SCALED_F_ROWS", "transform_scaled", "execute_tiles_scaled",
     "plan_export_scaled", "scaled_subtile", "scaled_items",
     "transform_amax", "layout_amax", "execute_tiles_amax", "amax_items",
+    "MxScales", "MX_ROWS", "MX_COLS", "MX_FLOOR", "MX_CEIL", "mx_scales", "transform_mx",
+    "execute_tiles_mx", "mx_items", "mx_check_ops", "mx_check_scales",
 ]
 
 FLOAT, DOUBLE, CFLOAT, CDOUBLE, INT32 = 0, 1, 2, 3, 4
@@ -149,6 +151,22 @@ class ScaledOp(C.Structure):
     """costa_scaled_op_t: source element (f, s) of the op is target element (row0 + f, col0 + s)
     with flag SCALED_F_ROWS, (row0 + s, col0 + f) without."""
     _fields_ = [("op", TileOp), ("row0", C.c_int32), ("col0", C.c_int32)]
+
+
+# MX block-scaled transforms (costa_hip.h): the axis a block of 32 runs along, the rounding of E
+MX_ROWS, MX_COLS = 0, 1
+MX_FLOOR, MX_CEIL = 0, 1
+
+
+class MxScales(C.Structure):
+    """costa_mx_scales_t: the E8M0 byte of (block b, line l) is data[b*block_stride + l*line_stride];
+    axis MX_ROWS: a block is 32 consecutive rows of column l, MX_COLS: 32 consecutive columns of
+    row l."""
+    _fields_ = [("data", C.c_void_p), ("axis", C.c_int), ("block_stride", C.c_int64),
+                ("line_stride", C.c_int64)]
+
+    def __init__(self, data=0, axis=MX_ROWS, block_stride=0, line_stride=0):
+        super().__init__(data, axis, block_stride, line_stride)
 
 
 class PlanInfo(C.Structure):
@@ -272,6 +290,14 @@ def lib():
         "costa_hip_execute_tiles_amax": (i, [i, i, C.POINTER(ScaledOp), i64, vp, vp, vp, i, vp, vp, vp, vp,
                                              i]),
         "costa_hip_amax_items": (i, [C.POINTER(i64), i]),
+        "costa_hip_transform_mx": (i, [vp, vp, c, vp, vp, C.POINTER(MxScales), C.POINTER(MxScales), i, vp]),
+        "costa_hip_transform_mx_async": (i, [vp, vp, c, vp, vp, C.POINTER(MxScales), C.POINTER(MxScales), i,
+                                             vp, vp]),
+        "costa_hip_execute_tiles_mx": (i, [i, i, C.POINTER(ScaledOp), i64, vp, vp, vp, i, C.POINTER(MxScales),
+                                           C.POINTER(MxScales), i, i64, i64, i, i]),
+        "costa_hip_mx_items": (i, [C.POINTER(i64), i]),
+        "costa_hip_mx_check_ops": (i, [C.POINTER(ScaledOp), i64, i, i64, i64]),
+        "costa_hip_mx_check_scales": (i, [C.POINTER(MxScales), i64, i64]),
         "costa_hip_plan_export_scaled": (i, [vp, vp, c, vp, vp, i, i, C.POINTER(ScaledPlanInfo), vp, vp,
                                              vp, vp, vp, vp, vp, vp]),
         "costa_hip_plan_export": (i, [i, C.POINTER(vp), C.POINTER(vp), C.c_char_p, vp, vp, i, i,
@@ -941,6 +967,133 @@ def amax_items(reset: bool = False) -> int:
     v = C.c_int64(0)
     _check(lib().costa_hip_amax_items(C.byref(v), int(reset)))
     return v.value
+
+
+# ------------------------------------------------------------------ MX block-scaled transforms
+def _mx_axis(axis) -> int:
+    if axis in (MX_ROWS, "rows", "ROWS"):
+        return MX_ROWS
+    if axis in (MX_COLS, "cols", "COLS"):
+        return MX_COLS
+    raise ValueError(f"axis: MX_ROWS / 'rows' or MX_COLS / 'cols', not {axis!r}")
+
+
+def _mx_rounding(rounding) -> int:
+    if rounding in (MX_FLOOR, "floor"):
+        return MX_FLOOR
+    if rounding in (MX_CEIL, "ceil"):
+        return MX_CEIL
+    raise ValueError(f"rounding: 'floor' or 'ceil', not {rounding!r}")
+
+
+def mx_scales(tensor, axis, shape=None) -> MxScales:
+    """The descriptor of a 2-D torch CUDA tensor of E8M0 bytes indexed ``[block, line]`` (``uint8``, or
+    ``torch.float8_e8m0fnu`` where this torch has it); the strides are the tensor's, so
+    ``torch.zeros(nb, lines)`` is block-major and ``torch.zeros(lines, nb).T`` line-major.  ``axis``:
+    MX_ROWS / "rows" (a block is 32 consecutive rows of column ``line``) or MX_COLS / "cols".  With
+    ``shape`` = (rows, cols) of the matrix the tensor's extent is checked too.  ValueError for a wrong
+    dtype, device, rank, stride or extent.  The descriptor keeps a reference to the tensor."""
+    ax = _mx_axis(axis)
+    if type(tensor).__module__.split(".")[0] != "torch":
+        raise ValueError(f"mx_scales: a torch CUDA tensor, not {type(tensor)}")
+    if str(tensor.dtype) not in ("torch.uint8", "torch.float8_e8m0fnu"):
+        raise ValueError(f"mx_scales: dtype {tensor.dtype}, scale bytes are uint8 (E8M0)")
+    if not tensor.is_cuda:
+        raise ValueError("mx_scales: the tensor must be device-resident (a CUDA tensor)")
+    if tensor.dim() != 2:
+        raise ValueError(f"mx_scales: a 2-D tensor indexed [block, line], not {tensor.dim()}-D")
+    if shape is not None:
+        rows, cols = shape
+        along, lines = (rows, cols) if ax == MX_ROWS else (cols, rows)
+        want = ((along + 31) // 32, lines)
+        if tuple(tensor.shape) != want:
+            raise ValueError(f"mx_scales: shape {tuple(tensor.shape)}, the matrix needs {want} "
+                             "([blocks, lines])")
+    bs, ls = tensor.stride()
+    if (tensor.shape[0] > 1 and bs <= 0) or (tensor.shape[1] > 1 and ls <= 0):
+        raise ValueError("mx_scales: the strides must be positive")
+    d = MxScales(tensor.data_ptr(), ax, max(bs, 1), max(ls, 1))
+    d._keep = tensor
+    return d
+
+
+def _mx_arg(d, what, shape=None):
+    """a descriptor by reference; one made from a tensor is checked against the matrix's extent"""
+    if d is None:
+        return None
+    if not isinstance(d, MxScales):
+        raise ValueError(f"{what}: an MxScales descriptor (costa.mx_scales(tensor, axis)), not {type(d)}")
+    t = getattr(d, "_keep", None)
+    if t is not None and shape is not None:
+        rows, cols = shape
+        along, lines = (rows, cols) if d.axis == MX_ROWS else (cols, rows)
+        want = ((along + 31) // 32, lines)
+        if tuple(t.shape) != want:
+            raise ValueError(f"{what}: shape {tuple(t.shape)}, the {rows} x {cols} matrix needs {want} "
+                             "([blocks, lines])")
+    return C.byref(d)
+
+
+def transform_mx(A: Layout, Cl: Layout, comm: Comm, trans: str = "N", alpha=1.0, beta=0.0,
+                 a_scales=None, c_scales=None, rounding="floor", stream=None):
+    """MX block-scaled transform (costa_hip_transform_mx; costa_hip.h, "MX block-scaled
+    transforms"): quantise (FLOAT -> FP8, ``c_scales``), dequantise (FP8 -> FLOAT, ``a_scales``) or
+    requantise (FP8 -> the same FP8, both) while redistributing, one E8M0 scale byte per 32 elements
+    along the descriptor's axis.  ``a_scales`` is indexed by A's matrix as stored (before ``trans``),
+    ``c_scales`` by C's; ``rounding`` is "floor" (the OCP rule, saturating) or "ceil" (no element
+    saturates).  beta must be 0 with ``c_scales``.  With ``stream`` the call is stream-ordered and the
+    tensors must stay valid until the stream has passed it.  With several ranks each rank writes the
+    ``c_scales`` bytes of its own blocks only (merge zero-initialised tensors with a MAX all-reduce)
+    and needs the ``a_scales`` bytes of every block it reads."""
+    if not isinstance(A, Layout) or not isinstance(Cl, Layout):
+        raise CostaError(1, "costa: batches of MX layout pairs are not supported")
+    code = _scalar_code(A.dtype, Cl.dtype)
+    ab, bb = _scalar_bytes(code, alpha), _scalar_bytes(code, beta)
+    args = (A.handle, Cl.handle, _chr(trans), ab, bb, _mx_arg(a_scales, "a_scales", A.shape()),
+            _mx_arg(c_scales, "c_scales", Cl.shape()), _mx_rounding(rounding), comm.handle)
+    if stream is None:
+        _check(lib().costa_hip_transform_mx(*args))
+    else:
+        s = getattr(stream, "cuda_stream", stream) or 0
+        _check(lib().costa_hip_transform_mx_async(*args, C.c_void_p(s)))
+
+
+def execute_tiles_mx(src_dtype, dst_dtype, ops: np.ndarray, scalars: np.ndarray, m: int, n: int,
+                     src_base=0, dst_base=0, a_scales=None, c_scales=None, rounding="floor",
+                     a_transposed: bool = False, device: int = 0):
+    """Run a list of scaled ops (SCALED_OP_DTYPE) in one launch of the MX kernel; ``m`` x ``n`` is C's
+    matrix, fp32 ``scalars``; with ``a_transposed`` A's matrix is n x m and ``a_scales`` is indexed by
+    it (costa_hip_execute_tiles_mx)."""
+    sc_, dc_ = element_code(src_dtype), element_code(dst_dtype)
+    ops = np.ascontiguousarray(ops, dtype=SCALED_OP_DTYPE)
+    sc = np.ascontiguousarray(scalars, dtype=np.float32).reshape(-1)
+    assert sc.size % 2 == 0
+    _check(lib().costa_hip_execute_tiles_mx(sc_, dc_, ops.ctypes.data_as(C.POINTER(ScaledOp)), ops.size,
+                                            C.c_void_p(_ptr(src_base)), C.c_void_p(_ptr(dst_base)),
+                                            sc.ctypes.data, sc.size // 2, _mx_arg(a_scales, "a_scales"),
+                                            _mx_arg(c_scales, "c_scales"), _mx_rounding(rounding), m, n,
+                                            int(a_transposed), device))
+
+
+def mx_items(reset: bool = False) -> int:
+    """Sub-tiles run by the MX kernel since the last reset."""
+    v = C.c_int64(0)
+    _check(lib().costa_hip_mx_items(C.byref(v), int(reset)))
+    return v.value
+
+
+def mx_check_ops(ops: np.ndarray, axis, m: int, n: int):
+    """The tile-boundary rule of ``c_scales`` on scaled ops (host only): CostaError with "MX block"
+    when an op splits a block of C's m x n matrix along ``axis``."""
+    ops = np.ascontiguousarray(ops, dtype=SCALED_OP_DTYPE)
+    _check(lib().costa_hip_mx_check_ops(ops.ctypes.data_as(C.POINTER(ScaledOp)), ops.size, _mx_axis(axis),
+                                        m, n))
+
+
+def mx_check_scales(d: MxScales, rows: int, cols: int):
+    """The stride rule of a descriptor for a rows x cols matrix (host only): positive strides, no two
+    (block, line) entries on one byte."""
+    _check(lib().costa_hip_mx_check_scales(C.byref(d), rows, cols))
 
 
 @dataclass

@@ -613,6 +613,79 @@ int costa_hip_amax_items(int64_t* items, int reset) {
     });
 }
 
+namespace {
+// the one job of costa_hip_transform_mx: a scaled job (the scaled plan, unchanged) whose lists run on
+// mx_kernel; an absent descriptor (NULL, or NULL data) is all zeros
+std::vector<job> make_mx_job(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                             const void* beta, const costa_mx_scales_t* a_scales,
+                             const costa_mx_scales_t* c_scales, int rounding) {
+    auto jobs = make_scaled_job(A, C, trans, alpha, beta, nullptr, nullptr);
+    jobs[0].mx = true;
+    if (a_scales && a_scales->data) jobs[0].a_scales = *a_scales;
+    if (c_scales && c_scales->data) jobs[0].c_scales = *c_scales;
+    jobs[0].mx_rounding = rounding;
+    return jobs;
+}
+}  // namespace
+
+int costa_hip_transform_mx(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                           const void* beta, const costa_mx_scales_t* a_scales,
+                           const costa_mx_scales_t* c_scales, int rounding, costa_comm_t comm) {
+    static_assert(sizeof(costa_mx_scales_t) == 32, "descriptor size");
+    return gpu_guarded([&] {
+        if (!comm || !alpha || !beta) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::transform(make_mx_job(A, C, trans, alpha, beta, a_scales, c_scales, rounding), comm->c);
+    });
+}
+
+int costa_hip_transform_mx_async(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                                 const void* beta, const costa_mx_scales_t* a_scales,
+                                 const costa_mx_scales_t* c_scales, int rounding, costa_comm_t comm,
+                                 void* stream) {
+    return gpu_guarded([&] {
+        if (!comm || !alpha || !beta) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::transform(make_mx_job(A, C, trans, alpha, beta, a_scales, c_scales, rounding), comm->c,
+                                 stream, true);
+    });
+}
+
+int costa_hip_execute_tiles_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
+                               const costa_scaled_op_t* ops, int64_t n_ops, const void* src_base,
+                               void* dst_base, const void* scalars, int n_slots,
+                               const costa_mx_scales_t* a_scales, const costa_mx_scales_t* c_scales,
+                               int rounding, int64_t m, int64_t n, int a_transposed, int device) {
+    return gpu_guarded([&] {
+        if (n_ops < 0 || (n_ops > 0 && (!ops || !scalars)))
+            throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::execute_tiles_mx(src_dtype, dst_dtype, ops, n_ops, src_base, dst_base, scalars, n_slots,
+                                        a_scales, c_scales, rounding, m, n, a_transposed, device);
+    });
+}
+
+int costa_hip_mx_items(int64_t* items, int reset) {
+    return guarded([&] {
+        if (!items) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        *items = costa::engine::mx_items(reset != 0);
+    });
+}
+
+int costa_hip_mx_check_ops(const costa_scaled_op_t* ops, int64_t n_ops, int axis, int64_t m, int64_t n) {
+    return guarded([&] {
+        if (n_ops < 0 || (n_ops > 0 && !ops)) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        if (axis != COSTA_MX_ROWS && axis != COSTA_MX_COLS)
+            throw costa::engine::error(COSTA_ERR_ARG, "costa_hip_mx_check_ops: axis must be COSTA_MX_ROWS or "
+                                                      "COSTA_MX_COLS");
+        costa::engine::check_mx_ops(std::vector<costa_scaled_op_t>(ops, ops + n_ops), axis, m, n);
+    });
+}
+
+int costa_hip_mx_check_scales(const costa_mx_scales_t* s, int64_t rows, int64_t cols) {
+    return guarded([&] {
+        if (!s) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::check_mx_scales(*s, rows, cols, "costa_hip_mx_check_scales");
+    });
+}
+
 int costa_hip_plan_export_scaled(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
                                  const void* beta, int rank, int nranks,
                                  costa_scaled_plan_info_t* info, costa_tile_op_t* pack_ops,

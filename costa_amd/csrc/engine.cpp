@@ -1841,6 +1841,8 @@ struct cached_plan {
     // the lists of a scaled plan (scaled_kernels.hip): LOCAL, and UNPACK per exchange round
     dbuf d_local_sc, w_local_sc;
     strip_list s_local;
+    // the tile-boundary rule of MX calls per c_scales axis: 0 not checked yet, 1 holds, -1 fails
+    int mx_rule[2] = {0, 0};
     struct xround {  // one exchange round: its pack ops (by their first element) and unpack
                      // ops (by their last element)
         dbuf d_pack, w_pack, d_unpack, w_unpack;
@@ -2388,6 +2390,7 @@ enum phase { PH_LOCAL, PH_PACK, PH_EXCHANGE, PH_UNPACK, PH_H2D, PH_D2H, PH_TRI_L
 double g_tri_ms = 0;
 int64_t g_scaled_items = 0;  // sub-tiles run by scaled_kernel (kept beside costa_stats_t)
 int64_t g_amax_items = 0;    // ... by its AMAX instantiations and by amax_kernel (likewise)
+int64_t g_mx_items = 0;      // ... by mx_kernel (likewise; not counted as scaled items)
 
 struct phase_timer {
     device_ctx& dc;
@@ -2505,7 +2508,92 @@ struct scaled_args {
     const void *row_scale = nullptr, *col_scale = nullptr;
     void *row_amax = nullptr, *col_amax = nullptr;
     bool amax() const { return row_amax || col_amax; }
+    // an MX call (costa_hip_transform_mx): the same lists on mx_kernel, its tensors in target coordinates
+    bool mx = false;
+    mx_side a_scales, c_scales;
+    bool ceil = false;
 };
+
+// the matrix a layout describes
+void layout_extent(const elayout& L, int64_t& rows, int64_t& cols) {
+    rows = L.rows_split.empty() ? 0 : int64_t(L.rows_split.back()) - L.rows_split.front();
+    cols = L.cols_split.empty() ? 0 : int64_t(L.cols_split.back()) - L.cols_split.front();
+}
+
+// The argument checks of costa_hip_transform_mx that need no plan and no device: the pair, which
+// descriptors it wants, beta, the rounding mode, strides and aliasing.
+void check_mx_job(const job& j) {
+    const costa_dtype_t a = j.A->dtype, c = j.C->dtype;
+    if (!mx_pair(a, c))
+        throw error(COSTA_ERR_ARG, std::string("costa_hip_transform_mx: no MX transform for ") + dtype_name(a) +
+                                       " -> " + dtype_name(c) + " (FLOAT -> FP8, FP8 -> FLOAT, FP8 -> the same FP8)");
+    if (j.uplo != 'A') throw error(COSTA_ERR_ARG, "costa_hip_transform_mx: no triangular mask");
+    if (j.A == j.C) throw error(COSTA_ERR_ARG, "costa_hip_transform_mx: in-place calls are not supported");
+    const bool want_a = dtype_is_fp8(a), want_c = dtype_is_fp8(c);
+    if (want_a && !j.a_scales.data)
+        throw error(COSTA_ERR_ARG, std::string("costa_hip_transform_mx: a_scales is required for ") + dtype_name(a) +
+                                       " -> " + dtype_name(c));
+    if (!want_a && j.a_scales.data)
+        throw error(COSTA_ERR_ARG, std::string("costa_hip_transform_mx: a_scales given for a FLOAT source (") +
+                                       dtype_name(a) + " -> " + dtype_name(c) + ")");
+    if (want_c && !j.c_scales.data)
+        throw error(COSTA_ERR_ARG, std::string("costa_hip_transform_mx: c_scales is required for ") + dtype_name(a) +
+                                       " -> " + dtype_name(c));
+    if (!want_c && j.c_scales.data)
+        throw error(COSTA_ERR_ARG, std::string("costa_hip_transform_mx: c_scales given for a FLOAT destination (") +
+                                       dtype_name(a) + " -> " + dtype_name(c) + ")");
+    if (j.mx_rounding != COSTA_MX_FLOOR && j.mx_rounding != COSTA_MX_CEIL)
+        throw error(COSTA_ERR_ARG, "costa_hip_transform_mx: rounding must be COSTA_MX_FLOOR or COSTA_MX_CEIL");
+    if (want_c) {
+        float beta;
+        std::memcpy(&beta, j.s.beta.data(), sizeof beta);
+        if (!(beta == 0.0f)) throw error(COSTA_ERR_ARG, "costa_hip_transform_mx: beta must be 0 with c_scales");
+    }
+    int64_t r, k;
+    if (want_a) {
+        layout_extent(*j.A, r, k);
+        check_mx_scales(j.a_scales, r, k, "costa_hip_transform_mx: a_scales");
+    }
+    if (want_c) {
+        layout_extent(*j.C, r, k);
+        check_mx_scales(j.c_scales, r, k, "costa_hip_transform_mx: c_scales");
+    }
+}
+
+// a descriptor as the kernel sees it: in target coordinates (`swap`: the tensor is indexed by A's
+// matrix of a transposing job, whose rows are target columns)
+mx_side mx_side_of(const costa_mx_scales_t& s, bool swap) {
+    mx_side o;
+    o.data = s.data;
+    o.block_stride = s.block_stride;
+    o.line_stride = s.line_stride;
+    o.rows = (s.axis == COSTA_MX_ROWS) != swap;
+    return o;
+}
+
+// ... and those that need them: device residency and the tile-boundary rule (kept per plan and
+// axis); fills sv
+void mx_args(const job& j, cached_plan& cp, scaled_args& sv) {
+    for (const void* v : {static_cast<const void*>(j.a_scales.data), static_cast<const void*>(j.c_scales.data)})
+        if (v && !is_device_ptr(v))
+            throw error(COSTA_ERR_ARG, "costa_hip_transform_mx: the scale tensors must be device-resident");
+    if (j.c_scales.data) {
+        int& ok = cp.mx_rule[j.c_scales.axis == COSTA_MX_ROWS ? 0 : 1];
+        int64_t m, n;
+        layout_extent(*j.C, m, n);
+        if (ok <= 0) {  // (a failing plan is checked again: the error carries the op)
+            ok = -1;
+            check_mx_ops(cp.p->local_scaled, j.c_scales.axis, m, n);
+            check_mx_ops(cp.p->unpack_scaled, j.c_scales.axis, m, n);
+            ok = 1;
+        }
+    }
+    sv = scaled_args{};
+    sv.mx = true;
+    sv.a_scales = mx_side_of(j.a_scales, std::toupper(static_cast<unsigned char>(j.trans)) != 'N');
+    sv.c_scales = mx_side_of(j.c_scales, false);
+    sv.ceil = j.mx_rounding == COSTA_MX_CEIL;
+}
 
 // The launch blocks of a transform: LOCAL, one round's PACK, one round's UNPACK.  transform() calls
 // them for an RCCL communicator (on the context's three streams, around issue_exchange) and for the
@@ -2537,9 +2625,14 @@ void launch_local(const cached_plan& cp, const scaled_args& sv, phase_timer& tm,
 
     if (cp.s_local.n_items) {  // the LOCAL list of a scaled plan
         tm.start(PH_LOCAL, ls);
-        launch_scaled(p.src_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(cp.d_local_sc.p),
+        if (sv.mx)
+            launch_mx(p.src_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(cp.d_local_sc.p),
                       static_cast<const uint64_t*>(cp.w_local_sc.p), cp.s_local, nullptr, nullptr,
-                      cp.d_scal.p, sv.row_scale, sv.col_scale, sv.row_amax, sv.col_amax, ls);
+                      cp.d_scal.p, sv.a_scales, sv.c_scales, sv.ceil, ls);
+        else
+            launch_scaled(p.src_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(cp.d_local_sc.p),
+                          static_cast<const uint64_t*>(cp.w_local_sc.p), cp.s_local, nullptr, nullptr,
+                          cp.d_scal.p, sv.row_scale, sv.col_scale, sv.row_amax, sv.col_amax, ls);
         tm.stop();
     }
 }
@@ -2598,9 +2691,14 @@ void launch_unpack_round(const cached_plan& cp, const cached_plan::xround& x, co
     if (x.s_unpack.n_items) {  // the round's unpack list of a scaled plan
         if (moved) HIP_CHECK(hipStreamWaitEvent(s, moved, 0));
         tm.start(PH_UNPACK, s);
-        launch_scaled(p.pkg_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(x.d_unpack_sc.p),
+        if (sv.mx)
+            launch_mx(p.pkg_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(x.d_unpack_sc.p),
                       static_cast<const uint64_t*>(x.w_unpack_sc.p), x.s_unpack, rb, nullptr,
-                      cp.d_scal.p, sv.row_scale, sv.col_scale, sv.row_amax, sv.col_amax, s);
+                      cp.d_scal.p, sv.a_scales, sv.c_scales, sv.ceil, s);
+        else
+            launch_scaled(p.pkg_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(x.d_unpack_sc.p),
+                          static_cast<const uint64_t*>(x.w_unpack_sc.p), x.s_unpack, rb, nullptr,
+                          cp.d_scal.p, sv.row_scale, sv.col_scale, sv.row_amax, sv.col_amax, s);
         tm.stop();
     }
 }
@@ -2615,10 +2713,10 @@ void count_items(const plan& p, const work_split& w) {
         g_stats.fused_pieces += w.n_tiny;
 }
 
-void count_local(const cached_plan& cp, bool amax) {
+void count_local(const cached_plan& cp, bool amax, bool mx) {
     const plan& p = *cp.p;
     g_stats.tri_items += cp.t_local.n_items;
-    g_scaled_items += cp.s_local.n_items;
+    (mx ? g_mx_items : g_scaled_items) += cp.s_local.n_items;
     if (amax) g_amax_items += cp.s_local.n_items;
     if (cp.l_local.n_items() || cp.c_local.n_items || cp.t_local.n_items || cp.s_local.n_items) {
         g_stats.local_launches++;
@@ -2634,11 +2732,11 @@ void count_pack_round(const cached_plan& cp, const cached_plan::xround& x) {
     g_stats.convert_items += x.c_pack.n_items;
 }
 
-void count_unpack_round(const cached_plan& cp, const cached_plan::xround& x, bool amax) {
+void count_unpack_round(const cached_plan& cp, const cached_plan::xround& x, bool amax, bool mx) {
     g_stats.unpack_launches +=
         x.l_unpack.n_items() || x.c_unpack.n_items || x.t_unpack.n_items || x.s_unpack.n_items ? 1 : 0;
     g_stats.tri_items += x.t_unpack.n_items;
-    g_scaled_items += x.s_unpack.n_items;
+    (mx ? g_mx_items : g_scaled_items) += x.s_unpack.n_items;
     if (amax) g_amax_items += x.s_unpack.n_items;
     count_items(*cp.p, x.l_unpack);
     g_stats.convert_items += x.c_unpack.n_items;
@@ -2668,7 +2766,7 @@ void run_emulated_part(const comm* c, device_ctx& dc, const cached_plan& cp, con
     const int r0 = c->round < 0 ? 0 : c->round, r1 = c->round < 0 ? R : c->round + 1;
     if (c->part == COSTA_EMULATE_LOCAL) {
         launch_local(cp, sv, tm, dc.main);
-        count_local(cp, sv.amax());
+        count_local(cp, sv.amax(), sv.mx);
         g_stats.transforms++;
     } else if (c->part == COSTA_EMULATE_PACK) {
         if (!buffer_holds(c->buffer, size_t(p.send_elems) * E))
@@ -2684,7 +2782,7 @@ void run_emulated_part(const comm* c, device_ctx& dc, const cached_plan& cp, con
         for (int r = r0; r < r1; ++r) {
             launch_unpack_round(cp, *cp.rounds[size_t(r)], static_cast<const char*>(c->buffer), sv, tm,
                                 dc.main, nullptr);
-            count_unpack_round(cp, *cp.rounds[size_t(r)], sv.amax());
+            count_unpack_round(cp, *cp.rounds[size_t(r)], sv.amax(), sv.mx);
         }
         if (r1 == R) g_stats.unpack_bytes += p.unpack_bytes;
     }
@@ -2709,6 +2807,8 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
             if (!layout_on_device(*j.A) || !layout_on_device(*j.C))
                 throw error(COSTA_ERR_ARG, "costa: an emulated communicator needs device-resident layouts");
     }
+    const bool mx = jobs.size() == 1 && jobs[0].mx;
+    if (mx) check_mx_job(jobs[0]);  // pair, descriptors, beta, strides: before the plan
     cached_plan& cp = *get_plan(jobs, c, dc);
     const plan& p = *cp.p;
     const size_t E = dtype_size(p.pkg_dtype);  // of the send / receive packages
@@ -2719,7 +2819,14 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
     void* row_amax = p.scaled ? jobs[0].row_amax : nullptr;
     void* col_amax = p.scaled ? jobs[0].col_amax : nullptr;
     const bool amax = row_amax || col_amax;
-    if (p.scaled) {
+    scaled_args sv;
+    sv.row_scale = row_scale;
+    sv.col_scale = col_scale;
+    sv.row_amax = row_amax;
+    sv.col_amax = col_amax;
+    if (mx) {
+        mx_args(jobs[0], cp, sv);
+    } else if (p.scaled) {
         if (!row_scale && !col_scale && !amax)
             throw error(COSTA_ERR_ARG, "costa: a scaled transform without scale vectors (use costa_hip_transform)");
         for (const void* v : {row_scale, col_scale})
@@ -2764,7 +2871,6 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
         g_stats.transforms++;
         return;
     }
-    const scaled_args sv{row_scale, col_scale, row_amax, col_amax};
     if (c->emulated) return run_emulated_part(c, dc, cp, sv);
     phase_timer tm(dc, g_profiling);
 
@@ -2824,11 +2930,11 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
     }
 
     g_stats.transforms++;
-    count_local(cp, amax);
+    count_local(cp, amax, sv.mx);
     if (exchange) {
         for (const auto& x : cp.rounds) {
             count_pack_round(cp, *x);
-            count_unpack_round(cp, *x, amax);
+            count_unpack_round(cp, *x, amax, sv.mx);
         }
         g_stats.pack_bytes += p.pack_bytes;
         g_stats.unpack_bytes += p.unpack_bytes;
@@ -3106,6 +3212,97 @@ int64_t scaled_items(bool reset) {
     std::lock_guard<std::recursive_mutex> lk(g_mutex);
     const int64_t v = g_scaled_items;
     if (reset) g_scaled_items = 0;
+    return v;
+}
+
+// ---------------------------------------------------------------- MX block-scaled transforms
+void check_mx_scales(const costa_mx_scales_t& s, int64_t rows, int64_t cols, const std::string& what) {
+    if (s.axis != COSTA_MX_ROWS && s.axis != COSTA_MX_COLS)
+        throw error(COSTA_ERR_ARG, what + ": axis must be COSTA_MX_ROWS or COSTA_MX_COLS");
+    if (s.block_stride <= 0 || s.line_stride <= 0)
+        throw error(COSTA_ERR_ARG, what + ": the strides must be positive");
+    const int64_t along = s.axis == COSTA_MX_ROWS ? rows : cols, lines = s.axis == COSTA_MX_ROWS ? cols : rows;
+    const int64_t nb = (along + 31) / 32;
+    // two positive strides address nb x lines distinct bytes exactly when the larger one steps over
+    // the whole extent of the smaller one's index, or some pair (db, dl) with db*bs == dl*ls exists
+    // inside the ranges: db < nb, dl < lines
+    if (nb > 1 && lines > 1) {
+        const int64_t g = std::gcd(s.block_stride, s.line_stride);
+        // the smallest coincidence: db = ls / g, dl = bs / g
+        if (s.line_stride / g < nb && s.block_stride / g < lines)
+            throw error(COSTA_ERR_ARG, what + ": the strides make two (block, line) entries share a byte");
+    }
+}
+
+void check_mx_ops(const std::vector<costa_scaled_op_t>& ops, int axis, int64_t m, int64_t n) {
+    for (const costa_scaled_op_t& t : ops) {
+        if (t.op.nf <= 0 || t.op.ns <= 0) continue;
+        const bool frow = t.op.flags & COSTA_SCALED_F_ROWS;
+        // the op's start and extent along the block axis, in C's coordinates
+        const int64_t at = axis == COSTA_MX_ROWS ? t.row0 : t.col0;
+        const int64_t len = (axis == COSTA_MX_ROWS) == frow ? t.op.nf : t.op.ns;
+        const int64_t edge = axis == COSTA_MX_ROWS ? m : n;
+        if (at % 32 != 0 || (len % 32 != 0 && at + len != edge) || at + len > edge)
+            throw error(COSTA_ERR_ARG,
+                        "costa: a tile boundary splits an MX block of C: a tile covers " +
+                            std::string(axis == COSTA_MX_ROWS ? "rows " : "columns ") + std::to_string(at) + " .. " +
+                            std::to_string(at + len) + " of " + std::to_string(edge) +
+                            " (block sizes and split points of both layouts must be multiples of 32 along "
+                            "c_scales.axis)");
+    }
+}
+
+void execute_tiles_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* ops,
+                      int64_t n_ops, const void* src_base, void* dst_base, const void* scalars, int n_slots,
+                      const costa_mx_scales_t* a_scales, const costa_mx_scales_t* c_scales, int rounding,
+                      int64_t m, int64_t n, int a_transposed, int device) {
+    std::lock_guard<std::recursive_mutex> lk(g_mutex);
+    const std::string who = "costa_hip_execute_tiles_mx";
+    if (!mx_pair(src_dtype, dst_dtype))
+        throw error(COSTA_ERR_ARG, who + ": no MX kernel for " + dtype_name(src_dtype) + " -> " + dtype_name(dst_dtype));
+    const costa_mx_scales_t none{};
+    const costa_mx_scales_t& sa = a_scales && a_scales->data ? *a_scales : none;
+    const costa_mx_scales_t& sc = c_scales && c_scales->data ? *c_scales : none;
+    if ((sa.data != nullptr) != dtype_is_fp8(src_dtype) || (sc.data != nullptr) != dtype_is_fp8(dst_dtype))
+        throw error(COSTA_ERR_ARG, who + ": a scale tensor is needed exactly on the FP8 sides of " +
+                                       dtype_name(src_dtype) + " -> " + dtype_name(dst_dtype));
+    if (rounding != COSTA_MX_FLOOR && rounding != COSTA_MX_CEIL)
+        throw error(COSTA_ERR_ARG, who + ": rounding must be COSTA_MX_FLOOR or COSTA_MX_CEIL");
+    if (m < 0 || n < 0) throw error(COSTA_ERR_ARG, who + ": negative matrix extent");
+    if (sa.data) check_mx_scales(sa, a_transposed ? n : m, a_transposed ? m : n, who + ": a_scales");
+    std::vector<costa_scaled_op_t> v(ops, ops + n_ops);
+    for (const costa_scaled_op_t& t : v) {
+        if (t.op.nf <= 0 || t.op.ns <= 0) continue;
+        if (t.row0 < 0 || t.col0 < 0) throw error(COSTA_ERR_ARG, who + ": negative target coordinate");
+        const bool frow = t.op.flags & COSTA_SCALED_F_ROWS;
+        if (t.row0 + int64_t(frow ? t.op.nf : t.op.ns) > m || t.col0 + int64_t(frow ? t.op.ns : t.op.nf) > n)
+            throw error(COSTA_ERR_ARG, who + ": an op reaches past the m x n matrix");
+    }
+    if (sc.data) {
+        check_mx_scales(sc, m, n, who + ": c_scales");
+        for (const costa_scaled_op_t& t : v)
+            if (((t.op.flags & COSTA_SCALE_MASK) >> COSTA_SCALE_SHIFT) == COSTA_SCALE_AXPBY)
+                throw error(COSTA_ERR_ARG, who + ": beta must be 0 with c_scales (an op of kind AXPBY)");
+        check_mx_ops(v, sc.axis, m, n);
+    }
+    ctx(device);  // (is_device_ptr needs the device's context)
+    for (const void* p : {static_cast<const void*>(sa.data), static_cast<const void*>(sc.data)})
+        if (p && !is_device_ptr(p)) throw error(COSTA_ERR_ARG, who + ": the scale tensors must be device-resident");
+    const mx_side da = mx_side_of(sa, a_transposed != 0), dc_ = mx_side_of(sc, false);
+    const uintptr_t sb = reinterpret_cast<uintptr_t>(src_base), db = reinterpret_cast<uintptr_t>(dst_base);
+    g_mx_items += run_strip_tiles(
+        who, v.data(), n_ops, scalars, n_slots, sizeof(float), device,
+        [&](const auto& l, auto& ord, auto& w) { return build_scaled_work(src_dtype, dst_dtype, l, sb, db, ord, w, false); },
+        [&](const costa_scaled_op_t* d_ops, const uint64_t* d_work, const strip_list& l, const void* d_scal, void* s) {
+            launch_mx(src_dtype, dst_dtype, d_ops, d_work, l, static_cast<const char*>(src_base),
+                      static_cast<char*>(dst_base), d_scal, da, dc_, rounding == COSTA_MX_CEIL, s);
+        });
+}
+
+int64_t mx_items(bool reset) {
+    std::lock_guard<std::recursive_mutex> lk(g_mutex);
+    const int64_t v = g_mx_items;
+    if (reset) g_mx_items = 0;
     return v;
 }
 

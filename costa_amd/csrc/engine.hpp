@@ -92,6 +92,13 @@ struct job {
     // a scaled job; arguments of the call like the scales (with one of them both scales may be null)
     void* row_amax = nullptr;
     void* col_amax = nullptr;
+    // MX block-scaled transforms (costa_hip_transform_mx): a scaled job whose LOCAL / UNPACK lists run
+    // on mx_kernel; the descriptors (data == NULL: none) and the rounding mode are arguments of the
+    // call like the vectors above
+    bool mx = false;
+    costa_mx_scales_t a_scales{};
+    costa_mx_scales_t c_scales{};
+    int mx_rounding = 0;
 };
 
 // The three tile-op lists of one rank plus the exchange geometry.  Addresses of pack
@@ -348,6 +355,38 @@ void layout_amax(const elayout& L, void* row_amax, void* col_amax, struct comm* 
                  bool async);
 // sub-tiles run by the AMAX instantiations of scaled_kernel and by amax_kernel since the last reset
 int64_t amax_items(bool reset);
+// ---- MX block-scaled transforms (mx_kernels.hip; costa_hip.h, "MX block-scaled transforms") ----
+// One kernel family, mx_kernel<Es, Ed, QUANT>, on the scaled ops and work items of a scaled plan
+// (build_scaled_work: the same 64 x 64 sub-tile and alignment rule).  A scale tensor as the kernel
+// sees it, in TARGET coordinates (C's; A's descriptor has its axis turned round when the job
+// transposes): byte of (block b, line l) at data[b * block_stride + l * line_stride], `rows` = a
+// block is 32 consecutive target rows of one target column.  data == nullptr: none.
+struct mx_side {
+    void* data = nullptr;
+    int64_t block_stride = 0, line_stride = 0;
+    bool rows = true;
+};
+// FLOAT -> Q (quantise), Q -> FLOAT (dequantise), Q -> Q of one Q (requantise)
+bool mx_pair(costa_dtype_t src, costa_dtype_t dst);
+// a scale tensor on exactly the FP8 sides of the pair; `ceil`: COSTA_MX_CEIL
+void launch_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* d_ops,
+               const uint64_t* d_work, const strip_list& l, const char* src_base, char* dst_base,
+               const void* d_scalars, const mx_side& a_scales, const mx_side& c_scales, bool ceil,
+               void* stream /* hipStream_t */);
+// a descriptor's strides are positive and no two (block, line) of a rows x cols matrix share a byte
+// (throws COSTA_ERR_ARG naming `what`); host only
+void check_mx_scales(const costa_mx_scales_t& s, int64_t rows, int64_t cols, const std::string& what);
+// the tile-boundary rule: along `axis` every op starts at a multiple of 32 of C's coordinates and
+// spans a multiple of 32 or ends at the edge of C's m x n matrix (throws COSTA_ERR_ARG, "MX block")
+void check_mx_ops(const std::vector<costa_scaled_op_t>& ops, int axis, int64_t m, int64_t n);
+// costa_hip_execute_tiles_mx: m x n is C's matrix; a_transposed: A's matrix is n x m (target (i, j)
+// is A's (j, i))
+void execute_tiles_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* ops,
+                      int64_t n_ops, const void* src_base, void* dst_base, const void* scalars, int n_slots,
+                      const costa_mx_scales_t* a_scales, const costa_mx_scales_t* c_scales, int rounding,
+                      int64_t m, int64_t n, int a_transposed, int device);
+// sub-tiles run by mx_kernel since the last reset
+int64_t mx_items(bool reset);
 // ... of every scaled unpack op (plan::unpack_scaled), by the rule of exchange_round_of_ops
 void exchange_round_of_scaled(const struct plan& p, int rounds, std::vector<int>& unpack_round);
 

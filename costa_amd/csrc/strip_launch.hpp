@@ -1,5 +1,5 @@
 // The host launch of the strip kernel families (convert_kernels.hip, tri_kernels.hip,
-// half_kernels.hip, fp8_kernels.hip, scaled_kernels.hip): each runs a work list built by
+// half_kernels.hip, fp8_kernels.hip, scaled_kernels.hip, mx_kernels.hip): each runs a work list built by
 // build_strip_work (strip_work.hpp), one workgroup per work item, on a kernel whose first two
 // arguments are the device array of ops and the work items.  Internal to the including file.
 #pragma once

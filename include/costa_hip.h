@@ -434,6 +434,92 @@ int costa_hip_layout_amax(costa_layout_t A, void* row_amax, void* col_amax, cost
 int costa_hip_layout_amax_async(costa_layout_t A, void* row_amax, void* col_amax, costa_comm_t comm,
                                 void* stream);
 
+/* ---- MX block-scaled transforms (MI355X-native): E8M0 scales per 32 elements, fused ----
+ * FP8 data with one power-of-two scale byte (E8M0) per 32 consecutive elements along one axis (OCP
+ * Microscaling v1.0, MXFP8), produced or consumed by the redistribution itself in one pass.
+ *
+ * Scale tensor.  A DEVICE array of bytes described by costa_mx_scales_t.  With axis COSTA_MX_ROWS a
+ * block is 32 consecutive ROWS of one column: block b of line l covers rows 32b .. 32b+31 of column
+ * l.  With COSTA_MX_COLS a block is 32 consecutive COLUMNS of one row (l is the row).  The byte of
+ * (b, l) is data[b*block_stride + l*line_stride] (block-major or line-major storage is the caller's
+ * choice).  Coordinates count from the first row and column of the layout's matrix, as for the scale
+ * vectors above: `a_scales` is indexed by A's matrix as stored (before op), `c_scales` by C's.  The
+ * last block of a line may be partial and reduces over the elements that exist.  Both strides must
+ * be positive and no two (b, l) of the matrix may share a byte (COSTA_ERR_ARG otherwise).
+ *
+ * Byte encoding.  pow2(E) is the fp32 with bits E << 23 for 1 <= E <= 254; pow2(0) = 0x00400000
+ * (2^-127, a subnormal, not flushed); pow2(255) = 0x7FC00000 (NaN).
+ *
+ * Arithmetic (fp32, no contraction).  For each written element:
+ *   1. x = w(a); with a_scales  x = x * pow2(SA[block of a])  (one rounded product)
+ *   2. v = g(x, w(c_old)): the ordinary ZERO / ALPHA / AXPBY branches (BITCOPY: v = x)
+ *   3. without c_scales (C is COSTA_FLOAT): store v
+ *   4. with c_scales (C is FP8, beta must be 0), per block of C: amax = the unsigned maximum of the
+ *      bit patterns of |v| over the block, e = amax >> 23.  e == 255 (an inf or NaN in the block):
+ *      E = 255 and every element of the block is stored as a NaN of the type.  Otherwise
+ *      E = clamp(e - emax, 0, 254), emax = 8 (e4m3) / 15 (e5m2): the OCP floor rule.  With rounding
+ *      COSTA_MX_CEIL E is one higher (at most 254) when amax * pow2(254 - E) > fmax (448 / 57344);
+ *      then no element saturates.  q = cvt(clamp(v * pow2(254 - E), -fmax, +fmax)) with the ordinary
+ *      round-to-nearest-even cvt; SC[block] = E.  An all-zero block gives E = 0 and zeros.
+ *
+ * Accepted calls (everything else is COSTA_ERR_ARG naming what was wrong, C and the scale tensors
+ * untouched):
+ *   quantise    COSTA_FLOAT -> FP8      a_scales NULL, c_scales required, beta = 0
+ *   dequantise  FP8 -> COSTA_FLOAT      a_scales required, c_scales NULL, alpha / beta free
+ *   requantise  FP8 -> the same FP8     both required, beta = 0 (e.g. 'T' with the other axis)
+ * A descriptor is "absent" when its pointer or its `data` is NULL.
+ *
+ * Tile boundaries.  A block of C must not be split by a tile boundary: along c_scales.axis every
+ * LOCAL and UNPACK op of the plan must start at a multiple of 32 of C's coordinates and span a
+ * multiple of 32 or end at the matrix edge, i.e. the block sizes and split points of both layouts
+ * (A's seen through op) are multiples of 32 along that axis.  Checked before anything is written:
+ * COSTA_ERR_ARG with "MX block" in the message.  a_scales has no such restriction.
+ *
+ * Several ranks.  The exchange is the ordinary plan's (COSTA_FLOAT -> Q sends fp32, Q -> .. sends Q
+ * bytes); only LOCAL and UNPACK ops touch scale tensors.  A rank writes only the c_scales bytes of
+ * the blocks it owns in C and leaves every other byte alone: zero-initialised tensors merge across
+ * ranks with a byte-wise all-reduce MAX.  A rank needs the a_scales bytes of every block it reads,
+ * those of tiles it receives included: the library moves no scales between ranks, so replicate
+ * a_scales.
+ *
+ * Device-resident layouts and scale tensors only (a host pointer is COSTA_ERR_ARG with
+ * "device-resident"); blocking or _async; any communicator size.  No batches, no triangular mask,
+ * no host staging, no in-place calls.  The plan is the scaled plan of the pair (the tensors and the
+ * rounding mode are arguments of the call): one cached plan serves scaled, amax and MX calls. */
+#define COSTA_MX_ROWS 0
+#define COSTA_MX_COLS 1
+#define COSTA_MX_FLOOR 0
+#define COSTA_MX_CEIL 1
+typedef struct {
+    void* data;           /* device array of E8M0 bytes */
+    int axis;             /* COSTA_MX_ROWS / COSTA_MX_COLS */
+    int64_t block_stride; /* bytes between consecutive blocks of one line */
+    int64_t line_stride;  /* bytes between the same block of consecutive lines */
+} costa_mx_scales_t; /* 32 bytes */
+int costa_hip_transform_mx(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                           const void* beta, const costa_mx_scales_t* a_scales,
+                           const costa_mx_scales_t* c_scales, int rounding, costa_comm_t comm);
+int costa_hip_transform_mx_async(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                                 const void* beta, const costa_mx_scales_t* a_scales,
+                                 const costa_mx_scales_t* c_scales, int rounding, costa_comm_t comm,
+                                 void* stream);
+/* scaled ops (costa_scaled_op_t, as for costa_hip_execute_tiles_scaled) of one accepted MX pair in
+ * ONE launch of mx_kernel; fp32 scalars.  m x n is C's matrix (the target coordinates of the ops);
+ * with a_transposed != 0 A's matrix is n x m and target (i, j) is A's (j, i), so a_scales is indexed
+ * accordingly.  The tile-boundary rule and beta = 0 with c_scales are checked on the ops. */
+int costa_hip_execute_tiles_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
+                               const costa_scaled_op_t* ops, int64_t n_ops, const void* src_base,
+                               void* dst_base, const void* scalars, int n_slots,
+                               const costa_mx_scales_t* a_scales, const costa_mx_scales_t* c_scales,
+                               int rounding, int64_t m, int64_t n, int a_transposed, int device);
+/* sub-tiles run by mx_kernel since the last reset; kept beside costa_stats_t, whose layout does not
+ * change.  costa_hip_scaled_items / costa_hip_amax_items do not count them. */
+int costa_hip_mx_items(int64_t* items, int reset);
+/* the tile-boundary rule alone, on caller-given ops (host only, no GPU): COSTA_OK or COSTA_ERR_ARG */
+int costa_hip_mx_check_ops(const costa_scaled_op_t* ops, int64_t n_ops, int axis, int64_t m, int64_t n);
+/* the stride / aliasing rule of a descriptor for a rows x cols matrix (host only, `data` unused) */
+int costa_hip_mx_check_scales(const costa_mx_scales_t* s, int64_t rows, int64_t cols);
+
 /* ---- stream-ordered variants (MI355X-native; no reference counterpart) ----
  * Enqueue the transform and return.  Layouts must be device-resident.  `stream` (a hipStream_t,
  * may be NULL) is joined at entry and made to wait for the result, so work queued on it after
