@@ -79,8 +79,48 @@ void with_type(costa_dtype_t t, F&& f) {
     case COSTA_BFLOAT16: f(costa::bfloat16_bits{}); return;
     case COSTA_FP8_E4M3: f(costa::fp8_e4m3_bits{}); return;
     case COSTA_FP8_E5M2: f(costa::fp8_e5m2_bits{}); return;
+    // (packed: no element type of its own; fp4_layout() below builds it from a byte layout)
+    case COSTA_FP4_E2M1: f(costa::fp8_e4m3_bits{}); return;
     }
     throw costa::engine::error(COSTA_ERR_ARG, "unknown dtype");
+}
+
+// An FP4_E2M1 layout from the 1-byte layout the builders made of the same arguments (every count in
+// elements): the layout-only part of the evenness rule (costa_hip.h, "MXFP4"), then every block
+// pointer at half its element offset from `base` (block-cyclic; a custom layout's pointers are the
+// caller's byte pointers, base == nullptr).  `sub_off`: the sub-matrix offset along the packed
+// dimension (block-cyclic), else 0.
+void fp4_layout(elayout& e, const char* base, int sub_off) {
+    auto bad = [](const std::string& what) {
+        throw costa::engine::error(COSTA_ERR_ARG, "costa: FP4 pair: an FP4_E2M1 layout must not split a byte: " + what);
+    };
+    const bool packed_rows = e.ordering != 'R';  // 'C': rows share bytes
+    const char* dim = packed_rows ? "row" : "column";
+    const std::vector<int>& split = packed_rows ? e.rows_split : e.cols_split;
+    if (!split.empty() && (split.back() - split.front()) % 2 != 0)
+        bad(std::string("the matrix has ") + std::to_string(split.back() - split.front()) + " " + dim +
+            "s along the packed dimension, [" + std::to_string(split.front()) + ", " + std::to_string(split.back()) +
+            ")");
+    if (sub_off % 2 != 0)
+        bad(std::string("the sub-matrix starts at ") + dim + " " + std::to_string(sub_off) + " (0-based), [" +
+            std::to_string(sub_off) + ", ...)");
+    for (size_t k = 0; k + 1 < split.size(); ++k)
+        if (split[k] % 2 != 0 || split[k + 1] % 2 != 0)
+            bad(std::string("the ") + dim + " interval [" + std::to_string(split[k]) + ", " +
+                std::to_string(split[k + 1]) + ") of its own grid has an odd end");
+    for (auto& b : e.blocks) {
+        const costa::interval& iv = packed_rows ? b.rows : b.cols;
+        if (b.ld % 2 != 0)
+            bad(std::string("ld ") + std::to_string(b.ld) + " of the block at " + dim + "s [" +
+                std::to_string(iv.start) + ", " + std::to_string(iv.end) + ") is odd");
+        if (!base) continue;
+        const std::ptrdiff_t off = b.data - base;  // elements
+        if (off % 2 != 0)
+            bad(std::string("the block at ") + dim + "s [" + std::to_string(iv.start) + ", " +
+                std::to_string(iv.end) + ") starts " + std::to_string(off) + " elements into the local buffer");
+        b.data = const_cast<char*>(base) + off / 2;
+    }
+    e.dtype = COSTA_FP4_E2M1;
 }
 
 scal make_scal(costa_dtype_t t, const void* a, const void* b) {
@@ -203,6 +243,8 @@ int costa_hip_block_cyclic_layout(costa_dtype_t dtype, int m, int n, int block_m
                                                    p_n, rank_grid_ordering, rsrc, csrc,
                                                    static_cast<T*>(ptr), lld, data_ordering, rank);
             h->e = costa::engine::erase(L);
+            if (dtype == COSTA_FP4_E2M1)
+                fp4_layout(h->e, static_cast<const char*>(ptr), h->e.ordering != 'R' ? i - 1 : j - 1);
             costa::engine::set_layout_hash(h->e);  // handles are immutable
         });
         *out = h.release();
@@ -224,6 +266,7 @@ int costa_hip_custom_layout(costa_dtype_t dtype, int rowblocks, int colblocks, c
                                              reinterpret_cast<const costa::block_t*>(localblocks),
                                              ordering);
             h->e = costa::engine::erase(L);
+            if (dtype == COSTA_FP4_E2M1) fp4_layout(h->e, nullptr, 0);
             costa::engine::set_layout_hash(h->e);  // handles are immutable
         });
         *out = h.release();
@@ -697,8 +740,10 @@ int costa_hip_plan_export_scaled(costa_layout_t A, costa_layout_t C, char trans,
         if (nranks < 1 || rank < 0 || rank >= nranks)
             throw costa::engine::error(COSTA_ERR_ARG, "bad rank/size");
         check_handles(1, &A, &C);
-        auto p = costa::engine::make_plan(make_scaled_job(A, C, trans, alpha, beta, nullptr, nullptr), rank,
-                                          nranks);
+        auto jobs = make_scaled_job(A, C, trans, alpha, beta, nullptr, nullptr);
+        // (an FP4 pair has a scaled plan as an MX job only: costa_hip.h, "MXFP4")
+        if (costa::engine::dtype_is_fp4(A->e.dtype) || costa::engine::dtype_is_fp4(C->e.dtype)) jobs[0].mx = true;
+        auto p = costa::engine::make_plan(jobs, rank, nranks);
         info->base.n_local = int64_t(p->local_ops.size());
         info->base.n_pack = int64_t(p->pack_ops.size());
         info->base.n_unpack = int64_t(p->unpack_ops.size());

@@ -56,6 +56,25 @@
 // The staged tile is scaled_kernel's: rows s, pitch 68 dwords, conflict-free as argued there.
 // Whole sub-tiles with both VEC flags take the FULL path; remainders and unaligned sides the guarded
 // one, where elements outside tf x ts count as 0 in every maximum whatever alpha is.  No scratch.
+//
+// Packed e2m1 (COSTA_FP4_E2M1; costa_hip.h, "MXFP4"): the codec q4_e beside q_e<Q>, three more
+// instantiations (f32_e -> q4_e QUANT, q4_e -> f32_e, q4_e -> q4_e QUANT) of the same kernel: the load
+// arrangement, both block reductions, the single barrier per mode, the 2 x 64 scale-byte stores and
+// the FULL / guarded split are shared line for line.  A strip of 4 elements is 2 bytes along the
+// side's stored-contiguous dimension -- f for the source, f for a copy-mode destination, s for a
+// transpose-mode one: the directions the strips already run in -- and holds its 4 codes unpacked, one
+// per byte of strip<uint8_t>, between load_strip4 and store_strip4.  Every element offset the kernel
+// forms on an FP4 side is even (the evenness rule: even ld, even extents; f0, s0, lf and sb are
+// multiples of 4), so elems() halves it exactly.  With the side's VEC flag (first byte at an even
+// address, ld a multiple of 4) a whole strip is one 2-byte access; otherwise one or two byte accesses
+// (ld = 2 mod 4 puts every other line on an odd byte).  A partial strip holds 2 elements: one whole
+// byte.  A destination byte is always written whole, by one lane: no read-modify-write, no atomics.
+// cvt4 is the FP8 codec's round_finite with one mantissa bit and bias 1 (integer rounding to nearest
+// even on the dropped bits, which is the type's tie rule; below 1.0 one exact fp32 addition; the sign
+// bit kept, NaN -> 0x0), w4 a shift and two selects; the gfx950 packed FP4 conversion instructions are
+// not used.  LDS: the codec adds and changes no LDS access -- the staged
+// tile holds fp32 v and `red` fp32 bit patterns exactly as for FP8, so the bank behaviour above
+// stands unchanged.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -88,6 +107,10 @@ template <>
 struct qlim<e5m2_t> {
     static constexpr uint32_t emax = 15, fmax = 0x47600000u;  // 57344
 };
+template <>
+struct qlim<e2m1_t> {
+    static constexpr uint32_t emax = 2, fmax = 0x40C00000u;  // 6
+};
 template <typename E>
 struct q_of {
     using type = e4m3_t;  // (unused for FLOAT destinations)
@@ -96,6 +119,32 @@ template <typename Q>
 struct q_of<q_e<Q>> {
     using type = Q;
 };
+template <>
+struct q_of<q4_e> {
+    using type = e2m1_t;
+};
+
+// element offset -> offset in storage units of the side (packed e2m1: two elements per byte; `at`
+// is even there)
+template <typename E>
+__device__ __forceinline__ int64_t elems(int64_t at) {
+    if constexpr (std::is_same<E, q4_e>::value) return at >> 1;
+    return at;
+}
+// the strip at element offset `at` from p
+template <typename E>
+__device__ __forceinline__ strip<typename E::st> load_at(const typename E::st* p, int64_t at, int n, bool vec_ok) {
+    if constexpr (std::is_same<E, q4_e>::value) return load_strip4(p + (at >> 1), n, vec_ok);
+    return load_strip(p + at, n, vec_ok);
+}
+template <typename E>
+__device__ __forceinline__ void store_at(typename E::st* p, int64_t at, const strip<typename E::st>& v, int n,
+                                         bool vec_ok) {
+    if constexpr (std::is_same<E, q4_e>::value)
+        store_strip4(p + (at >> 1), v, n, vec_ok);
+    else
+        store_strip(p + at, v, n, vec_ok);
+}
 
 __device__ __forceinline__ float pow2(uint32_t E) {
     return u2f(E == 0 ? 0x00400000u : E == 255 ? 0x7FC00000u : E << 23);
@@ -148,7 +197,7 @@ __device__ __forceinline__ void run_mx(const costa_scaled_op_t& sop, int f0, int
     const int64_t F0 = int64_t(frow ? sop.row0 : sop.col0) + f0, S0 = int64_t(frow ? sop.col0 : sop.row0) + s0;
     const bool sa_f = sa.rows == frow;  // A's blocks run along f
     const bool cf = sc.rows == frow;    // C's blocks run along f (QUANT)
-    const Ss* src = reinterpret_cast<const Ss*>(src_base + op.src) + int64_t(s0) * lds + f0;
+    const Ss* src = reinterpret_cast<const Ss*>(src_base + op.src) + elems<Es>(int64_t(s0) * lds + f0);
     const int t = int(threadIdx.x), lane = t % 64, wave = t / 64;
 
     // ---- load phase: lane -> (strip along f, column s); all loads issued first
@@ -160,7 +209,7 @@ __device__ __forceinline__ void run_mx(const costa_scaled_op_t& sop, int f0, int
     for (int k = 0; k < SPL; ++k) {
         const int s = c0 + k * SCPP;
         x[k] = strip<Ss>{};
-        if (FULL || (nf_lane > 0 && s < ts)) x[k] = load_strip(src + s * lds + lf, nf_lane, vs);
+        if (FULL || (nf_lane > 0 && s < ts)) x[k] = load_at<Es>(src, s * lds + lf, nf_lane, vs);
     }
     // the input scale bytes (default cache policy); elements outside the sub-tile take 127 (1.0)
     [[maybe_unused]] uint32_t sab[SPL][SV];
@@ -187,7 +236,8 @@ __device__ __forceinline__ void run_mx(const costa_scaled_op_t& sop, int f0, int
         }
     }
     const bool tr = flags & COSTA_TILE_TRANSPOSE;
-    Sd* dst = reinterpret_cast<Sd*>(dst_base + op.dst) + (tr ? int64_t(f0) * ldd + s0 : int64_t(s0) * ldd + f0);
+    Sd* dst = reinterpret_cast<Sd*>(dst_base + op.dst) +
+              elems<Ed>(tr ? int64_t(f0) * ldd + s0 : int64_t(s0) * ldd + f0);
     // store unit k of this lane in transpose mode (as scaled_kernel): after the lane exchange lane
     // (base + j) stores f = q*4 + j for s = base .. base + 3
     const int j = lane & (SV - 1);
@@ -304,7 +354,7 @@ __device__ __forceinline__ void run_mx(const costa_scaled_op_t& sop, int f0, int
                 }
                 o.e[e] = Ed::narrow(v);
             }
-            store_strip(dst + s * ldd + lf, o, nf_lane, vd);
+            store_at<Ed>(dst, s * ldd + lf, o, nf_lane, vd);
         }
         if constexpr (QUANT) {
             if (cf) __syncthreads();  // (after the stores: no wavefront waits before it stores)
@@ -349,7 +399,7 @@ __device__ __forceinline__ void run_mx(const costa_scaled_op_t& sop, int f0, int
             }
             o.e[e] = Ed::narrow(v);
         }
-        store_strip(dst + f * ldd + sb, o, n_s, vd);
+        store_at<Ed>(dst, f * ldd + sb, o, n_s, vd);
     }
 }
 
@@ -394,22 +444,22 @@ void launch_inst(const costa_scaled_op_t* d_ops, const uint64_t* d_work, const s
                                                                      sa, sc, int(ceil));
 }
 
-template <typename Q>
+template <typename EQ>  // the codec of the pair's narrow type: q_e<Q> or q4_e
 void launch_q(bool src_f, bool dst_f, const costa_scaled_op_t* d_ops, const uint64_t* d_work, const strip_list& l,
               const char* src_base, char* dst_base, const void* d_scalars, const mx_side& sa, const mx_side& sc,
               bool ceil, hipStream_t s) {
     if (src_f)
-        launch_inst<f32_e, q_e<Q>, true>(d_ops, d_work, l, src_base, dst_base, d_scalars, sa, sc, ceil, s);
+        launch_inst<f32_e, EQ, true>(d_ops, d_work, l, src_base, dst_base, d_scalars, sa, sc, ceil, s);
     else if (dst_f)
-        launch_inst<q_e<Q>, f32_e, false>(d_ops, d_work, l, src_base, dst_base, d_scalars, sa, sc, ceil, s);
+        launch_inst<EQ, f32_e, false>(d_ops, d_work, l, src_base, dst_base, d_scalars, sa, sc, ceil, s);
     else
-        launch_inst<q_e<Q>, q_e<Q>, true>(d_ops, d_work, l, src_base, dst_base, d_scalars, sa, sc, ceil, s);
+        launch_inst<EQ, EQ, true>(d_ops, d_work, l, src_base, dst_base, d_scalars, sa, sc, ceil, s);
 }
 
 }  // namespace
 
 bool mx_pair(costa_dtype_t src, costa_dtype_t dst) {
-    return fp8_pair(src, dst);  // FLOAT -> Q, Q -> FLOAT, Q -> Q of one Q
+    return fp8_pair(src, dst) || fp4_pair(src, dst);  // FLOAT -> Q, Q -> FLOAT, Q -> Q of one Q
 }
 
 void launch_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* d_ops,
@@ -423,10 +473,13 @@ void launch_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_sca
     if ((a_scales.data != nullptr) == src_f || (c_scales.data != nullptr) == dst_f)
         throw error(COSTA_ERR_ARG, "costa: an MX launch needs a scale tensor exactly on its FP8 sides");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if ((src_f ? dst_dtype : src_dtype) == COSTA_FP8_E4M3)
-        launch_q<e4m3_t>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, a_scales, c_scales, ceil, s);
+    const costa_dtype_t nt = src_f ? dst_dtype : src_dtype;
+    if (nt == COSTA_FP8_E4M3)
+        launch_q<q_e<e4m3_t>>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, a_scales, c_scales, ceil, s);
+    else if (nt == COSTA_FP8_E5M2)
+        launch_q<q_e<e5m2_t>>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, a_scales, c_scales, ceil, s);
     else
-        launch_q<e5m2_t>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, a_scales, c_scales, ceil, s);
+        launch_q<q4_e>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, a_scales, c_scales, ceil, s);
 }
 
 }  // namespace engine

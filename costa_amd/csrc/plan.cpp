@@ -39,17 +39,29 @@ size_t dtype_size(costa_dtype_t t) {
     case COSTA_BFLOAT16: return 2;
     case COSTA_FP8_E4M3: return 1;
     case COSTA_FP8_E5M2: return 1;
+    // (half a byte: elem_size() says it; whoever asks for whole bytes does not take the type)
+    case COSTA_FP4_E2M1:
+        throw error(COSTA_ERR_ARG, "costa: FP4_E2M1 elements are half a byte: only the MX entry points "
+                                   "(costa_hip_transform_mx, costa_hip_execute_tiles_mx) take them");
     }
     throw error(COSTA_ERR_ARG, "unknown dtype");
 }
+
+esize elem_size(costa_dtype_t t) { return dtype_is_fp4(t) ? esize::packed4() : esize(dtype_size(t)); }
+size_t pkg_unit_size(costa_dtype_t pkg) { return dtype_is_fp4(pkg) ? 1 : dtype_size(pkg); }
+int64_t pkg_units(costa_dtype_t pkg, int64_t elems) { return dtype_is_fp4(pkg) ? elems / 2 : elems; }
 
 bool dtype_is_complex(costa_dtype_t t) { return t == COSTA_CFLOAT || t == COSTA_CDOUBLE; }
 bool dtype_is_half(costa_dtype_t t) { return t == COSTA_HALF || t == COSTA_BFLOAT16; }
 
 bool dtype_is_fp8(costa_dtype_t t) { return t == COSTA_FP8_E4M3 || t == COSTA_FP8_E5M2; }
+bool dtype_is_fp4(costa_dtype_t t) { return t == COSTA_FP4_E2M1; }
 
 costa_dtype_t compute_dtype(costa_dtype_t src, costa_dtype_t dst) {
-    return dtype_is_half(src) || dtype_is_half(dst) || dtype_is_fp8(src) || dtype_is_fp8(dst) ? COSTA_FLOAT : dst;
+    return dtype_is_half(src) || dtype_is_half(dst) || dtype_is_fp8(src) || dtype_is_fp8(dst) ||
+                   dtype_is_fp4(src) || dtype_is_fp4(dst)
+               ? COSTA_FLOAT
+               : dst;
 }
 
 bool half_pair(costa_dtype_t src, costa_dtype_t dst) {
@@ -60,6 +72,10 @@ bool half_pair(costa_dtype_t src, costa_dtype_t dst) {
 bool fp8_pair(costa_dtype_t src, costa_dtype_t dst) {
     return (dtype_is_fp8(src) && (dst == src || dst == COSTA_FLOAT)) ||
            (src == COSTA_FLOAT && dtype_is_fp8(dst));
+}
+
+bool fp4_pair(costa_dtype_t src, costa_dtype_t dst) {
+    return (dtype_is_fp4(src) && (dst == src || dst == COSTA_FLOAT)) || (src == COSTA_FLOAT && dtype_is_fp4(dst));
 }
 
 bool wide_pair(costa_dtype_t src, costa_dtype_t dst) {
@@ -82,12 +98,13 @@ const char* dtype_name(costa_dtype_t t) {
     case COSTA_BFLOAT16: return "BFLOAT16";
     case COSTA_FP8_E4M3: return "FP8_E4M3";
     case COSTA_FP8_E5M2: return "FP8_E5M2";
+    case COSTA_FP4_E2M1: return "FP4_E2M1";
     }
     return "unknown";
 }
 
 costa_dtype_t plan_pkg_dtype(costa_dtype_t src, costa_dtype_t dst) {
-    if (fp8_pair(src, dst)) return src;
+    if (fp8_pair(src, dst) || fp4_pair(src, dst)) return src;
     return dtype_size(src) < dtype_size(dst) ? src : dst;
 }
 
@@ -117,6 +134,12 @@ bool any_mixed(const std::vector<job>& jobs) {
 bool any_half(const std::vector<job>& jobs) {
     for (const job& jb : jobs)
         if (jb.A && jb.C && (dtype_is_half(jb.A->dtype) || dtype_is_half(jb.C->dtype))) return true;
+    return false;
+}
+
+bool any_fp4(const std::vector<job>& jobs) {
+    for (const job& jb : jobs)
+        if (jb.A && jb.C && (dtype_is_fp4(jb.A->dtype) || dtype_is_fp4(jb.C->dtype))) return true;
     return false;
 }
 
@@ -230,6 +253,26 @@ struct view {
     }
 };
 
+// The evenness rule of an FP4 layout's tile (costa_hip.h, "MXFP4"): the target-coordinate rectangle
+// rr x cc of block b of L (seen transposed when `t`) starts at an even element offset from the block's
+// pointer and has an even extent along L's stored-contiguous (packed) dimension.
+void check_fp4_tile(const elayout& L, const eblock& b, bool t, const interval& rr, const interval& cc) {
+    const bool packed_rows = L.ordering != 'R';             // 'C': rows share bytes
+    const interval& own_r = t ? cc : rr;                    // back to L's own coordinates
+    const interval& own_c = t ? rr : cc;
+    const interval& iv = packed_rows ? own_r : own_c;
+    const int at = iv.start - (packed_rows ? b.rows.start : b.cols.start);
+    if (at % 2 == 0 && (iv.end - iv.start) % 2 == 0 && b.ld % 2 == 0) return;
+    throw error(COSTA_ERR_ARG,
+                std::string("costa: FP4 pair: a tile splits a byte of the FP4_E2M1 layout: its ") +
+                    (packed_rows ? "rows [" : "columns [") + std::to_string(iv.start) + ", " +
+                    std::to_string(iv.end) + ") start " + std::to_string(at) + " elements into the block at [" +
+                    std::to_string(packed_rows ? b.rows.start : b.cols.start) +
+                    ", ...) (ld " + std::to_string(b.ld) +
+                    "); offsets, extents and ld along the packed dimension must be even, which makes the "
+                    "other layout's split points count through op");
+}
+
 // decompose every local block of `src` (seen through `sv`) by the grid of `dst` (seen
 // through `dv`) and append the tiles (utils.hpp:26-115)
 // Under a mask each intersection tile is classified in target coordinates: wholly dropped tiles
@@ -240,7 +283,8 @@ struct view {
 // the same tiles with the same sort keys.
 void decompose(const view& sv, const view& dv, int tag, const tri_mask& mk, std::vector<side_tile>& out) {
     out.reserve(out.size() + sv.L->blocks.size() * 4);
-    const size_t elem = dtype_size(sv.L->dtype);  // of the layout being decomposed
+    const esize elem = elem_size(sv.L->dtype);  // of the layout being decomposed
+    const bool fp4 = dtype_is_fp4(sv.L->dtype);
     const auto& drs = dv.rsplit();
     const auto& dcs = dv.csplit();
     if (sv.rsplit().back() != drs.back() || sv.csplit().back() != dcs.back())
@@ -261,6 +305,7 @@ void decompose(const view& sv, const view& dv, int tag, const tri_mask& mk, std:
                 if (r.empty()) continue;
                 const int peer = dv.owner(i, j);
                 auto emit = [&](const interval& rr, const interval& cc, bool edge) {
+                    if (fp4) check_fp4_tile(*sv.L, b, sv.t, rr, cc);  // no tile may split a byte
                     // back to the stored orientation of the block (block.cpp:85-99)
                     const tile_side ts = sub_tile(reinterpret_cast<uint64_t>(b.data), b.ld, b.rows.start,
                                                   b.cols.start, row_major, sv.t, rr.start, rr.end,
@@ -340,6 +385,7 @@ uint32_t scale_kind(costa_dtype_t dtype, const scal& s, bool copy_mode, bool con
     // 1-byte types: the same
     case COSTA_FP8_E4M3: return kind_t<float>(s, copy_mode, conj);
     case COSTA_FP8_E5M2: return kind_t<float>(s, copy_mode, conj);
+    case COSTA_FP4_E2M1: return kind_t<float>(s, copy_mode, conj);
     }
     throw error(COSTA_ERR_ARG, "unknown dtype");
 }
@@ -372,7 +418,16 @@ std::vector<job_params> check_jobs(const std::vector<job>& jobs, int n_ranks, co
     if (jobs.size() > 0xFFFF) throw error(COSTA_ERR_ARG, "costa::transform: too many layout pairs");
     src_dtype = jobs[0].A->dtype;
     dtype = jobs[0].C->dtype;
-    if (any_scaled(jobs)) {  // scaled transforms: their own set of pairs, one unmasked layout pair
+    if (any_fp4(jobs)) {  // packed e2m1: the MX transforms alone, one of their three pairs
+        if (!(jobs.size() == 1 && jobs[0].mx))
+            throw error(COSTA_ERR_ARG, std::string("costa::transform: FP4_E2M1 layouts are taken by "
+                                                   "costa_hip_transform_mx alone, not ") +
+                                           dtype_name(src_dtype) + " (A) -> " + dtype_name(dtype) +
+                                           " (C) here");
+        if (!fp4_pair(src_dtype, dtype))
+            throw error(COSTA_ERR_ARG, std::string("costa_hip_transform_mx: no MX transform for ") +
+                                           dtype_name(src_dtype) + " -> " + dtype_name(dtype));
+    } else if (any_scaled(jobs)) {  // scaled transforms: their own set of pairs, one unmasked layout pair
         if (!scaled_pair(src_dtype, dtype))
             throw error(COSTA_ERR_ARG,
                         std::string("costa::transform_scaled: no scaled transform for ") +
@@ -390,6 +445,7 @@ std::vector<job_params> check_jobs(const std::vector<job>& jobs, int n_ranks, co
     // (half precision: H -> H, FLOAT -> H, H -> FLOAT, computed in fp32; FP8: the same three shapes)
     const bool pair_ok =
         src_dtype == dtype || half_pair(src_dtype, dtype) || fp8_pair(src_dtype, dtype) ||
+        fp4_pair(src_dtype, dtype) ||
         (src_dtype == COSTA_FLOAT && dtype == COSTA_DOUBLE) || (src_dtype == COSTA_DOUBLE && dtype == COSTA_FLOAT) ||
         (src_dtype == COSTA_CFLOAT && dtype == COSTA_CDOUBLE) || (src_dtype == COSTA_CDOUBLE && dtype == COSTA_CFLOAT);
     if (!pair_ok)
@@ -464,9 +520,13 @@ std::unique_ptr<plan> make_plan(const std::vector<job>& jobs, int rank, int n_ra
     // narrowing pairs convert in PACK, widening pairs in UNPACK); all equal for same-type plans.
     // FP8 pairs carry A's type, FLOAT -> Q too: its source is not rounded before the arithmetic,
     // which happens in UNPACK
-    const size_t EA = dtype_size(p->src_dtype), EC = dtype_size(p->dtype);
+    // (an FP4 side is half a byte per element: esize; a packed package -- A holds FP4 -- is counted
+    // in BYTES, `units`, so that no count, displacement or round boundary falls inside a byte)
+    const esize EA = elem_size(p->src_dtype), EC = elem_size(p->dtype);
     p->pkg_dtype = plan_pkg_dtype(p->src_dtype, p->dtype);
-    const size_t EP = dtype_size(p->pkg_dtype);
+    const esize EP = elem_size(p->pkg_dtype);
+    const bool packed_pkg = dtype_is_fp4(p->pkg_dtype);
+    auto units = [&](int64_t elems) { return pkg_units(p->pkg_dtype, elems); };
     std::vector<side_tile> send, recv;
     for (const job& jb : jobs) p->slots.push_back(jb.s);
     // prepare_to_send and prepare_to_recv are independent: the receive side runs on a second
@@ -544,11 +604,16 @@ std::unique_ptr<plan> make_plan(const std::vector<job>& jobs, int rank, int n_ra
             continue;
         }
         const tag_info& ti = tags[size_t(m.tag)];
-        const int64_t n = int64_t(m.n_rows) * m.n_cols;
+        const int64_t n = units(int64_t(m.n_rows) * m.n_cols);
         // copy_to_buffer: stored shape and ordering, dense, no transform (cpp:191-217)
-        p->pack_ops.push_back(make_tile_op(m.n_rows, m.n_cols, uint64_t(m.ptr), m.ld, ti.a_cm,
-                                           uint64_t(off) * EP, 0, ti.a_cm, false, false,
-                                           COSTA_SCALE_BITCOPY, 0, EA, EP));
+        if (packed_pkg)  // a copy of bytes: half the extent and half the pitch along the packed dimension
+            p->pack_ops.push_back(tile_op(ti.a_cm ? m.n_rows / 2 : m.n_rows, ti.a_cm ? m.n_cols : m.n_cols / 2,
+                                          uint64_t(m.ptr), m.ld / 2, ti.a_cm, uint64_t(off), 0, ti.a_cm, false,
+                                          false, COSTA_SCALE_BITCOPY, 0, 1, 1));
+        else
+            p->pack_ops.push_back(tile_op(m.n_rows, m.n_cols, uint64_t(m.ptr), m.ld, ti.a_cm,
+                                          EP.bytes(uint64_t(off)), 0, ti.a_cm, false, false,
+                                          COSTA_SCALE_BITCOPY, 0, EA, EP));
         at_pack.push_back(&m);
         p->send_counts[size_t(m.peer)] += n;
         off += n;
@@ -564,15 +629,15 @@ std::unique_ptr<plan> make_plan(const std::vector<job>& jobs, int rank, int n_ra
             continue;
         }
         const tag_info& ti = tags[size_t(m.tag)];
-        const int64_t n = int64_t(m.n_rows) * m.n_cols;
+        const int64_t n = units(int64_t(m.n_rows) * m.n_cols);
         // copy_from_buffer(idx): the buffer holds the tile in A's stored shape/ordering
         // (cpp:219-244); dims swapped back when transposing
         const int nr = ti.transpose ? m.n_cols : m.n_rows;
         const int nc = ti.transpose ? m.n_rows : m.n_cols;
         const bool wt = will_tr(ti, ti.a_cm, ti.c_cm);
-        const costa_tile_op_t op = make_tile_op(nr, nc, uint64_t(off) * EP, 0, ti.a_cm, uint64_t(m.ptr),
-                                                m.ld, ti.c_cm, ti.transpose, ti.conj, kind_of(ti, wt),
-                                                uint32_t(m.tag), EP, EC);
+        const costa_tile_op_t op = tile_op(nr, nc, packed_pkg ? uint64_t(off) : EP.bytes(uint64_t(off)), 0, ti.a_cm,
+                                           uint64_t(m.ptr), m.ld, ti.c_cm, ti.transpose, ti.conj, kind_of(ti, wt),
+                                           uint32_t(m.tag), EP, EC);
         if (m.edge) {
             p->unpack_tri.push_back(edge_op(op, m, ti));
         } else {
@@ -595,9 +660,9 @@ std::unique_ptr<plan> make_plan(const std::vector<job>& jobs, int rank, int n_ra
             throw error(COSTA_ERR_INTERNAL, "costa: local tiles do not pair up");
         const tag_info& ti = tags[size_t(s.tag)];
         const bool wt = will_tr(ti, ti.a_cm, ti.c_cm);
-        const costa_tile_op_t op = make_tile_op(s.n_rows, s.n_cols, uint64_t(s.ptr), s.ld, ti.a_cm,
-                                                uint64_t(d.ptr), d.ld, ti.c_cm, ti.transpose, ti.conj,
-                                                kind_of(ti, wt), uint32_t(s.tag), EA, EC);
+        const costa_tile_op_t op = tile_op(s.n_rows, s.n_cols, uint64_t(s.ptr), s.ld, ti.a_cm,
+                                           uint64_t(d.ptr), d.ld, ti.c_cm, ti.transpose, ti.conj,
+                                           kind_of(ti, wt), uint32_t(s.tag), EA, EC);
         if (d.edge) {
             p->local_tri.push_back(edge_op(op, d, ti));
             p->local_elems += tri_kept(p->local_tri.back());
@@ -617,7 +682,8 @@ std::unique_ptr<plan> make_plan(const std::vector<job>& jobs, int rank, int n_ra
     set_order(p->local_ops, at_local);
     // algorithmic bytes: each side of an op at its own element size
     for (auto& op : p->local_ops) p->local_bytes += op_alg_bytes(op, EA, EC);
-    for (auto& op : p->pack_ops) p->pack_bytes += op_alg_bytes(op, EA, EP);
+    for (auto& op : p->pack_ops)  // (a packed package's pack ops are byte ops)
+        p->pack_bytes += packed_pkg ? op_alg_bytes(op, 1, 1) : op_alg_bytes(op, EA, EP);
     for (auto& op : p->unpack_ops) p->unpack_bytes += op_alg_bytes(op, EP, EC);
     for (auto& t : p->local_tri) p->local_bytes += op_alg_bytes(t, EC);  // kept elements only
     for (auto& t : p->unpack_tri) p->unpack_bytes += op_alg_bytes(t, EC);

@@ -549,14 +549,18 @@ strip_list build_scaled_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
                              const std::vector<costa_scaled_op_t>& ops, uint64_t src_base,
                              uint64_t dst_base, std::vector<costa_scaled_op_t>& ordered,
                              std::vector<uint64_t>& work, bool dst_order) {
-    const uint64_t ES = dtype_size(src_dtype), ED = dtype_size(dst_dtype);
+    // (a packed FP4 side of an MX pair: half a byte per element, its strip of 4 is 2 bytes)
+    const esize ES = elem_size(src_dtype), ED = elem_size(dst_dtype);
+    strip_align al = strip_alignment(strip_family::scaled, std::max<uint64_t>(1, ES.hb / 2), std::max<uint64_t>(1, ED.hb / 2));
+    if (dtype_is_fp4(src_dtype)) al.src = 2;
+    if (dtype_is_fp4(dst_dtype)) al.dst = 2;
     for (const costa_scaled_op_t& t : ops) {  // (empty ops are skipped unchecked, as by the builder)
         if (t.op.nf <= 0 || t.op.ns <= 0) continue;
         if (t.op.lds < 0 || t.op.ldd < 0) throw error(COSTA_ERR_ARG, "costa: negative leading dimension");
         if (t.row0 < 0 || t.col0 < 0) throw error(COSTA_ERR_ARG, "costa: negative target coordinate");
     }
-    return build_strip_work("scaled", ops, src_base, dst_base, SBF, SBS, ES, ED,
-                            strip_alignment(strip_family::scaled, ES, ED), ordered, work, all_listed(), dst_order);
+    return build_strip_work("scaled", ops, src_base, dst_base, SBF, SBS, ES, ED, al, ordered, work, all_listed(),
+                            dst_order);
 }
 
 void launch_scaled(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* d_ops,

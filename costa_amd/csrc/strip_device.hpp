@@ -59,6 +59,14 @@ struct q_e {
     static __device__ __forceinline__ float widen(uint8_t b) { return Q::widen(b); }
     static __device__ __forceinline__ uint8_t narrow(float x) { return uint8_t(Q::narrow(x)); }
 };
+// packed e2m1 (COSTA_FP4_E2M1): a strip<uint8_t> holds 4 unpacked codes, one per byte; two codes
+// share a stored byte (load_strip4 / store_strip4 below)
+struct q4_e {
+    using st = uint8_t;
+    using ct = float;
+    static __device__ __forceinline__ float widen(uint8_t c) { return e2m1_t::widen(c); }
+    static __device__ __forceinline__ uint8_t narrow(float x) { return uint8_t(e2m1_t::narrow(x)); }
+};
 template <typename H>  // the FLOAT source of a FLOAT -> H pair: rounded to H first
 struct f32_via {
     using st = float;
@@ -126,6 +134,33 @@ __device__ __forceinline__ void store_strip(S* p, const strip<S>& in, int n, boo
 #pragma unroll
         for (int k = 0; k < SV; ++k)
             if (k < n) p[k] = in.e[k];
+    }
+}
+
+// a strip of 4 packed e2m1 codes: 2 bytes at p, the even element in bits 3..0.  One 2-byte access
+// where `vec_ok` (p is 2-byte aligned on every line of the side) and the strip is whole, else a byte
+// per pair of elements; n is even (the evenness rule), so a byte is read or written whole
+__device__ __forceinline__ strip<uint8_t> load_strip4(const uint8_t* p, int n, bool vec_ok) {
+    strip<uint8_t> out{};
+    uint32_t v = 0;
+    if (vec_ok && n >= SV) {
+        v = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(p));
+    } else {
+        if (n >= 2) v = p[0];
+        if (n >= SV) v |= uint32_t(p[1]) << 8;
+    }
+#pragma unroll
+    for (int k = 0; k < SV; ++k) out.e[k] = uint8_t(v >> (4 * k) & 15u);
+    return out;
+}
+__device__ __forceinline__ void store_strip4(uint8_t* p, const strip<uint8_t>& in, int n, bool vec_ok) {
+    const uint32_t lo = uint32_t(in.e[0] & 15u) | uint32_t(in.e[1] & 15u) << 4;
+    const uint32_t hi = uint32_t(in.e[2] & 15u) | uint32_t(in.e[3] & 15u) << 4;
+    if (vec_ok && n >= SV) {
+        __builtin_nontemporal_store(uint16_t(lo | hi << 8), reinterpret_cast<uint16_t*>(p));
+    } else {
+        if (n >= 2) p[0] = uint8_t(lo);
+        if (n >= SV) p[1] = uint8_t(hi);
     }
 }
 

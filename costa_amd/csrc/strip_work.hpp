@@ -24,6 +24,7 @@ namespace engine {
 //   FP8 with FLOAT              4                     4 on the 1-byte side, 16 on fp32
 //   Q -> Q                      16 (its whole copies) 16                   16
 //   scaled pair                 4                     min(16, 4 x element size)
+//   MX pair with packed FP4     4                     2 on the FP4 side (a strip is 2 bytes)
 //   tri                         16 / element          16                   16
 enum class strip_family { pair, scaled, tri };
 struct strip_align {
@@ -56,7 +57,7 @@ struct all_listed {
 // build_work dst_order).  `what` names the list in the error text.
 template <bool WHOLE_BIT = false, typename Op, typename SubOf = all_listed>
 strip_list build_strip_work(const char* what, const std::vector<Op>& ops, uint64_t src_base, uint64_t dst_base,
-                            int bf_, int bs_, uint64_t es, uint64_t ed, strip_align align,
+                            int bf_, int bs_, esize es, esize ed, strip_align align,
                             std::vector<Op>& ordered, std::vector<uint64_t>& work, SubOf sub_of = SubOf(),
                             bool dst_order = false) {
     const int64_t bf = bf_, bs = bs_;
@@ -72,9 +73,9 @@ strip_list build_strip_work(const char* what, const std::vector<Op>& ops, uint64
         Op t = in;
         costa_tile_op_t& op = tile_of(t);
         op.flags &= ~uint32_t(COSTA_TILE_VEC_SRC | COSTA_TILE_VEC_DST);
-        if ((src_base + op.src) % align.src == 0 && (uint64_t(op.lds) * es) % align.src == 0)
+        if ((src_base + op.src) % align.src == 0 && es.bytes(uint64_t(op.lds)) % align.src == 0)
             op.flags |= COSTA_TILE_VEC_SRC;
-        if ((dst_base + op.dst) % align.dst == 0 && (uint64_t(op.ldd) * ed) % align.dst == 0)
+        if ((dst_base + op.dst) % align.dst == 0 && ed.bytes(uint64_t(op.ldd)) % align.dst == 0)
             op.flags |= COSTA_TILE_VEC_DST;
         const uint64_t idx = ordered.size();
         const int64_t nbf = (int64_t(op.nf) + bf - 1) / bf, nbs = (int64_t(op.ns) + bs - 1) / bs;
@@ -99,7 +100,7 @@ strip_list build_strip_work(const char* what, const std::vector<Op>& ops, uint64
             const uint64_t q = (work[x] & 0xFFFFFFFFull) >> SHIFT, nbf = uint64_t((op.nf + bf - 1) / bf);
             const int64_t f0 = int64_t(q % nbf) * bf, s0 = int64_t(q / nbf) * bs;
             const int64_t at = op.flags & COSTA_TILE_TRANSPOSE ? f0 * op.ldd + s0 : s0 * op.ldd + f0;
-            key[x] = {op.dst + uint64_t(at) * ed, work[x]};
+            key[x] = {op.dst + ed.bytes(uint64_t(at)), work[x]};
         }
         std::stable_sort(key.begin(), key.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
         for (size_t x = 0; x < key.size(); ++x) work[x] = key[x].second;

@@ -387,6 +387,28 @@ struct e5m2_t {  // OCP e5m2: bias 15, the high byte of IEEE binary16
     }
 };
 
+// The packed 4-bit type (costa_hip.h, "MXFP4"): one OCP e2m1 code, bit 3 the sign, bits 2..1 the
+// exponent (bias 1), bit 0 the mantissa; magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6; no inf, no NaN.
+struct e2m1_t {
+    // w4: the 3 magnitude bits shifted to fp32's exponent / mantissa boundary are the value / 2^126
+    // for the normal codes (2 .. 7); code 1 is the one subnormal, 0.5
+    static __device__ __forceinline__ float widen(uint32_t c) {
+        const uint32_t m = c & 7u;
+        const uint32_t a = m >= 2u ? (m << 22) + (126u << 23) : m ? 0x3F000000u : 0u;
+        return u2f(a | ((c & 8u) << 28));
+    }
+    // cvt4 of a finite t with |t| <= 6 (the caller clamps, so nothing overflows): round_finite with 1
+    // mantissa bit and bias 1, whose round-to-nearest-even IS the tie rule of the type -- a tie goes to
+    // the code whose mantissa bit is 0 (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4,
+    // 5 -> 4); below 1.0 the one exact addition of 2^22 rounds to the subnormal step 0.5.  The sign bit
+    // is always kept; NaN -> 0x0
+    static __device__ __forceinline__ uint32_t narrow(float x) {
+        const uint32_t u = f2u(x), a = u & 0x7FFFFFFFu;
+        if (a > 0x7F800000u) return 0u;
+        return (u >> 28 & 8u) | round_finite<1, 1>(a);
+    }
+};
+
 }  // namespace
 }  // namespace engine
 }  // namespace costa

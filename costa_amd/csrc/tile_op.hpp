@@ -16,6 +16,20 @@
 namespace costa {
 namespace engine {
 
+// The size of one element of a side, in half-bytes: COSTA_FP4_E2M1 packs two elements into a byte
+// (costa_hip.h, "MXFP4"), so no byte count says it.  A plain byte count converts implicitly; bytes(n)
+// is exact for an FP4 side because the evenness rule keeps every n it is asked about even.
+struct esize {
+    uint64_t hb;  // half-bytes per element
+    COSTA_HD constexpr esize(uint64_t bytes) : hb(2 * bytes) {}
+    COSTA_HD static constexpr esize packed4() {
+        esize e(0);
+        e.hb = 1;
+        return e;
+    }
+    COSTA_HD constexpr uint64_t bytes(uint64_t n) const { return n * hb / 2; }
+};
+
 // The stored-orientation sub-tile of a block for the target-coordinate rectangle
 // [r0, r1) x [c0, c1) of a view that is transposed when `t` (block.cpp:72-111).
 struct tile_side {
@@ -26,13 +40,13 @@ struct tile_side {
 
 COSTA_HD inline tile_side sub_tile(uint64_t data, int ld, int block_row0, int block_col0,
                                    bool row_major, bool t, int r0, int r1, int c0, int c1,
-                                   uint64_t elem) {
+                                   esize elem) {
     // back to the stored orientation of the block
     const int sr0 = t ? c0 : r0, sr1 = t ? c1 : r1;
     const int sc0 = t ? r0 : c0, sc1 = t ? r1 : c1;
     const int64_t dr = sr0 - block_row0, dc = sc0 - block_col0;
     const int64_t off = row_major ? dr * ld + dc : dc * ld + dr;
-    return {data + uint64_t(off * int64_t(elem)), ld, sr1 - sr0, sc1 - sc0};
+    return {data + uint64_t(off * int64_t(elem.hb) / 2), ld, sr1 - sr0, sc1 - sc0};
 }
 
 // copy_and_transform (memory_utils.hpp:339-412) as one op: an ordering mismatch is itself a
@@ -43,7 +57,7 @@ COSTA_HD inline tile_side sub_tile(uint64_t data, int ld, int block_row0, int bl
 COSTA_HD inline costa_tile_op_t tile_op(int n_rows, int n_cols, uint64_t src, int src_stride,
                                         bool src_cm, uint64_t dst, int dst_stride, bool dst_cm,
                                         bool transpose, bool conj, uint32_t kind, uint32_t slot,
-                                        uint64_t src_elem, uint64_t dst_elem) {
+                                        esize src_elem, esize dst_elem) {
     const bool will_transpose = (transpose && src_cm == dst_cm) || (!transpose && src_cm != dst_cm);
     if (dst_stride == 0) {
         const int r = will_transpose ? n_cols : n_rows, c = will_transpose ? n_rows : n_cols;
@@ -60,15 +74,15 @@ COSTA_HD inline costa_tile_op_t tile_op(int n_rows, int n_cols, uint64_t src, in
     if (will_transpose && kind == COSTA_SCALE_BITCOPY) kind = COSTA_SCALE_ALPHA;  // never memcpy
     op.flags = (will_transpose ? COSTA_TILE_TRANSPOSE : 0u) | (conj ? COSTA_TILE_CONJ : 0u) |
                (kind << COSTA_SCALE_SHIFT) | (slot << COSTA_SLOT_SHIFT);
-    if (src % 16 == 0 && (uint64_t(src_stride) * src_elem) % 16 == 0) op.flags |= COSTA_TILE_VEC_SRC;
-    if (dst % 16 == 0 && (uint64_t(dst_stride) * dst_elem) % 16 == 0) op.flags |= COSTA_TILE_VEC_DST;
+    if (src % 16 == 0 && src_elem.bytes(uint64_t(src_stride)) % 16 == 0) op.flags |= COSTA_TILE_VEC_SRC;
+    if (dst % 16 == 0 && dst_elem.bytes(uint64_t(dst_stride)) % 16 == 0) op.flags |= COSTA_TILE_VEC_DST;
     return op;
 }
 
 COSTA_HD inline costa_tile_op_t tile_op(int n_rows, int n_cols, uint64_t src, int src_stride,
                                         bool src_cm, uint64_t dst, int dst_stride, bool dst_cm,
                                         bool transpose, bool conj, uint32_t kind, uint32_t slot,
-                                        uint64_t elem) {
+                                        esize elem) {
     return tile_op(n_rows, n_cols, src, src_stride, src_cm, dst, dst_stride, dst_cm, transpose, conj,
                    kind, slot, elem, elem);
 }
@@ -128,23 +142,23 @@ COSTA_HD inline int64_t tri_kept(const costa_tri_op_t& t) {
 }
 
 // algorithmic HBM bytes of one op: read + write (+ read of the target when beta != 0)
-COSTA_HD inline int64_t op_alg_bytes(const costa_tile_op_t& op, uint64_t elem) {
+COSTA_HD inline int64_t op_alg_bytes(const costa_tile_op_t& op, esize elem) {
     const uint32_t k = (op.flags & COSTA_SCALE_MASK) >> COSTA_SCALE_SHIFT;
     const int64_t n = int64_t(op.nf) * op.ns;
-    return int64_t(elem) * n * (1 + (k != COSTA_SCALE_ZERO) + (k == COSTA_SCALE_AXPBY));
+    return int64_t(elem.bytes(uint64_t(n))) * (1 + (k != COSTA_SCALE_ZERO) + (k == COSTA_SCALE_AXPBY));
 }
 // ... of a converting op: each side at its own element size
-COSTA_HD inline int64_t op_alg_bytes(const costa_tile_op_t& op, uint64_t src_elem, uint64_t dst_elem) {
+COSTA_HD inline int64_t op_alg_bytes(const costa_tile_op_t& op, esize src_elem, esize dst_elem) {
     const uint32_t k = (op.flags & COSTA_SCALE_MASK) >> COSTA_SCALE_SHIFT;
     const int64_t n = int64_t(op.nf) * op.ns;
-    return int64_t(src_elem) * n * (k != COSTA_SCALE_ZERO) +
-           int64_t(dst_elem) * n * (1 + (k == COSTA_SCALE_AXPBY));
+    return int64_t(src_elem.bytes(uint64_t(n))) * (k != COSTA_SCALE_ZERO) +
+           int64_t(dst_elem.bytes(uint64_t(n))) * (1 + (k == COSTA_SCALE_AXPBY));
 }
 
 // ... of an edge op: kept elements only
-COSTA_HD inline int64_t op_alg_bytes(const costa_tri_op_t& t, uint64_t elem) {
+COSTA_HD inline int64_t op_alg_bytes(const costa_tri_op_t& t, esize elem) {
     const uint32_t k = (t.op.flags & COSTA_SCALE_MASK) >> COSTA_SCALE_SHIFT;
-    return int64_t(elem) * tri_kept(t) * (1 + (k != COSTA_SCALE_ZERO) + (k == COSTA_SCALE_AXPBY));
+    return int64_t(elem.bytes(uint64_t(tri_kept(t)))) * (1 + (k != COSTA_SCALE_ZERO) + (k == COSTA_SCALE_AXPBY));
 }
 
 }  // namespace engine

@@ -58,7 +58,8 @@ typedef enum {
     COSTA_HALF = 5,    /* IEEE binary16, 2 bytes, raw bits ("Half precision" below) */
     COSTA_BFLOAT16 = 6, /* bfloat16, 2 bytes, raw bits */
     COSTA_FP8_E4M3 = 7, /* OCP e4m3fn, 1 byte, raw bits ("FP8" below) */
-    COSTA_FP8_E5M2 = 8  /* OCP e5m2, 1 byte, raw bits */
+    COSTA_FP8_E5M2 = 8, /* OCP e5m2, 1 byte, raw bits */
+    COSTA_FP4_E2M1 = 9  /* OCP e2m1, 4 bits, two codes per byte ("MXFP4" below; MX entry points only) */
 } costa_dtype_t;
 
 typedef struct costa_layout_s* costa_layout_t;
@@ -519,6 +520,59 @@ int costa_hip_mx_items(int64_t* items, int reset);
 int costa_hip_mx_check_ops(const costa_scaled_op_t* ops, int64_t n_ops, int axis, int64_t m, int64_t n);
 /* the stride / aliasing rule of a descriptor for a rows x cols matrix (host only, `data` unused) */
 int costa_hip_mx_check_scales(const costa_mx_scales_t* s, int64_t rows, int64_t cols);
+
+/* ---- MXFP4 (MI355X-native): packed e2m1 layouts in the MX block-scaled transforms ----
+ * Element type.  COSTA_FP4_E2M1 is OCP e2m1.  A code is 4 bits: bit 3 the sign, bits 2..1 the
+ * exponent (bias 1), bit 0 the mantissa; the magnitudes of codes 0..7 are 0, 0.5, 1, 1.5, 2, 3, 4, 6.
+ * No infinity, no NaN.
+ *
+ * Packing.  Two codes share a byte along the layout's stored-contiguous dimension: rows for
+ * column-major 'C' storage, columns for 'R'.  Element indices count from the first element of the
+ * local block's buffer; the element with the even index sits in bits 3..0, the next one in bits 7..4
+ * (the order of torch's float4_e2m1fn_x2 helpers, hi << 4 | lo).
+ *
+ * Layouts.  Every count of the layout calls stays in ELEMENTS (m, n, block sizes, i / j, sub_m /
+ * sub_n, lld / ld, split points); the data pointer addresses bytes and the byte pitch is ld / 2.
+ *
+ * w4(code) is the exact fp32 value of a code (w4(0x8) = -0.0).  cvt4(t) converts a finite fp32 t
+ * with |t| <= 6: round to the nearest representable magnitude, ties to the code whose mantissa bit
+ * is 0 (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4); the sign bit of t is
+ * always kept (-0.0 and -0.2 give 0x8).  cvt4(NaN) = 0x0, which occurs only in a block whose scale
+ * byte is 255.
+ *
+ * Block rule.  The MXFP8 rule above with emax = 2 and fmax = 6.0 (bits 0x40C00000): per block of 32
+ * elements of C along c_scales.axis, amax = the unsigned maximum of the bits of |v|, e = amax >> 23;
+ * e == 255 gives E = 255, else E = max(e - 2, 0); with COSTA_MX_CEIL E is one higher (at most 254)
+ * where amax * pow2(254 - E) > 6.0.  q = cvt4(clamp(v * pow2(254 - E), -6, 6)), SC[block] = E; a block
+ * with E = 255 stores code 0x0 everywhere.  Under the floor rule a block's maximum lands in [4, 8),
+ * so values above 6 saturate: the clamp is load-bearing, as for e4m3.
+ *
+ * Dequantise.  x = w4(a) * pow2(SA[block]) is one rounded fp32 product; the ordinary alpha / beta
+ * branches follow in fp32 with contraction off (beta is free: C is fp32).
+ *
+ * Accepted calls (costa_hip_transform_mx, _async, costa_hip_execute_tiles_mx; the descriptor,
+ * rounding, stride, device-residency and "MX block" checks apply unchanged):
+ *   quantise    COSTA_FLOAT -> COSTA_FP4_E2M1     c_scales, beta = 0
+ *   dequantise  COSTA_FP4_E2M1 -> COSTA_FLOAT     a_scales
+ *   requantise  COSTA_FP4_E2M1 -> COSTA_FP4_E2M1  both, beta = 0
+ * COSTA_FP4_E2M1 with any other type is "no MX transform".  Every other entry point refuses an FP4
+ * layout or dtype with COSTA_ERR_ARG naming FP4_E2M1, except costa_hip_plan_export_scaled, which
+ * plans the three pairs (host only).  In a plan of an FP4 pair every count of an op is in elements
+ * and src / dst are byte addresses; when A holds FP4 the package is packed too: its PACK ops are
+ * 1-byte copy ops (nf / 2 x ns, pitch lds / 2) and the send / receive counts and displacements count
+ * BYTES, so that no round boundary falls inside a byte.
+ *
+ * Evenness rule ("FP4 pair").  No tile may split a byte.  At layout creation of an FP4 layout: ld
+ * is even, and along the packed dimension the matrix extent, the layout's own split points and (for
+ * block-cyclic layouts) the sub-matrix offset and every local block offset are even.  At plan time,
+ * for every op of the pair on each FP4 side: the op's element offset from its block pointer and its
+ * extent along that side's stored-contiguous dimension are even -- through op, the OTHER layout's
+ * split points count too.  costa_hip_execute_tiles_mx applies the per-op half (even extent and even
+ * leading dimension on each FP4 side) to caller-given ops.  A violation is COSTA_ERR_ARG with "FP4
+ * pair" and the offending interval in the message, before anything is written.
+ *
+ * Not covered: MXFP6, NVFP4 (16-element blocks, e4m3 scales), bf16 / fp16 sides, host-resident FP4
+ * layouts, batches, masks, in-place calls, odd extents (a half-filled last byte), swizzled scales. */
 
 /* ---- stream-ordered variants (MI355X-native; no reference counterpart) ----
  * Enqueue the transform and return.  Layouts must be device-resident.  `stream` (a hipStream_t,
