@@ -28,7 +28,7 @@ import numpy as np
 
 __all__ = [
     "CostaError", "lib", "FLOAT", "DOUBLE", "CFLOAT", "CDOUBLE", "INT32", "HALF", "BFLOAT16",
-    "FP8_E4M3", "FP8_E5M2", "FP4_E2M1", "dtype_code", "element_code",
+    "FP8_E4M3", "FP8_E5M2", "FP4_E2M1", "FP6_E2M3", "FP6_E3M2", "dtype_code", "element_code",
     "np_dtype", "Layout", "block_cyclic_layout", "custom_layout", "Comm", "transform",
     "transform_batch", "transform_async", "transform_batch_async", "synchronize", "transformer", "copy_and_transform", "execute_tiles", "execute_tiles_mixed",
     "convert_subtile", "TileOp", "TriOp", "TRI_OP_DTYPE", "transform_tri", "transform_tri_async",
@@ -64,7 +64,14 @@ _TORCH_FP8 = {"torch.float8_e4m3fn": FP8_E4M3, "torch.float8_e5m2": FP8_E5M2}
 FP4_E2M1 = 9
 _NP_FP8[FP4_E2M1] = np.uint8
 _TORCH_FP8["torch.float4_e2m1fn_x2"] = FP4_E2M1
-_FP32_SCALARS = (HALF, BFLOAT16, FP8_E4M3, FP8_E5M2, FP4_E2M1)
+# The packed 6-bit types (costa_hip.h, "MXFP6"): OCP e2m3 / e3m2, four codes per three bytes (np.uint8
+# is the storage: 3 bytes hold 4 elements, the first in the lowest bits), every layout count in
+# elements.  torch has no FP6 dtype: pass the code over uint8 storage.  Only transform_mx,
+# execute_tiles_mx and plan_export_scaled take them; alpha / beta are fp32.
+FP6_E2M3, FP6_E3M2 = 10, 11
+_NP_FP8[FP6_E2M3] = np.uint8
+_NP_FP8[FP6_E3M2] = np.uint8
+_FP32_SCALARS = (HALF, BFLOAT16, FP8_E4M3, FP8_E5M2, FP4_E2M1, FP6_E2M3, FP6_E3M2)
 
 TILE_TRANSPOSE, TILE_CONJ, TILE_VEC_SRC, TILE_VEC_DST = 0x1, 0x2, 0x4, 0x8
 SCALE_BITCOPY, SCALE_ZERO, SCALE_ALPHA, SCALE_AXPBY = 0, 1, 2, 3
@@ -114,7 +121,8 @@ def element_code(dtype) -> int:
     """dtype_code() plus the FP8 types and packed FP4: ``torch.float8_e4m3fn`` is FP8_E4M3,
     ``torch.float8_e5m2`` is FP8_E5M2 and ``torch.float4_e2m1fn_x2`` is FP4_E2M1 (by module and name,
     without importing torch).  numpy has no FP8 or FP4 type, and a plain ``np.uint8`` array is neither
-    an FP8 nor an FP4 matrix: pass the code."""
+    an FP8 nor an FP4 matrix: pass the code.  Neither numpy nor torch has an FP6 type: FP6_E2M3 and
+    FP6_E3M2 are always passed as codes (they pass through), over ``uint8`` storage."""
     if not isinstance(dtype, int) and type(dtype).__module__.split(".")[0] == "torch" \
             and str(dtype) in _TORCH_FP8:
         return _TORCH_FP8[str(dtype)]
@@ -123,7 +131,8 @@ def element_code(dtype) -> int:
 
 def np_dtype(code: int):
     """numpy type holding one element of ``code``; BFLOAT16 is ``np.uint16`` and the FP8 types are
-    ``np.uint8`` (their bits).  FP4_E2M1 is ``np.uint8`` too, but a byte holds TWO elements."""
+    ``np.uint8`` (their bits).  FP4_E2M1 is ``np.uint8`` too, but a byte holds TWO elements; FP6_E2M3
+    and FP6_E3M2 are ``np.uint8`` as well: 3 bytes hold 4 elements."""
     return _NP_FP8[code] if code in _NP_FP8 else _NP[code]
 
 
@@ -1051,6 +1060,9 @@ def transform_mx(A: Layout, Cl: Layout, comm: Comm, trans: str = "N", alpha=1.0,
     saturates).  beta must be 0 with ``c_scales``.  The same three calls take packed FP4_E2M1 in
     place of FP8 (MXFP4; costa_hip.h, "MXFP4"): quantise FLOAT -> FP4_E2M1, dequantise FP4_E2M1 ->
     FLOAT, requantise FP4_E2M1 -> FP4_E2M1; no tile may split a byte (CostaError with "FP4 pair").
+    And packed FP6_E2M3 / FP6_E3M2 (MXFP6; costa_hip.h, "MXFP6"): quantise FLOAT -> P, dequantise
+    P -> FLOAT, requantise P -> the same P; four codes share three bytes and no tile may split such a
+    group (CostaError with "FP6 quad").
     With ``stream`` the call is stream-ordered and the
     tensors must stay valid until the stream has passed it.  With several ranks each rank writes the
     ``c_scales`` bytes of its own blocks only (merge zero-initialised tensors with a MAX all-reduce)
@@ -1075,7 +1087,9 @@ def execute_tiles_mx(src_dtype, dst_dtype, ops: np.ndarray, scalars: np.ndarray,
     matrix, fp32 ``scalars``; with ``a_transposed`` A's matrix is n x m and ``a_scales`` is indexed by
     it (costa_hip_execute_tiles_mx).  With FP4_E2M1 (quantise, dequantise, requantise as for
     transform_mx) every count of an op is in elements, ``src`` / ``dst`` are byte offsets, and on each
-    FP4 side the leading dimension and the extent along the stored-contiguous dimension are even."""
+    FP4 side the leading dimension and the extent along the stored-contiguous dimension are even.
+    With FP6_E2M3 / FP6_E3M2 the same holds with multiples of 4 on each FP6 side ("FP6 quad"); a byte
+    offset may have any parity."""
     sc_, dc_ = element_code(src_dtype), element_code(dst_dtype)
     ops = np.ascontiguousarray(ops, dtype=SCALED_OP_DTYPE)
     sc = np.ascontiguousarray(scalars, dtype=np.float32).reshape(-1)
@@ -1120,7 +1134,8 @@ def plan_export_scaled(A: Layout, Cl: Layout, rank: int, nranks: int, trans: str
     ordinary plan with every local and unpack op in ``local_scaled`` / ``unpack_scaled``; the
     ordinary ``local_ops`` / ``unpack_ops`` are empty.  The three FP4_E2M1 pairs of transform_mx
     (quantise, dequantise, requantise) are planned too: op counts are elements, addresses bytes; when
-    A holds FP4 the pack ops are byte copies and the send / receive counts are bytes."""
+    A holds FP4 the pack ops are byte copies and the send / receive counts are bytes.  The six pairs
+    of FP6_E2M3 / FP6_E3M2 are planned the same way: a packed side's bytes are 3/4 of its elements."""
     if not isinstance(A, Layout) or not isinstance(Cl, Layout):
         raise CostaError(1, "costa: batches of scaled layout pairs are not supported")
     code = _scalar_code(A.dtype, Cl.dtype)

@@ -79,48 +79,57 @@ void with_type(costa_dtype_t t, F&& f) {
     case COSTA_BFLOAT16: f(costa::bfloat16_bits{}); return;
     case COSTA_FP8_E4M3: f(costa::fp8_e4m3_bits{}); return;
     case COSTA_FP8_E5M2: f(costa::fp8_e5m2_bits{}); return;
-    // (packed: no element type of its own; fp4_layout() below builds it from a byte layout)
+    // (packed: no element type of their own; packed_layout() below builds them from a byte layout)
     case COSTA_FP4_E2M1: f(costa::fp8_e4m3_bits{}); return;
+    case COSTA_FP6_E2M3: f(costa::fp8_e4m3_bits{}); return;
+    case COSTA_FP6_E3M2: f(costa::fp8_e4m3_bits{}); return;
     }
     throw costa::engine::error(COSTA_ERR_ARG, "unknown dtype");
 }
 
-// An FP4_E2M1 layout from the 1-byte layout the builders made of the same arguments (every count in
-// elements): the layout-only part of the evenness rule (costa_hip.h, "MXFP4"), then every block
-// pointer at half its element offset from `base` (block-cyclic; a custom layout's pointers are the
-// caller's byte pointers, base == nullptr).  `sub_off`: the sub-matrix offset along the packed
-// dimension (block-cyclic), else 0.
-void fp4_layout(elayout& e, const char* base, int sub_off) {
-    auto bad = [](const std::string& what) {
-        throw costa::engine::error(COSTA_ERR_ARG, "costa: FP4 pair: an FP4_E2M1 layout must not split a byte: " + what);
+// A packed layout (FP4_E2M1, FP6_E2M3, FP6_E3M2) from the 1-byte layout the builders made of the same
+// arguments (every count in elements): the layout-only part of the type's rule -- no tile may split a
+// packing group of g elements: the evenness rule, g = 2 (costa_hip.h, "MXFP4"), the quad rule, g = 4
+// ("MXFP6") -- then every block pointer at the byte offset of its element offset from `base`
+// (block-cyclic; a custom layout's pointers are the caller's byte pointers, base == nullptr).
+// `sub_off`: the sub-matrix offset along the packed dimension (block-cyclic), else 0.
+void packed_layout(elayout& e, costa_dtype_t dtype, const char* base, int sub_off) {
+    const int g = costa::engine::packed_group(dtype);
+    const bool fp4 = g == 2;
+    auto bad = [&](const std::string& what) {
+        throw costa::engine::error(COSTA_ERR_ARG, std::string("costa: ") + costa::engine::packed_rule(dtype) + ": an " +
+                                                      costa::engine::dtype_name(dtype) + " layout must not split a " +
+                                                      (fp4 ? "byte" : "3-byte group") + ": " + what);
     };
     const bool packed_rows = e.ordering != 'R';  // 'C': rows share bytes
     const char* dim = packed_rows ? "row" : "column";
     const std::vector<int>& split = packed_rows ? e.rows_split : e.cols_split;
-    if (!split.empty() && (split.back() - split.front()) % 2 != 0)
+    if (!split.empty() && (split.back() - split.front()) % g != 0)
         bad(std::string("the matrix has ") + std::to_string(split.back() - split.front()) + " " + dim +
             "s along the packed dimension, [" + std::to_string(split.front()) + ", " + std::to_string(split.back()) +
             ")");
-    if (sub_off % 2 != 0)
+    if (sub_off % g != 0)
         bad(std::string("the sub-matrix starts at ") + dim + " " + std::to_string(sub_off) + " (0-based), [" +
             std::to_string(sub_off) + ", ...)");
     for (size_t k = 0; k + 1 < split.size(); ++k)
-        if (split[k] % 2 != 0 || split[k + 1] % 2 != 0)
+        if (split[k] % g != 0 || split[k + 1] % g != 0)
             bad(std::string("the ") + dim + " interval [" + std::to_string(split[k]) + ", " +
-                std::to_string(split[k + 1]) + ") of its own grid has an odd end");
+                std::to_string(split[k + 1]) + ") of its own grid has an " +
+                (fp4 ? "odd end" : "end that is no multiple of 4"));
     for (auto& b : e.blocks) {
         const costa::interval& iv = packed_rows ? b.rows : b.cols;
-        if (b.ld % 2 != 0)
+        if (b.ld % g != 0)
             bad(std::string("ld ") + std::to_string(b.ld) + " of the block at " + dim + "s [" +
-                std::to_string(iv.start) + ", " + std::to_string(iv.end) + ") is odd");
+                std::to_string(iv.start) + ", " + std::to_string(iv.end) + ") is " +
+                (fp4 ? "odd" : "no multiple of 4"));
         if (!base) continue;
         const std::ptrdiff_t off = b.data - base;  // elements
-        if (off % 2 != 0)
+        if (off % g != 0)
             bad(std::string("the block at ") + dim + "s [" + std::to_string(iv.start) + ", " +
                 std::to_string(iv.end) + ") starts " + std::to_string(off) + " elements into the local buffer");
-        b.data = const_cast<char*>(base) + off / 2;
+        b.data = const_cast<char*>(base) + costa::engine::elem_size(dtype).bytes(uint64_t(off));
     }
-    e.dtype = COSTA_FP4_E2M1;
+    e.dtype = dtype;
 }
 
 scal make_scal(costa_dtype_t t, const void* a, const void* b) {
@@ -243,8 +252,8 @@ int costa_hip_block_cyclic_layout(costa_dtype_t dtype, int m, int n, int block_m
                                                    p_n, rank_grid_ordering, rsrc, csrc,
                                                    static_cast<T*>(ptr), lld, data_ordering, rank);
             h->e = costa::engine::erase(L);
-            if (dtype == COSTA_FP4_E2M1)
-                fp4_layout(h->e, static_cast<const char*>(ptr), h->e.ordering != 'R' ? i - 1 : j - 1);
+            if (costa::engine::dtype_is_packed(dtype))
+                packed_layout(h->e, dtype, static_cast<const char*>(ptr), h->e.ordering != 'R' ? i - 1 : j - 1);
             costa::engine::set_layout_hash(h->e);  // handles are immutable
         });
         *out = h.release();
@@ -266,7 +275,7 @@ int costa_hip_custom_layout(costa_dtype_t dtype, int rowblocks, int colblocks, c
                                              reinterpret_cast<const costa::block_t*>(localblocks),
                                              ordering);
             h->e = costa::engine::erase(L);
-            if (dtype == COSTA_FP4_E2M1) fp4_layout(h->e, nullptr, 0);
+            if (costa::engine::dtype_is_packed(dtype)) packed_layout(h->e, dtype, nullptr, 0);
             costa::engine::set_layout_hash(h->e);  // handles are immutable
         });
         *out = h.release();
@@ -741,8 +750,8 @@ int costa_hip_plan_export_scaled(costa_layout_t A, costa_layout_t C, char trans,
             throw costa::engine::error(COSTA_ERR_ARG, "bad rank/size");
         check_handles(1, &A, &C);
         auto jobs = make_scaled_job(A, C, trans, alpha, beta, nullptr, nullptr);
-        // (an FP4 pair has a scaled plan as an MX job only: costa_hip.h, "MXFP4")
-        if (costa::engine::dtype_is_fp4(A->e.dtype) || costa::engine::dtype_is_fp4(C->e.dtype)) jobs[0].mx = true;
+        // (a packed pair has a scaled plan as an MX job only: costa_hip.h, "MXFP4", "MXFP6")
+        if (costa::engine::dtype_is_packed(A->e.dtype) || costa::engine::dtype_is_packed(C->e.dtype)) jobs[0].mx = true;
         auto p = costa::engine::make_plan(jobs, rank, nranks);
         info->base.n_local = int64_t(p->local_ops.size());
         info->base.n_pack = int64_t(p->pack_ops.size());

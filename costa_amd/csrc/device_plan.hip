@@ -322,7 +322,7 @@ std::unique_ptr<plan> make_plan_device(const std::vector<job>& jobs, int rank, i
     if (any_mixed(jobs) && !any_half(jobs) && !any_fp8(jobs)) return nullptr;
     // ... and so are triangular (masked) transforms: the mask's cut lives in plan.cpp decompose
     if (any_masked(jobs) || any_scaled(jobs)) return nullptr;  // (the host planner builds those)
-    if (any_fp4(jobs)) return nullptr;  // (packed e2m1: the evenness rule and half-byte addresses live in plan.cpp)
+    if (any_packed(jobs)) return nullptr;  // (packed e2m1 / FP6: their rules and sub-byte addresses live in plan.cpp)
     auto p = std::make_unique<plan>();
     const std::vector<job_params> prm = check_jobs(jobs, n_ranks, p->src_dtype, p->dtype);
     const uint64_t EA = dtype_size(p->src_dtype), EC = dtype_size(p->dtype);

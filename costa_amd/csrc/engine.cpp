@@ -2012,8 +2012,9 @@ std::unique_ptr<plan> plan_jobs(const std::vector<job>& jobs, comm* c, hipStream
     size_t blocks = 0;
     for (const job& j : jobs) blocks += j.A->blocks.size() + j.C->blocks.size();
     const size_t need = g_device_planner_warm ? kDevicePlanBlocks : kColdDevicePlanBlocks;
-    // (FP4 pairs are planned on the host, whatever the mode: make_plan holds their evenness rule)
-    if (!any_fp4(jobs) && (mode == 2 || (mode == 1 && blocks >= need))) {
+    // (FP4 and FP6 pairs are planned on the host, whatever the mode: make_plan holds their evenness /
+    // quad rule)
+    if (!any_packed(jobs) && (mode == 2 || (mode == 1 && blocks >= need))) {
         if (auto p = make_plan_device(jobs, c->rank, c->size, lb, c->device, s)) {
             g_stats.device_plans++;
             g_device_planner_warm = true;
@@ -2023,10 +2024,10 @@ std::unique_ptr<plan> plan_jobs(const std::vector<job>& jobs, comm* c, hipStream
     return make_plan(jobs, c->rank, c->size, lb);
 }
 
-// the element types a converting plan's PACK list runs on: a packed FP4 package is copied as bytes by
-// the FP8 family's Q -> Q kernel (scale kind BITCOPY: the bits of every byte)
-costa_dtype_t pack_src(const plan& p) { return dtype_is_fp4(p.src_dtype) ? COSTA_FP8_E4M3 : p.src_dtype; }
-costa_dtype_t pack_dst(const plan& p) { return dtype_is_fp4(p.pkg_dtype) ? COSTA_FP8_E4M3 : p.pkg_dtype; }
+// the element types a converting plan's PACK list runs on: a packed FP4 / FP6 package is copied as
+// bytes by the FP8 family's Q -> Q kernel (scale kind BITCOPY: the bits of every byte)
+costa_dtype_t pack_src(const plan& p) { return dtype_is_packed(p.src_dtype) ? COSTA_FP8_E4M3 : p.src_dtype; }
+costa_dtype_t pack_dst(const plan& p) { return dtype_is_packed(p.pkg_dtype) ? COSTA_FP8_E4M3 : p.pkg_dtype; }
 
 cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
     std::vector<uint64_t> key;
@@ -2069,8 +2070,9 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
 
     const bool half = any_half(jobs);  // 2-byte element types: treated like mixed pairs here
     const bool fp8 = any_fp8(jobs);    // 1-byte element types: the same
-    const bool fp4 = any_fp4(jobs);    // the packed 4-bit type: the same
-    const bool mixed = any_mixed(jobs) || half || fp8 || fp4;
+    const bool packed = any_packed(jobs);  // the packed 4-bit and 6-bit types: the same
+    const bool fp6 = packed && (dtype_is_fp6(jobs[0].A->dtype) || dtype_is_fp6(jobs[0].C->dtype));
+    const bool mixed = any_mixed(jobs) || half || fp8 || packed;
     const bool masked = any_masked(jobs);
     const bool scaled = any_scaled(jobs);
     if (mixed || masked || scaled) {  // an unsupported pair is reported as such, whatever the residency
@@ -2095,7 +2097,9 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
     std::vector<uint8_t> range_flags;
     if (!all_dev && mixed)
         throw error(COSTA_ERR_ARG,
-                    fp4  ? "costa: FP4 transforms (A or C of the packed 4-bit element type) need "
+                    fp6  ? "costa: FP6 transforms (A or C of a packed 6-bit element type) need "
+                           "device-resident layouts"
+                    : packed ? "costa: FP4 transforms (A or C of the packed 4-bit element type) need "
                            "device-resident layouts"
                     : fp8 ? "costa: FP8 transforms (A or C of a 1-byte element type) need "
                            "device-resident layouts"
@@ -2247,15 +2251,16 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
     // list of a half-precision plan runs on the converting family, its same-type H -> H lists too)
     // (an FP8 plan's package holds A's type: PACK is a byte copy on the FP8 family when A holds Q and
     // an ordinary FLOAT list when A is FLOAT; UNPACK always runs on the FP8 family, Q -> Q included)
-    // (an FP4 plan is a scaled plan, its ordinary LOCAL and UNPACK lists are empty; PACK is a byte copy
-    // on the FP8 family when A holds FP4 -- pack_src / pack_dst -- and a FLOAT list when A is FLOAT)
-    const bool cv_pack = p.half() || (p.fp4()   ? dtype_is_fp4(p.src_dtype)
+    // (an FP4 / FP6 plan is a scaled plan, its ordinary LOCAL and UNPACK lists are empty; PACK is a byte
+    // copy on the FP8 family when A holds the packed type -- pack_src / pack_dst -- and a FLOAT list
+    // when A is FLOAT)
+    const bool cv_pack = p.half() || (p.packed() ? dtype_is_packed(p.src_dtype)
                                       : p.fp8() ? dtype_is_fp8(p.src_dtype)
                                                 : p.mixed() && p.pkg_dtype != p.src_dtype);
-    const bool cv_unpack = !p.fp4() && (p.half() || p.fp8() || (p.mixed() && p.pkg_dtype != p.dtype));
-    if (p.fp4()) {
+    const bool cv_unpack = !p.packed() && (p.half() || p.fp8() || (p.mixed() && p.pkg_dtype != p.dtype));
+    if (p.packed()) {
         if (!p.local_ops.empty() || !p.unpack_ops.empty())
-            throw error(COSTA_ERR_INTERNAL, "costa: an FP4 plan with ordinary LOCAL / UNPACK ops");
+            throw error(COSTA_ERR_INTERNAL, "costa: an FP4 / FP6 plan with ordinary LOCAL / UNPACK ops");
     } else if (p.converting())
         cp->c_local = build_convert_work(p.src_dtype, p.dtype, p.local_ops, 0, 0, ord_l, w_l);
     else
@@ -2319,7 +2324,7 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
         if (cv_unpack)
             x->c_unpack = build_convert_work(p.pkg_dtype, p.dtype, up[size_t(r)], 0, 0, ord_u[size_t(r)],
                                              w_u[size_t(r)]);
-        else if (!p.fp4())  // (an FP4 plan has no ordinary UNPACK list)
+        else if (!p.packed())  // (an FP4 / FP6 plan has no ordinary UNPACK list)
             x->l_unpack = build_work(p.dtype, up[size_t(r)], ord_u[size_t(r)], w_u[size_t(r)], list_unpack,
                                      &sec_u[size_t(r)]);
         if (!upt[size_t(r)].empty())
@@ -2543,12 +2548,14 @@ void check_mx_job(const job& j) {
     if (!mx_pair(a, c))
         throw error(COSTA_ERR_ARG, std::string("costa_hip_transform_mx: no MX transform for ") + dtype_name(a) +
                                        " -> " + dtype_name(c) +
-                                       (dtype_is_fp4(a) || dtype_is_fp4(c)
+                                       (dtype_is_fp6(a) || dtype_is_fp6(c)
+                                            ? " (FLOAT -> FP6, FP6 -> FLOAT, FP6 -> the same FP6)"
+                                        : dtype_is_fp4(a) || dtype_is_fp4(c)
                                             ? " (FLOAT -> FP4_E2M1, FP4_E2M1 -> FLOAT, FP4_E2M1 -> FP4_E2M1)"
                                             : " (FLOAT -> FP8, FP8 -> FLOAT, FP8 -> the same FP8)"));
     if (j.uplo != 'A') throw error(COSTA_ERR_ARG, "costa_hip_transform_mx: no triangular mask");
     if (j.A == j.C) throw error(COSTA_ERR_ARG, "costa_hip_transform_mx: in-place calls are not supported");
-    const bool want_a = dtype_is_fp8(a) || dtype_is_fp4(a), want_c = dtype_is_fp8(c) || dtype_is_fp4(c);
+    const bool want_a = dtype_is_fp8(a) || dtype_is_packed(a), want_c = dtype_is_fp8(c) || dtype_is_packed(c);
     if (want_a && !j.a_scales.data)
         throw error(COSTA_ERR_ARG, std::string("costa_hip_transform_mx: a_scales is required for ") + dtype_name(a) +
                                        " -> " + dtype_name(c));
@@ -2827,7 +2834,7 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
                 throw error(COSTA_ERR_ARG, "costa: an emulated communicator needs device-resident layouts");
     }
     const bool mx = jobs.size() == 1 && jobs[0].mx;
-    if (!mx && any_fp4(jobs)) {  // (before any residency or staging question)
+    if (!mx && any_packed(jobs)) {  // (before any residency or staging question)
         costa_dtype_t a, b;
         check_jobs(jobs, c->size, a, b);
     }
@@ -2980,7 +2987,7 @@ void execute_tiles(costa_dtype_t dtype, const costa_tile_op_t* ops, int64_t n,
                    const void* src_base, void* dst_base, const void* scalars, int n_slots,
                    int device) {
     std::lock_guard<std::recursive_mutex> lk(g_mutex);
-    if (dtype_is_half(dtype) || dtype_is_fp8(dtype) || dtype_is_fp4(dtype))
+    if (dtype_is_half(dtype) || dtype_is_fp8(dtype) || dtype_is_packed(dtype))
         throw error(COSTA_ERR_ARG, std::string("costa_hip_execute_tiles: no same-type tile kernel for ") +
                                        dtype_name(dtype) + " (use costa_hip_execute_tiles_mixed)");
     device_ctx& dc = ctx(device);
@@ -3092,7 +3099,7 @@ void execute_tiles_mixed(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const
 void execute_tiles_tri(costa_dtype_t dtype, const costa_tri_op_t* ops, int64_t n, const void* src_base,
                        void* dst_base, const void* scalars, int n_slots, int device) {
     std::lock_guard<std::recursive_mutex> lk(g_mutex);
-    if (dtype_is_half(dtype) || dtype_is_fp8(dtype) || dtype_is_fp4(dtype))
+    if (dtype_is_half(dtype) || dtype_is_fp8(dtype) || dtype_is_packed(dtype))
         throw error(COSTA_ERR_ARG, std::string("costa_hip_execute_tiles_tri: no edge-tile kernel for ") +
                                        dtype_name(dtype));
     const uintptr_t sb = reinterpret_cast<uintptr_t>(src_base), db = reinterpret_cast<uintptr_t>(dst_base);
@@ -3275,15 +3282,24 @@ void check_mx_ops(const std::vector<costa_scaled_op_t>& ops, int axis, int64_t m
     }
 }
 
-void check_fp4_ops(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const std::vector<costa_scaled_op_t>& ops) {
+void check_packed_ops(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const std::vector<costa_scaled_op_t>& ops) {
+    const int gs = std::max(1, packed_group(src_dtype)), gd = std::max(1, packed_group(dst_dtype));
     for (const costa_scaled_op_t& t : ops) {
         const costa_tile_op_t& op = t.op;
         if (op.nf <= 0 || op.ns <= 0) continue;
         // the source's stored-contiguous dimension is f; the destination's f (copy) or s (transpose)
         const bool tr = op.flags & COSTA_TILE_TRANSPOSE;
         const int64_t dn = tr ? op.ns : op.nf;
-        const bool bad_src = dtype_is_fp4(src_dtype) && (op.nf % 2 != 0 || op.lds % 2 != 0);
-        const bool bad_dst = dtype_is_fp4(dst_dtype) && (dn % 2 != 0 || op.ldd % 2 != 0);
+        const bool bad_src = op.nf % gs != 0 || op.lds % gs != 0;
+        const bool bad_dst = dn % gd != 0 || op.ldd % gd != 0;
+        if ((bad_src && dtype_is_fp6(src_dtype)) || (!bad_src && bad_dst && dtype_is_fp6(dst_dtype)))
+            throw error(COSTA_ERR_ARG,
+                        std::string("costa: FP6 quad: an op splits a 3-byte group of its ") +
+                            dtype_name(bad_src ? src_dtype : dst_dtype) + (bad_src ? " source" : " destination") +
+                            ": [0, " + std::to_string(bad_src ? int64_t(op.nf) : dn) +
+                            ") elements along the stored-contiguous dimension with ld " +
+                            std::to_string(bad_src ? op.lds : op.ldd) + " (both must be multiples of 4; target rows " +
+                            std::to_string(t.row0) + " .., columns " + std::to_string(t.col0) + " ..)");
         if (bad_src || bad_dst)
             throw error(COSTA_ERR_ARG,
                         std::string("costa: FP4 pair: an op splits a byte of its FP4_E2M1 ") +
@@ -3307,8 +3323,9 @@ void execute_tiles_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const co
     const costa_mx_scales_t& sa = a_scales && a_scales->data ? *a_scales : none;
     const costa_mx_scales_t& sc = c_scales && c_scales->data ? *c_scales : none;
     const bool p4 = dtype_is_fp4(src_dtype) || dtype_is_fp4(dst_dtype);
+    const bool p6 = dtype_is_fp6(src_dtype) || dtype_is_fp6(dst_dtype);
     if ((sa.data != nullptr) != (src_dtype != COSTA_FLOAT) || (sc.data != nullptr) != (dst_dtype != COSTA_FLOAT))
-        throw error(COSTA_ERR_ARG, who + ": a scale tensor is needed exactly on the " + (p4 ? "FP4" : "FP8") +
+        throw error(COSTA_ERR_ARG, who + ": a scale tensor is needed exactly on the " + (p6 ? "FP6" : p4 ? "FP4" : "FP8") +
                                        " sides of " + dtype_name(src_dtype) + " -> " + dtype_name(dst_dtype));
     if (rounding != COSTA_MX_FLOOR && rounding != COSTA_MX_CEIL)
         throw error(COSTA_ERR_ARG, who + ": rounding must be COSTA_MX_FLOOR or COSTA_MX_CEIL");
@@ -3329,7 +3346,7 @@ void execute_tiles_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const co
                 throw error(COSTA_ERR_ARG, who + ": beta must be 0 with c_scales (an op of kind AXPBY)");
         check_mx_ops(v, sc.axis, m, n);
     }
-    if (p4) check_fp4_ops(src_dtype, dst_dtype, v);
+    if (p4 || p6) check_packed_ops(src_dtype, dst_dtype, v);
     ctx(device);  // (is_device_ptr needs the device's context)
     for (const void* p : {static_cast<const void*>(sa.data), static_cast<const void*>(sc.data)})
         if (p && !is_device_ptr(p)) throw error(COSTA_ERR_ARG, who + ": the scale tensors must be device-resident");
@@ -3356,7 +3373,7 @@ void copy_and_transform(costa_dtype_t dtype, int n_rows, int n_cols, const void*
                         bool trans, bool conj, const void* alpha, const void* beta) {
     if (n_rows < 0 || n_cols < 0 || src_stride < 0 || dst_stride < 0)
         throw error(COSTA_ERR_ARG, "costa_hip_copy_and_transform: negative size or stride");
-    if (dtype_is_half(dtype) || dtype_is_fp8(dtype) || dtype_is_fp4(dtype))
+    if (dtype_is_half(dtype) || dtype_is_fp8(dtype) || dtype_is_packed(dtype))
         throw error(COSTA_ERR_ARG, std::string("costa_hip_copy_and_transform: no same-type tile kernel for ") +
                                        dtype_name(dtype));
     if (size_t(n_rows) * size_t(n_cols) == 0) return;  // memory_utils.hpp:72-74

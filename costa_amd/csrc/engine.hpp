@@ -16,9 +16,10 @@
 namespace costa {
 namespace engine {
 
-// bytes of one element; COSTA_FP4_E2M1 (half a byte) throws COSTA_ERR_ARG naming the type
+// bytes of one element; COSTA_FP4_E2M1 (half a byte) and the FP6 types (three quarters) throw
+// COSTA_ERR_ARG naming the type
 size_t dtype_size(costa_dtype_t t);
-// ... of any type, in half-bytes (tile_op.hpp esize): wherever an address or a byte count of a
+// ... of any type, in quarter-bytes (tile_op.hpp esize): wherever an address or a byte count of a
 // layout side is formed
 esize elem_size(costa_dtype_t t);
 bool dtype_is_complex(costa_dtype_t t);
@@ -32,12 +33,20 @@ bool half_pair(costa_dtype_t src, costa_dtype_t dst);
 // pairs Q -> Q of one Q, FLOAT -> Q, Q -> FLOAT: the pairs of fp8_kernels.hip
 bool dtype_is_fp8(costa_dtype_t t);
 bool fp8_pair(costa_dtype_t src, costa_dtype_t dst);
-// the packed 4-bit type (COSTA_FP4_E2M1; compute_dtype is FLOAT) and its pairs P -> P, FLOAT -> P,
-// P -> FLOAT: MX transforms only (costa_hip.h, "MXFP4"), planned on the host
+// the packed sub-byte types (compute_dtype is FLOAT): COSTA_FP4_E2M1, two elements per byte, and
+// COSTA_FP6_E2M3 / COSTA_FP6_E3M2, four elements per three bytes; packed_group() is the elements of
+// one packing group (2, 4; 0 for every other type) and packed_rule() the name of the rule that keeps
+// a tile from splitting one ("FP4 pair", "FP6 quad").  Their pairs P -> P, FLOAT -> P, P -> FLOAT:
+// MX transforms only (costa_hip.h, "MXFP4", "MXFP6"), planned on the host
 bool dtype_is_fp4(costa_dtype_t t);
-bool fp4_pair(costa_dtype_t src, costa_dtype_t dst);
-// a package is counted in units of this many bytes: its elements, or single bytes when it holds
-// packed FP4 (A holds FP4), so that no count, displacement or round boundary falls inside a byte
+bool dtype_is_fp6(costa_dtype_t t);
+bool dtype_is_packed(costa_dtype_t t);
+int packed_group(costa_dtype_t t);
+const char* packed_rule(costa_dtype_t t);
+bool packed_pair(costa_dtype_t src, costa_dtype_t dst);
+// a package is counted in units of this many bytes: its elements, or single bytes when it holds a
+// packed type (A holds FP4 or FP6), so that no count, displacement or round boundary falls inside a
+// byte
 size_t pkg_unit_size(costa_dtype_t pkg);
 int64_t pkg_units(costa_dtype_t pkg, int64_t elems);
 // element type of the packages of an (A, C) plan: the narrower of the two; A's for FP8 pairs
@@ -136,10 +145,10 @@ struct plan {
     // LOCAL and UNPACK run on the converting family of fp8_kernels.hip; PACK is a byte copy of
     // 1-byte tiles on it when A holds Q, and a same-type FLOAT list on tile_kernel when A is FLOAT.
     bool fp8() const { return dtype_is_fp8(src_dtype) || dtype_is_fp8(dtype); }
-    // FP4 plans (A or C of COSTA_FP4_E2M1, scaled plans of MX calls only): the package holds A's type;
-    // a packed package's PACK list is a byte copy on the FP8 family's Q -> Q kernel
-    bool fp4() const { return dtype_is_fp4(src_dtype) || dtype_is_fp4(dtype); }
-    bool converting() const { return mixed() || half() || fp8() || fp4(); }
+    // packed plans (A or C of COSTA_FP4_E2M1 or an FP6 type, scaled plans of MX calls only): the package
+    // holds A's type; a packed package's PACK list is a byte copy on the FP8 family's Q -> Q kernel
+    bool packed() const { return dtype_is_packed(src_dtype) || dtype_is_packed(dtype); }
+    bool converting() const { return mixed() || half() || fp8() || packed(); }
     costa_dtype_t scalar_dtype() const { return compute_dtype(src_dtype, dtype); }
     int rank = 0, n_ranks = 1;
     std::vector<costa_tile_op_t> local_ops, pack_ops, unpack_ops;
@@ -185,8 +194,8 @@ bool any_mixed(const std::vector<job>& jobs);
 bool any_half(const std::vector<job>& jobs);
 // whether some job of the batch has a 1-byte element type on either side
 bool any_fp8(const std::vector<job>& jobs);
-// whether some job of the batch has the packed 4-bit element type on either side
-bool any_fp4(const std::vector<job>& jobs);
+// whether some job of the batch has a packed sub-byte element type on either side
+bool any_packed(const std::vector<job>& jobs);
 
 // Build the plan of `rank` (of `n_ranks`) for a batch of jobs (host only).  `loopback` (test
 // mode, see loopback_exchange()): 1 = the rank's own tiles all go through pack -> exchange with
@@ -385,12 +394,13 @@ struct mx_side {
     int64_t block_stride = 0, line_stride = 0;
     bool rows = true;
 };
-// FLOAT -> Q (quantise), Q -> FLOAT (dequantise), Q -> Q of one Q (requantise); Q an FP8 type or
-// COSTA_FP4_E2M1
+// FLOAT -> Q (quantise), Q -> FLOAT (dequantise), Q -> Q of one Q (requantise); Q an FP8 type,
+// COSTA_FP4_E2M1 or an FP6 type
 bool mx_pair(costa_dtype_t src, costa_dtype_t dst);
-// the per-op half of the evenness rule ("FP4 pair") on caller-given ops: on each FP4 side the
-// leading dimension and the extent along the side's stored-contiguous dimension are even
-void check_fp4_ops(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const std::vector<costa_scaled_op_t>& ops);
+// the per-op half of the evenness rule ("FP4 pair") and of the quad rule ("FP6 quad") on caller-given
+// ops: on each packed side the leading dimension and the extent along the side's stored-contiguous
+// dimension are multiples of the packing group
+void check_packed_ops(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const std::vector<costa_scaled_op_t>& ops);
 // a scale tensor on exactly the FP8 sides of the pair; `ceil`: COSTA_MX_CEIL
 void launch_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* d_ops,
                const uint64_t* d_work, const strip_list& l, const char* src_base, char* dst_base,

@@ -75,6 +75,31 @@
 // not used.  LDS: the codec adds and changes no LDS access -- the staged
 // tile holds fp32 v and `red` fp32 bit patterns exactly as for FP8, so the bank behaviour above
 // stands unchanged.
+//
+// Packed FP6 (COSTA_FP6_E2M3 / COSTA_FP6_E3M2; costa_hip.h, "MXFP6"): the codecs q6_e<e2m3_t> /
+// q6_e<e3m2_t> and six more instantiations (f32_e -> q6_e QUANT, q6_e -> f32_e, q6_e -> q6_e QUANT per
+// type) of the same kernel; everything named above as shared stays shared line for line.  A strip of 4
+// elements is exactly one packing group: 3 bytes along the side's stored-contiguous dimension, its 4
+// codes unpacked one per byte of strip<uint8_t> between load_strip6 and store_strip6.  Every element
+// offset the kernel forms on an FP6 side is a multiple of 4 (the quad rule: ld and extents are
+// multiples of 4; f0, s0, lf and sb are multiples of 4), so elems() = (at >> 2) * 3 is exact, a strip
+// starts on a group boundary, and a group never straddles two lanes: strips are 4 elements, groups
+// are 4 elements, and both count from the op's first element.  For the same reason a strip on an FP6
+// side is whole or absent (tf / ts are multiples of 4 along that side's contiguous direction): there
+// are no partial groups.  Access widths on an FP6 side: two non-temporal accesses per strip, 2 bytes
+// at p and 1 byte at p + 2.  Byte addresses have any parity (an op may start on an odd byte, and
+// ld = 4 mod 8 gives an odd byte pitch, so consecutive lines alternate parity); the 2-byte access is
+// made through a type of alignment 1 -- global memory takes it at an odd address, and written as two
+// byte accesses the compiler merges them into the same instruction anyway, but drops the load's
+// non-temporal hint -- so nothing is asked of the address, the side's VEC flag is vacuous
+// (strip_work.hpp gives it alignment 1) and the FULL / guarded split follows the other side's flag
+// and the sub-tile's extents alone.  No access,
+// reads included, touches a byte outside the 3 bytes of its own group, so the last group of a tile
+// may be the last three bytes of an allocation; a destination group is written whole by one lane: no
+// read-modify-write, no atomics.  cvt6 is round_finite<3, 1> / round_finite<2, 3> with the sign bit
+// kept and NaN -> 0x00, w6 a shift and a select (subnormal codes: an exact int -> fp32 conversion
+// times the step); the gfx950 packed FP6 conversion instructions are not used.  LDS: as for FP4, the
+// staged tile holds fp32 v and `red` fp32 bit patterns, so the bank argument above stands unchanged.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -111,6 +136,14 @@ template <>
 struct qlim<e2m1_t> {
     static constexpr uint32_t emax = 2, fmax = 0x40C00000u;  // 6
 };
+template <>
+struct qlim<e2m3_t> {
+    static constexpr uint32_t emax = 2, fmax = 0x40F00000u;  // 7.5
+};
+template <>
+struct qlim<e3m2_t> {
+    static constexpr uint32_t emax = 4, fmax = 0x41E00000u;  // 28
+};
 template <typename E>
 struct q_of {
     using type = e4m3_t;  // (unused for FLOAT destinations)
@@ -124,17 +157,28 @@ struct q_of<q4_e> {
     using type = e2m1_t;
 };
 
-// element offset -> offset in storage units of the side (packed e2m1: two elements per byte; `at`
-// is even there)
+template <typename T>
+struct q_of<q6_e<T>> {
+    using type = T;
+};
+template <typename E>
+struct is_q6 : std::false_type {};
+template <typename T>
+struct is_q6<q6_e<T>> : std::true_type {};
+
+// element offset -> offset in storage units of the side (packed e2m1: two elements per byte, `at`
+// is even there; packed FP6: four elements per three bytes, `at` is a multiple of 4 there)
 template <typename E>
 __device__ __forceinline__ int64_t elems(int64_t at) {
     if constexpr (std::is_same<E, q4_e>::value) return at >> 1;
+    if constexpr (is_q6<E>::value) return (at >> 2) * 3;
     return at;
 }
 // the strip at element offset `at` from p
 template <typename E>
 __device__ __forceinline__ strip<typename E::st> load_at(const typename E::st* p, int64_t at, int n, bool vec_ok) {
     if constexpr (std::is_same<E, q4_e>::value) return load_strip4(p + (at >> 1), n, vec_ok);
+    if constexpr (is_q6<E>::value) return load_strip6(p + (at >> 2) * 3, n);
     return load_strip(p + at, n, vec_ok);
 }
 template <typename E>
@@ -142,6 +186,8 @@ __device__ __forceinline__ void store_at(typename E::st* p, int64_t at, const st
                                          bool vec_ok) {
     if constexpr (std::is_same<E, q4_e>::value)
         store_strip4(p + (at >> 1), v, n, vec_ok);
+    else if constexpr (is_q6<E>::value)
+        store_strip6(p + (at >> 2) * 3, v, n);
     else
         store_strip(p + at, v, n, vec_ok);
 }
@@ -444,7 +490,7 @@ void launch_inst(const costa_scaled_op_t* d_ops, const uint64_t* d_work, const s
                                                                      sa, sc, int(ceil));
 }
 
-template <typename EQ>  // the codec of the pair's narrow type: q_e<Q> or q4_e
+template <typename EQ>  // the codec of the pair's narrow type: q_e<Q>, q4_e or q6_e<T>
 void launch_q(bool src_f, bool dst_f, const costa_scaled_op_t* d_ops, const uint64_t* d_work, const strip_list& l,
               const char* src_base, char* dst_base, const void* d_scalars, const mx_side& sa, const mx_side& sc,
               bool ceil, hipStream_t s) {
@@ -459,7 +505,7 @@ void launch_q(bool src_f, bool dst_f, const costa_scaled_op_t* d_ops, const uint
 }  // namespace
 
 bool mx_pair(costa_dtype_t src, costa_dtype_t dst) {
-    return fp8_pair(src, dst) || fp4_pair(src, dst);  // FLOAT -> Q, Q -> FLOAT, Q -> Q of one Q
+    return fp8_pair(src, dst) || packed_pair(src, dst);  // FLOAT -> Q, Q -> FLOAT, Q -> Q of one Q
 }
 
 void launch_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* d_ops,
@@ -478,8 +524,12 @@ void launch_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_sca
         launch_q<q_e<e4m3_t>>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, a_scales, c_scales, ceil, s);
     else if (nt == COSTA_FP8_E5M2)
         launch_q<q_e<e5m2_t>>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, a_scales, c_scales, ceil, s);
-    else
+    else if (nt == COSTA_FP4_E2M1)
         launch_q<q4_e>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, a_scales, c_scales, ceil, s);
+    else if (nt == COSTA_FP6_E2M3)
+        launch_q<q6_e<e2m3_t>>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, a_scales, c_scales, ceil, s);
+    else
+        launch_q<q6_e<e3m2_t>>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, a_scales, c_scales, ceil, s);
 }
 
 }  // namespace engine

@@ -43,23 +43,37 @@ size_t dtype_size(costa_dtype_t t) {
     case COSTA_FP4_E2M1:
         throw error(COSTA_ERR_ARG, "costa: FP4_E2M1 elements are half a byte: only the MX entry points "
                                    "(costa_hip_transform_mx, costa_hip_execute_tiles_mx) take them");
+    // (three quarters of a byte)
+    case COSTA_FP6_E2M3:
+    case COSTA_FP6_E3M2:
+        throw error(COSTA_ERR_ARG, std::string("costa: ") + dtype_name(t) +
+                                       " elements are three quarters of a byte: only the MX entry points "
+                                       "(costa_hip_transform_mx, costa_hip_execute_tiles_mx) take them");
     }
     throw error(COSTA_ERR_ARG, "unknown dtype");
 }
 
-esize elem_size(costa_dtype_t t) { return dtype_is_fp4(t) ? esize::packed4() : esize(dtype_size(t)); }
-size_t pkg_unit_size(costa_dtype_t pkg) { return dtype_is_fp4(pkg) ? 1 : dtype_size(pkg); }
-int64_t pkg_units(costa_dtype_t pkg, int64_t elems) { return dtype_is_fp4(pkg) ? elems / 2 : elems; }
+esize elem_size(costa_dtype_t t) {
+    return dtype_is_fp4(t) ? esize::packed(4) : dtype_is_fp6(t) ? esize::packed(6) : esize(dtype_size(t));
+}
+size_t pkg_unit_size(costa_dtype_t pkg) { return dtype_is_packed(pkg) ? 1 : dtype_size(pkg); }
+int64_t pkg_units(costa_dtype_t pkg, int64_t elems) {
+    return dtype_is_packed(pkg) ? int64_t(elem_size(pkg).bytes(uint64_t(elems))) : elems;
+}
 
 bool dtype_is_complex(costa_dtype_t t) { return t == COSTA_CFLOAT || t == COSTA_CDOUBLE; }
 bool dtype_is_half(costa_dtype_t t) { return t == COSTA_HALF || t == COSTA_BFLOAT16; }
 
 bool dtype_is_fp8(costa_dtype_t t) { return t == COSTA_FP8_E4M3 || t == COSTA_FP8_E5M2; }
 bool dtype_is_fp4(costa_dtype_t t) { return t == COSTA_FP4_E2M1; }
+bool dtype_is_fp6(costa_dtype_t t) { return t == COSTA_FP6_E2M3 || t == COSTA_FP6_E3M2; }
+int packed_group(costa_dtype_t t) { return dtype_is_fp4(t) ? 2 : dtype_is_fp6(t) ? 4 : 0; }
+bool dtype_is_packed(costa_dtype_t t) { return packed_group(t) != 0; }
+const char* packed_rule(costa_dtype_t t) { return dtype_is_fp6(t) ? "FP6 quad" : "FP4 pair"; }
 
 costa_dtype_t compute_dtype(costa_dtype_t src, costa_dtype_t dst) {
     return dtype_is_half(src) || dtype_is_half(dst) || dtype_is_fp8(src) || dtype_is_fp8(dst) ||
-                   dtype_is_fp4(src) || dtype_is_fp4(dst)
+                   dtype_is_packed(src) || dtype_is_packed(dst)
                ? COSTA_FLOAT
                : dst;
 }
@@ -74,8 +88,9 @@ bool fp8_pair(costa_dtype_t src, costa_dtype_t dst) {
            (src == COSTA_FLOAT && dtype_is_fp8(dst));
 }
 
-bool fp4_pair(costa_dtype_t src, costa_dtype_t dst) {
-    return (dtype_is_fp4(src) && (dst == src || dst == COSTA_FLOAT)) || (src == COSTA_FLOAT && dtype_is_fp4(dst));
+bool packed_pair(costa_dtype_t src, costa_dtype_t dst) {
+    return (dtype_is_packed(src) && (dst == src || dst == COSTA_FLOAT)) ||
+           (src == COSTA_FLOAT && dtype_is_packed(dst));
 }
 
 bool wide_pair(costa_dtype_t src, costa_dtype_t dst) {
@@ -99,12 +114,14 @@ const char* dtype_name(costa_dtype_t t) {
     case COSTA_FP8_E4M3: return "FP8_E4M3";
     case COSTA_FP8_E5M2: return "FP8_E5M2";
     case COSTA_FP4_E2M1: return "FP4_E2M1";
+    case COSTA_FP6_E2M3: return "FP6_E2M3";
+    case COSTA_FP6_E3M2: return "FP6_E3M2";
     }
     return "unknown";
 }
 
 costa_dtype_t plan_pkg_dtype(costa_dtype_t src, costa_dtype_t dst) {
-    if (fp8_pair(src, dst) || fp4_pair(src, dst)) return src;
+    if (fp8_pair(src, dst) || packed_pair(src, dst)) return src;
     return dtype_size(src) < dtype_size(dst) ? src : dst;
 }
 
@@ -137,9 +154,9 @@ bool any_half(const std::vector<job>& jobs) {
     return false;
 }
 
-bool any_fp4(const std::vector<job>& jobs) {
+bool any_packed(const std::vector<job>& jobs) {
     for (const job& jb : jobs)
-        if (jb.A && jb.C && (dtype_is_fp4(jb.A->dtype) || dtype_is_fp4(jb.C->dtype))) return true;
+        if (jb.A && jb.C && (dtype_is_packed(jb.A->dtype) || dtype_is_packed(jb.C->dtype))) return true;
     return false;
 }
 
@@ -253,16 +270,27 @@ struct view {
     }
 };
 
-// The evenness rule of an FP4 layout's tile (costa_hip.h, "MXFP4"): the target-coordinate rectangle
-// rr x cc of block b of L (seen transposed when `t`) starts at an even element offset from the block's
-// pointer and has an even extent along L's stored-contiguous (packed) dimension.
-void check_fp4_tile(const elayout& L, const eblock& b, bool t, const interval& rr, const interval& cc) {
+// The rule of a packed layout's tile (costa_hip.h, "MXFP4": the evenness rule, group 2; "MXFP6": the
+// quad rule, group 4): the target-coordinate rectangle rr x cc of block b of L (seen transposed when
+// `t`) starts at a whole number of packing groups from the block's pointer and has a whole number of
+// them along L's stored-contiguous (packed) dimension.
+void check_packed_tile(const elayout& L, const eblock& b, bool t, const interval& rr, const interval& cc) {
+    const int g = packed_group(L.dtype);
     const bool packed_rows = L.ordering != 'R';             // 'C': rows share bytes
     const interval& own_r = t ? cc : rr;                    // back to L's own coordinates
     const interval& own_c = t ? rr : cc;
     const interval& iv = packed_rows ? own_r : own_c;
     const int at = iv.start - (packed_rows ? b.rows.start : b.cols.start);
-    if (at % 2 == 0 && (iv.end - iv.start) % 2 == 0 && b.ld % 2 == 0) return;
+    if (at % g == 0 && (iv.end - iv.start) % g == 0 && b.ld % g == 0) return;
+    if (dtype_is_fp6(L.dtype))
+        throw error(COSTA_ERR_ARG,
+                    std::string("costa: FP6 quad: a tile splits a 3-byte group of the ") + dtype_name(L.dtype) +
+                        " layout: its " + (packed_rows ? "rows [" : "columns [") + std::to_string(iv.start) + ", " +
+                        std::to_string(iv.end) + ") start " + std::to_string(at) + " elements into the block at [" +
+                        std::to_string(packed_rows ? b.rows.start : b.cols.start) + ", ...) (ld " +
+                        std::to_string(b.ld) +
+                        "); offsets, extents and ld along the packed dimension must be multiples of 4, which "
+                        "makes the other layout's split points count through op");
     throw error(COSTA_ERR_ARG,
                 std::string("costa: FP4 pair: a tile splits a byte of the FP4_E2M1 layout: its ") +
                     (packed_rows ? "rows [" : "columns [") + std::to_string(iv.start) + ", " +
@@ -284,7 +312,7 @@ void check_fp4_tile(const elayout& L, const eblock& b, bool t, const interval& r
 void decompose(const view& sv, const view& dv, int tag, const tri_mask& mk, std::vector<side_tile>& out) {
     out.reserve(out.size() + sv.L->blocks.size() * 4);
     const esize elem = elem_size(sv.L->dtype);  // of the layout being decomposed
-    const bool fp4 = dtype_is_fp4(sv.L->dtype);
+    const bool packed = dtype_is_packed(sv.L->dtype);
     const auto& drs = dv.rsplit();
     const auto& dcs = dv.csplit();
     if (sv.rsplit().back() != drs.back() || sv.csplit().back() != dcs.back())
@@ -305,7 +333,7 @@ void decompose(const view& sv, const view& dv, int tag, const tri_mask& mk, std:
                 if (r.empty()) continue;
                 const int peer = dv.owner(i, j);
                 auto emit = [&](const interval& rr, const interval& cc, bool edge) {
-                    if (fp4) check_fp4_tile(*sv.L, b, sv.t, rr, cc);  // no tile may split a byte
+                    if (packed) check_packed_tile(*sv.L, b, sv.t, rr, cc);  // no tile may split a packing group
                     // back to the stored orientation of the block (block.cpp:85-99)
                     const tile_side ts = sub_tile(reinterpret_cast<uint64_t>(b.data), b.ld, b.rows.start,
                                                   b.cols.start, row_major, sv.t, rr.start, rr.end,
@@ -386,6 +414,8 @@ uint32_t scale_kind(costa_dtype_t dtype, const scal& s, bool copy_mode, bool con
     case COSTA_FP8_E4M3: return kind_t<float>(s, copy_mode, conj);
     case COSTA_FP8_E5M2: return kind_t<float>(s, copy_mode, conj);
     case COSTA_FP4_E2M1: return kind_t<float>(s, copy_mode, conj);
+    case COSTA_FP6_E2M3: return kind_t<float>(s, copy_mode, conj);
+    case COSTA_FP6_E3M2: return kind_t<float>(s, copy_mode, conj);
     }
     throw error(COSTA_ERR_ARG, "unknown dtype");
 }
@@ -418,13 +448,14 @@ std::vector<job_params> check_jobs(const std::vector<job>& jobs, int n_ranks, co
     if (jobs.size() > 0xFFFF) throw error(COSTA_ERR_ARG, "costa::transform: too many layout pairs");
     src_dtype = jobs[0].A->dtype;
     dtype = jobs[0].C->dtype;
-    if (any_fp4(jobs)) {  // packed e2m1: the MX transforms alone, one of their three pairs
+    if (any_packed(jobs)) {  // packed e2m1 / FP6: the MX transforms alone, one of the type's three pairs
         if (!(jobs.size() == 1 && jobs[0].mx))
-            throw error(COSTA_ERR_ARG, std::string("costa::transform: FP4_E2M1 layouts are taken by "
-                                                   "costa_hip_transform_mx alone, not ") +
+            throw error(COSTA_ERR_ARG, std::string("costa::transform: ") +
+                                           dtype_name(dtype_is_packed(src_dtype) ? src_dtype : dtype) +
+                                           " layouts are taken by costa_hip_transform_mx alone, not " +
                                            dtype_name(src_dtype) + " (A) -> " + dtype_name(dtype) +
                                            " (C) here");
-        if (!fp4_pair(src_dtype, dtype))
+        if (!packed_pair(src_dtype, dtype))
             throw error(COSTA_ERR_ARG, std::string("costa_hip_transform_mx: no MX transform for ") +
                                            dtype_name(src_dtype) + " -> " + dtype_name(dtype));
     } else if (any_scaled(jobs)) {  // scaled transforms: their own set of pairs, one unmasked layout pair
@@ -445,7 +476,7 @@ std::vector<job_params> check_jobs(const std::vector<job>& jobs, int n_ranks, co
     // (half precision: H -> H, FLOAT -> H, H -> FLOAT, computed in fp32; FP8: the same three shapes)
     const bool pair_ok =
         src_dtype == dtype || half_pair(src_dtype, dtype) || fp8_pair(src_dtype, dtype) ||
-        fp4_pair(src_dtype, dtype) ||
+        packed_pair(src_dtype, dtype) ||
         (src_dtype == COSTA_FLOAT && dtype == COSTA_DOUBLE) || (src_dtype == COSTA_DOUBLE && dtype == COSTA_FLOAT) ||
         (src_dtype == COSTA_CFLOAT && dtype == COSTA_CDOUBLE) || (src_dtype == COSTA_CDOUBLE && dtype == COSTA_CFLOAT);
     if (!pair_ok)
@@ -520,12 +551,13 @@ std::unique_ptr<plan> make_plan(const std::vector<job>& jobs, int rank, int n_ra
     // narrowing pairs convert in PACK, widening pairs in UNPACK); all equal for same-type plans.
     // FP8 pairs carry A's type, FLOAT -> Q too: its source is not rounded before the arithmetic,
     // which happens in UNPACK
-    // (an FP4 side is half a byte per element: esize; a packed package -- A holds FP4 -- is counted
-    // in BYTES, `units`, so that no count, displacement or round boundary falls inside a byte)
+    // (an FP4 side is half a byte per element, an FP6 side three quarters: esize; a packed package --
+    // A holds FP4 or FP6 -- is counted in BYTES, `units`, so that no count, displacement or round
+    // boundary falls inside a byte)
     const esize EA = elem_size(p->src_dtype), EC = elem_size(p->dtype);
     p->pkg_dtype = plan_pkg_dtype(p->src_dtype, p->dtype);
     const esize EP = elem_size(p->pkg_dtype);
-    const bool packed_pkg = dtype_is_fp4(p->pkg_dtype);
+    const bool packed_pkg = dtype_is_packed(p->pkg_dtype);
     auto units = [&](int64_t elems) { return pkg_units(p->pkg_dtype, elems); };
     std::vector<side_tile> send, recv;
     for (const job& jb : jobs) p->slots.push_back(jb.s);
@@ -606,14 +638,16 @@ std::unique_ptr<plan> make_plan(const std::vector<job>& jobs, int rank, int n_ra
         const tag_info& ti = tags[size_t(m.tag)];
         const int64_t n = units(int64_t(m.n_rows) * m.n_cols);
         // copy_to_buffer: stored shape and ordering, dense, no transform (cpp:191-217)
-        if (packed_pkg)  // a copy of bytes: half the extent and half the pitch along the packed dimension
-            p->pack_ops.push_back(tile_op(ti.a_cm ? m.n_rows / 2 : m.n_rows, ti.a_cm ? m.n_cols : m.n_cols / 2,
-                                          uint64_t(m.ptr), m.ld / 2, ti.a_cm, uint64_t(off), 0, ti.a_cm, false,
+        if (packed_pkg) {  // a copy of bytes: the extent and the pitch along the packed dimension in bytes
+            auto pb = [&](int n) { return int(EP.bytes(uint64_t(n))); };  // (1/2 for FP4, 3/4 for FP6)
+            p->pack_ops.push_back(tile_op(ti.a_cm ? pb(m.n_rows) : m.n_rows, ti.a_cm ? m.n_cols : pb(m.n_cols),
+                                          uint64_t(m.ptr), pb(m.ld), ti.a_cm, uint64_t(off), 0, ti.a_cm, false,
                                           false, COSTA_SCALE_BITCOPY, 0, 1, 1));
-        else
+        } else {
             p->pack_ops.push_back(tile_op(m.n_rows, m.n_cols, uint64_t(m.ptr), m.ld, ti.a_cm,
                                           EP.bytes(uint64_t(off)), 0, ti.a_cm, false, false,
                                           COSTA_SCALE_BITCOPY, 0, EA, EP));
+        }
         at_pack.push_back(&m);
         p->send_counts[size_t(m.peer)] += n;
         off += n;

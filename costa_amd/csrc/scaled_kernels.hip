@@ -549,11 +549,14 @@ strip_list build_scaled_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
                              const std::vector<costa_scaled_op_t>& ops, uint64_t src_base,
                              uint64_t dst_base, std::vector<costa_scaled_op_t>& ordered,
                              std::vector<uint64_t>& work, bool dst_order) {
-    // (a packed FP4 side of an MX pair: half a byte per element, its strip of 4 is 2 bytes)
+    // (a packed side of an MX pair: its strip of 4 is 2 bytes for FP4, and 3 bytes at any address for
+    // FP6, where the flag is vacuous)
     const esize ES = elem_size(src_dtype), ED = elem_size(dst_dtype);
-    strip_align al = strip_alignment(strip_family::scaled, std::max<uint64_t>(1, ES.hb / 2), std::max<uint64_t>(1, ED.hb / 2));
+    strip_align al = strip_alignment(strip_family::scaled, std::max<uint64_t>(1, ES.qb / 4), std::max<uint64_t>(1, ED.qb / 4));
     if (dtype_is_fp4(src_dtype)) al.src = 2;
     if (dtype_is_fp4(dst_dtype)) al.dst = 2;
+    if (dtype_is_fp6(src_dtype)) al.src = 1;
+    if (dtype_is_fp6(dst_dtype)) al.dst = 1;
     for (const costa_scaled_op_t& t : ops) {  // (empty ops are skipped unchecked, as by the builder)
         if (t.op.nf <= 0 || t.op.ns <= 0) continue;
         if (t.op.lds < 0 || t.op.ldd < 0) throw error(COSTA_ERR_ARG, "costa: negative leading dimension");

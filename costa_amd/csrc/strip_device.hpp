@@ -67,6 +67,15 @@ struct q4_e {
     static __device__ __forceinline__ float widen(uint8_t c) { return e2m1_t::widen(c); }
     static __device__ __forceinline__ uint8_t narrow(float x) { return uint8_t(e2m1_t::narrow(x)); }
 };
+// packed FP6 (COSTA_FP6_E2M3 / COSTA_FP6_E3M2; T = e2m3_t / e3m2_t): a strip<uint8_t> holds 4 unpacked
+// codes, one per byte; four codes share three stored bytes (load_strip6 / store_strip6 below)
+template <typename T>
+struct q6_e {
+    using st = uint8_t;
+    using ct = float;
+    static __device__ __forceinline__ float widen(uint8_t c) { return T::widen(c); }
+    static __device__ __forceinline__ uint8_t narrow(float x) { return uint8_t(T::narrow(x)); }
+};
 template <typename H>  // the FLOAT source of a FLOAT -> H pair: rounded to H first
 struct f32_via {
     using st = float;
@@ -162,6 +171,30 @@ __device__ __forceinline__ void store_strip4(uint8_t* p, const strip<uint8_t>& i
         if (n >= 2) p[0] = uint8_t(lo);
         if (n >= SV) p[1] = uint8_t(hi);
     }
+}
+
+// a strip of 4 packed FP6 codes: one packing group, 3 bytes at p (any address), the first element in
+// the lowest bits of w = c0 | c1 << 6 | c2 << 12 | c3 << 18.  Two non-temporal accesses: the low 2
+// bytes at p through a type of alignment 1 (global memory takes a 2-byte access at an odd address; no
+// alignment is asked of p) and the third byte at p + 2, so no byte outside the group is touched.  On
+// an FP6 side a strip is whole or absent (the quad rule), so n < 4 moves nothing
+typedef uint16_t u16_any __attribute__((aligned(1)));
+__device__ __forceinline__ strip<uint8_t> load_strip6(const uint8_t* p, int n) {
+    strip<uint8_t> out{};
+    if (n >= SV) {
+        const uint32_t w = uint32_t(__builtin_nontemporal_load(reinterpret_cast<const u16_any*>(p))) |
+                           uint32_t(__builtin_nontemporal_load(p + 2)) << 16;
+#pragma unroll
+        for (int k = 0; k < SV; ++k) out.e[k] = uint8_t(w >> (6 * k) & 63u);
+    }
+    return out;
+}
+__device__ __forceinline__ void store_strip6(uint8_t* p, const strip<uint8_t>& in, int n) {
+    if (n < SV) return;
+    const uint32_t w = uint32_t(in.e[0] & 63u) | uint32_t(in.e[1] & 63u) << 6 | uint32_t(in.e[2] & 63u) << 12 |
+                       uint32_t(in.e[3] & 63u) << 18;
+    __builtin_nontemporal_store(uint16_t(w), reinterpret_cast<u16_any*>(p));
+    __builtin_nontemporal_store(uint8_t(w >> 16), p + 2);
 }
 
 // a strip of the staged tile (compute type; 16-byte aligned)

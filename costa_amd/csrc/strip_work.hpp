@@ -25,6 +25,11 @@ namespace engine {
 //   Q -> Q                      16 (its whole copies) 16                   16
 //   scaled pair                 4                     min(16, 4 x element size)
 //   MX pair with packed FP4     4                     2 on the FP4 side (a strip is 2 bytes)
+//   MX pair with packed FP6     4                     1 on the FP6 side: a strip is 3 bytes at any
+//                                                     address, moved by a 2-byte and a 1-byte access
+//                                                     that ask nothing of it, so the flag is
+//                                                     always set there (vacuous) and a whole sub-tile
+//                                                     takes the FULL path on the other side's flag alone
 //   tri                         16 / element          16                   16
 enum class strip_family { pair, scaled, tri };
 struct strip_align {

@@ -409,6 +409,32 @@ struct e2m1_t {
     }
 };
 
+// The packed 6-bit types (costa_hip.h, "MXFP6"): one OCP FP6 code, bit 5 the sign, then the exponent
+// and MB mantissa bits; no inf, no NaN.  e2m3: bias 1, subnormal step 1/8, largest 7.5; e3m2: bias 3,
+// subnormal step 1/16, largest 28.
+template <int MB, int BIAS>
+struct fp6_t {
+    // w6: the 5 magnitude bits shifted to fp32's exponent / mantissa boundary are the value /
+    // 2^(127 - BIAS) for the normal codes; a subnormal code is its mantissa times the step (exact)
+    static __device__ __forceinline__ float widen(uint32_t c) {
+        const uint32_t m = c & 31u;
+        const uint32_t a = m >= (1u << MB) ? (m << (23 - MB)) + (uint32_t(127 - BIAS) << 23)
+                                           : f2u(float(m) * (1.0f / float(1 << (MB + BIAS - 1))));
+        return u2f(a | ((c & 32u) << 26));
+    }
+    // cvt6 of a finite t with |t| <= fmax (the caller clamps, so nothing overflows): round_finite's
+    // round-to-nearest-even on the dropped bits IS the tie rule of the type -- a tie goes to the code
+    // whose mantissa is even, subnormals included (below the smallest normal one exact fp32 addition
+    // rounds to the subnormal step).  The sign bit is always kept; NaN -> 0x00
+    static __device__ __forceinline__ uint32_t narrow(float x) {
+        const uint32_t u = f2u(x), a = u & 0x7FFFFFFFu;
+        if (a > 0x7F800000u) return 0u;
+        return (u >> 26 & 32u) | round_finite<MB, BIAS>(a);
+    }
+};
+using e2m3_t = fp6_t<3, 1>;
+using e3m2_t = fp6_t<2, 3>;
+
 }  // namespace
 }  // namespace engine
 }  // namespace costa

@@ -16,18 +16,20 @@
 namespace costa {
 namespace engine {
 
-// The size of one element of a side, in half-bytes: COSTA_FP4_E2M1 packs two elements into a byte
-// (costa_hip.h, "MXFP4"), so no byte count says it.  A plain byte count converts implicitly; bytes(n)
-// is exact for an FP4 side because the evenness rule keeps every n it is asked about even.
+// The size of one element of a side, in quarter-bytes: COSTA_FP4_E2M1 packs two elements into a byte
+// (costa_hip.h, "MXFP4") and the FP6 types four into three bytes ("MXFP6"), so no byte count says it.
+// A plain byte count converts implicitly; bytes(n) is exact for a packed side because its rule (the
+// evenness rule, the quad rule) keeps every n it is asked about a multiple of the packing group.
 struct esize {
-    uint64_t hb;  // half-bytes per element
-    COSTA_HD constexpr esize(uint64_t bytes) : hb(2 * bytes) {}
-    COSTA_HD static constexpr esize packed4() {
+    uint64_t qb;  // quarter-bytes per element
+    COSTA_HD constexpr esize(uint64_t bytes) : qb(4 * bytes) {}
+    // `bits` per element of a packed sub-byte type: 4 or 6
+    COSTA_HD static constexpr esize packed(unsigned bits) {
         esize e(0);
-        e.hb = 1;
+        e.qb = bits / 2;
         return e;
     }
-    COSTA_HD constexpr uint64_t bytes(uint64_t n) const { return n * hb / 2; }
+    COSTA_HD constexpr uint64_t bytes(uint64_t n) const { return n * qb / 4; }
 };
 
 // The stored-orientation sub-tile of a block for the target-coordinate rectangle
@@ -46,7 +48,7 @@ COSTA_HD inline tile_side sub_tile(uint64_t data, int ld, int block_row0, int bl
     const int sc0 = t ? r0 : c0, sc1 = t ? r1 : c1;
     const int64_t dr = sr0 - block_row0, dc = sc0 - block_col0;
     const int64_t off = row_major ? dr * ld + dc : dc * ld + dr;
-    return {data + uint64_t(off * int64_t(elem.hb) / 2), ld, sr1 - sr0, sc1 - sc0};
+    return {data + uint64_t(off * int64_t(elem.qb) / 4), ld, sr1 - sr0, sc1 - sc0};
 }
 
 // copy_and_transform (memory_utils.hpp:339-412) as one op: an ordering mismatch is itself a

@@ -59,7 +59,9 @@ typedef enum {
     COSTA_BFLOAT16 = 6, /* bfloat16, 2 bytes, raw bits */
     COSTA_FP8_E4M3 = 7, /* OCP e4m3fn, 1 byte, raw bits ("FP8" below) */
     COSTA_FP8_E5M2 = 8, /* OCP e5m2, 1 byte, raw bits */
-    COSTA_FP4_E2M1 = 9  /* OCP e2m1, 4 bits, two codes per byte ("MXFP4" below; MX entry points only) */
+    COSTA_FP4_E2M1 = 9, /* OCP e2m1, 4 bits, two codes per byte ("MXFP4" below; MX entry points only) */
+    COSTA_FP6_E2M3 = 10, /* OCP e2m3, 6 bits, four codes per three bytes ("MXFP6" below; MX entry points only) */
+    COSTA_FP6_E3M2 = 11  /* OCP e3m2, 6 bits, packed the same way */
 } costa_dtype_t;
 
 typedef struct costa_layout_s* costa_layout_t;
@@ -571,8 +573,71 @@ int costa_hip_mx_check_scales(const costa_mx_scales_t* s, int64_t rows, int64_t 
  * leading dimension on each FP4 side) to caller-given ops.  A violation is COSTA_ERR_ARG with "FP4
  * pair" and the offending interval in the message, before anything is written.
  *
- * Not covered: MXFP6, NVFP4 (16-element blocks, e4m3 scales), bf16 / fp16 sides, host-resident FP4
+ * Not covered: NVFP4 (16-element blocks, e4m3 scales), bf16 / fp16 sides, host-resident FP4
  * layouts, batches, masks, in-place calls, odd extents (a half-filled last byte), swizzled scales. */
+
+/* ---- MXFP6 (MI355X-native): packed e2m3 / e3m2 layouts in the MX block-scaled transforms ----
+ * Element types.  COSTA_FP6_E2M3 = 10 and COSTA_FP6_E3M2 = 11 (OCP Microscaling v1.0 FP6).  A code is
+ * 6 bits, bit 5 the sign.  Neither type has an infinity or a NaN.
+ *          exponent bits (bias)  mantissa bits  magnitudes (mantissa m, exponent e)              largest             emax
+ *   e2m3   4..3 (1)              2..0           e = 0: m / 8, else (1 + m / 8) * 2^(e - 1):      7.5 (0x40F00000)    2
+ *                                               0, 0.125 .. 0.875, 1 .. 7.5
+ *   e3m2   4..2 (3)              1..0           e = 0: m / 16, else (1 + m / 4) * 2^(e - 3):     28 (0x41E00000)     4
+ *                                               0, 0.0625, 0.125, 0.1875, 0.25 .. 28
+ *
+ * Packing.  Four codes share three bytes along the layout's stored-contiguous dimension (rows for
+ * 'C', columns for 'R').  Element indices count from the first element of the local block's buffer.
+ * Group g holds elements 4g .. 4g + 3 in bytes 3g .. 3g + 2: with w = c0 | c1 << 6 | c2 << 12 |
+ * c3 << 18 the bytes are w & 0xFF, (w >> 8) & 0xFF, w >> 16 -- the lowest bits hold the first
+ * element, which continues the FP4 rule.
+ *
+ * Layouts.  Every count of the layout calls stays in ELEMENTS (m, n, block sizes, i / j, sub_m /
+ * sub_n, lld / ld, split points).  Pointers address bytes and the byte pitch is 3 * ld / 4.  A block
+ * pointer may sit at any byte address: there is no alignment requirement.
+ *
+ * Codec.  w6(code) is the exact fp32 value; the code with only the sign bit set is -0.0.  cvt6(t),
+ * for finite |t| <= fmax, rounds to the nearest representable magnitude; ties go to the code whose
+ * mantissa is even (round-to-nearest-even on the dropped bits, subnormals included).  The sign bit of
+ * t is always kept: -0.0 and -0.01 give 0x20.  cvt6(NaN) = 0x00, which occurs only in a block whose
+ * scale byte is 255.
+ *
+ * Block rule.  The MXFP8 rule with the type's emax and fmax: per block of 32 elements of C along
+ * c_scales.axis, amax = the unsigned maximum of the bits of |v|, e = amax >> 23; e == 255 gives
+ * E = 255 and the block stores code 0x00 everywhere, else E = max(e - emax, 0); with COSTA_MX_CEIL E
+ * is one higher (at most 254) where amax * pow2(254 - E) > fmax.  q = cvt6(clamp(v * pow2(254 - E),
+ * -fmax, fmax)), SC[block] = E.  Under the floor rule a block's maximum lands in [4, 8) for e2m3 and
+ * [16, 32) for e3m2; values above 7.5 / 28 saturate, so the clamp is load-bearing.
+ *
+ * Dequantise.  x = w6(a) * pow2(SA[block]) is one rounded fp32 product; the ordinary alpha / beta
+ * branches follow in fp32 with contraction off.
+ *
+ * Accepted calls (costa_hip_transform_mx, _async, costa_hip_execute_tiles_mx; the descriptor,
+ * rounding, stride, device-residency, in-place and "MX block" checks apply unchanged), for each FP6
+ * type P:
+ *   quantise    COSTA_FLOAT -> P   c_scales, beta = 0
+ *   dequantise  P -> COSTA_FLOAT   a_scales
+ *   requantise  P -> P             both, beta = 0
+ * P with any other type is COSTA_ERR_ARG "no MX transform", naming both types: the other FP6 type,
+ * FP4, FP8, half, double, int32 and complex.  Every other entry point refuses an FP6 layout or dtype
+ * with COSTA_ERR_ARG naming the type, except costa_hip_plan_export_scaled, which plans the six pairs
+ * (host only).
+ *
+ * Quad rule ("FP6 quad").  No tile may split a 3-byte group.  At creation of an FP6 layout: ld is a
+ * multiple of 4, and along the packed dimension the matrix extent, the layout's own split points and
+ * (block-cyclic) the sub-matrix offset, the sub-matrix extent and every local block offset are
+ * multiples of 4.  At plan time, for every op on each FP6 side: the op's element offset from its
+ * block pointer and its extent along that side's stored-contiguous dimension are multiples of 4 --
+ * through op, the OTHER layout's split points count too.  costa_hip_execute_tiles_mx applies the
+ * per-op half (extent and leading dimension) to caller-given ops.  A violation is COSTA_ERR_ARG with
+ * "FP6 quad", the type's name and the offending interval, raised before anything is written.
+ *
+ * Package.  When A holds FP6 the package is packed: its PACK ops are 1-byte copy ops (3 nf / 4 x ns,
+ * pitch 3 lds / 4) and the send / receive counts and displacements count BYTES.  A round boundary may
+ * fall inside a group but never inside an op's bytes: ops are assigned to rounds whole.
+ * COSTA_FLOAT -> P sends fp32, as for FP8 / FP4.
+ *
+ * Not covered: NVFP4, bf16 / fp16 sides, host-resident packed layouts, batches, masks, in-place
+ * calls, extents off the grid of 4 (2 for FP4), swizzled scales, FP6 <-> FP4 / FP8 requantise. */
 
 /* ---- stream-ordered variants (MI355X-native; no reference counterpart) ----
  * Enqueue the transform and return.  Layouts must be device-resident.  `stream` (a hipStream_t,
