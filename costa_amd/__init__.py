@@ -39,6 +39,8 @@ __all__ = [
     "transform_amax", "layout_amax", "execute_tiles_amax", "amax_items",
     "MxScales", "MX_ROWS", "MX_COLS", "MX_FLOOR", "MX_CEIL", "mx_scales", "transform_mx",
     "execute_tiles_mx", "mx_items", "mx_check_ops", "mx_check_scales",
+    "BlockScales", "BLOCK_EXACT", "BLOCK_POW2", "block_scales", "transform_block_scaled",
+    "execute_tiles_block_scaled", "block_items", "block_check_ops", "block_check_scales",
 ]
 
 FLOAT, DOUBLE, CFLOAT, CDOUBLE, INT32 = 0, 1, 2, 3, 4
@@ -185,6 +187,21 @@ class MxScales(C.Structure):
         super().__init__(data, axis, block_stride, line_stride)
 
 
+# Block-scaled FP8 transforms (costa_hip.h): how the fp32 scale of a block is rounded
+BLOCK_EXACT, BLOCK_POW2 = 0, 1
+BLOCK_SHAPES = ((1, 128), (128, 1), (128, 128))
+
+
+class BlockScales(C.Structure):
+    """costa_block_scales_t: the fp32 scale of block (bi, bj) -- rows bi*block_rows .., columns
+    bj*block_cols .. -- is data[bi*row_stride + bj*col_stride] (strides in floats)."""
+    _fields_ = [("data", C.c_void_p), ("block_rows", C.c_int32), ("block_cols", C.c_int32),
+                ("row_stride", C.c_int64), ("col_stride", C.c_int64)]
+
+    def __init__(self, data=0, block_rows=128, block_cols=128, row_stride=0, col_stride=0):
+        super().__init__(data, block_rows, block_cols, row_stride, col_stride)
+
+
 class PlanInfo(C.Structure):
     _fields_ = [("n_local", C.c_int64), ("n_pack", C.c_int64), ("n_unpack", C.c_int64),
                 ("send_elems", C.c_int64), ("recv_elems", C.c_int64),
@@ -312,6 +329,16 @@ def lib():
         "costa_hip_execute_tiles_mx": (i, [i, i, C.POINTER(ScaledOp), i64, vp, vp, vp, i, C.POINTER(MxScales),
                                            C.POINTER(MxScales), i, i64, i64, i, i]),
         "costa_hip_mx_items": (i, [C.POINTER(i64), i]),
+        "costa_hip_transform_block_scaled": (i, [vp, vp, c, vp, vp, C.POINTER(BlockScales),
+                                                 C.POINTER(BlockScales), i, vp]),
+        "costa_hip_transform_block_scaled_async": (i, [vp, vp, c, vp, vp, C.POINTER(BlockScales),
+                                                       C.POINTER(BlockScales), i, vp, vp]),
+        "costa_hip_execute_tiles_block_scaled": (i, [i, i, C.POINTER(ScaledOp), i64, vp, vp, vp, i,
+                                                     C.POINTER(BlockScales), C.POINTER(BlockScales), i, i64,
+                                                     i64, i, i]),
+        "costa_hip_block_items": (i, [C.POINTER(i64), i]),
+        "costa_hip_block_check_ops": (i, [C.POINTER(ScaledOp), i64, i, i, i64, i64]),
+        "costa_hip_block_check_scales": (i, [C.POINTER(BlockScales), i64, i64]),
         "costa_hip_mx_check_ops": (i, [C.POINTER(ScaledOp), i64, i, i64, i64]),
         "costa_hip_mx_check_scales": (i, [C.POINTER(MxScales), i64, i64]),
         "costa_hip_plan_export_scaled": (i, [vp, vp, c, vp, vp, i, i, C.POINTER(ScaledPlanInfo), vp, vp,
@@ -1120,6 +1147,128 @@ def mx_check_scales(d: MxScales, rows: int, cols: int):
     """The stride rule of a descriptor for a rows x cols matrix (host only): positive strides, no two
     (block, line) entries on one byte."""
     _check(lib().costa_hip_mx_check_scales(C.byref(d), rows, cols))
+
+
+# ------------------------------------------------------------------ block-scaled FP8 transforms
+def _block_rounding(rounding) -> int:
+    if rounding in (BLOCK_EXACT, "exact"):
+        return BLOCK_EXACT
+    if rounding in (BLOCK_POW2, "pow2"):
+        return BLOCK_POW2
+    if isinstance(rounding, int):  # (an unknown value is the library's to refuse)
+        return rounding
+    raise ValueError(f"rounding: BLOCK_EXACT / 'exact' or BLOCK_POW2 / 'pow2', not {rounding!r}")
+
+
+def _block_want(block, shape):
+    rows, cols = shape
+    return ((rows + block[0] - 1) // block[0], (cols + block[1] - 1) // block[1])
+
+
+def block_scales(tensor, block, shape=None) -> BlockScales:
+    """The descriptor of a 2-D ``float32`` torch CUDA tensor of scales indexed ``[block row, block
+    column]``; the strides are the tensor's.  ``block`` is (1, 128), (128, 1) or (128, 128).  With
+    ``shape`` = (rows, cols) of the matrix the tensor's extent is checked too.  ValueError for a wrong
+    dtype, device, rank, block shape, stride or extent.  The descriptor keeps a reference to the
+    tensor."""
+    block = tuple(int(b) for b in block)
+    if block not in BLOCK_SHAPES:
+        raise ValueError(f"block_scales: block {block}, the shapes are (1, 128), (128, 1) and (128, 128)")
+    if type(tensor).__module__.split(".")[0] != "torch":
+        raise ValueError(f"block_scales: a torch CUDA tensor, not {type(tensor)}")
+    if str(tensor.dtype) != "torch.float32":
+        raise ValueError(f"block_scales: dtype {tensor.dtype}, the scales are float32")
+    if not tensor.is_cuda:
+        raise ValueError("block_scales: the tensor must be device-resident (a CUDA tensor)")
+    if tensor.dim() != 2:
+        raise ValueError(f"block_scales: a 2-D tensor indexed [block row, block column], not {tensor.dim()}-D")
+    if shape is not None and tuple(tensor.shape) != _block_want(block, shape):
+        raise ValueError(f"block_scales: shape {tuple(tensor.shape)}, the matrix needs "
+                         f"{_block_want(block, shape)} ([block rows, block columns])")
+    rs, cs = tensor.stride()
+    if (tensor.shape[0] > 1 and rs <= 0) or (tensor.shape[1] > 1 and cs <= 0):
+        raise ValueError("block_scales: the strides must be positive")
+    d = BlockScales(tensor.data_ptr(), block[0], block[1], max(rs, 1), max(cs, 1))
+    d._keep = tensor
+    return d
+
+
+def _block_arg(d, what, shape=None):
+    """a descriptor by reference; one made from a tensor is checked against the matrix's extent"""
+    if d is None:
+        return None
+    if not isinstance(d, BlockScales):
+        raise ValueError(f"{what}: a BlockScales descriptor (costa.block_scales(tensor, block)), not {type(d)}")
+    t = getattr(d, "_keep", None)
+    if t is not None and shape is not None and (d.block_rows, d.block_cols) in BLOCK_SHAPES:
+        want = _block_want((d.block_rows, d.block_cols), shape)
+        if tuple(t.shape) != want:
+            raise ValueError(f"{what}: shape {tuple(t.shape)}, the {shape[0]} x {shape[1]} matrix needs {want} "
+                             "([block rows, block columns])")
+    return C.byref(d)
+
+
+def transform_block_scaled(A: Layout, Cl: Layout, comm: Comm, trans: str = "N", alpha=1.0, beta=0.0,
+                           a_scales=None, c_scales=None, rounding="exact", stream=None):
+    """Block-scaled FP8 transform (costa_hip_transform_block_scaled; costa_hip.h, "Block-scaled FP8
+    transforms (fp32 scales)"): quantise (FLOAT -> FP8, ``c_scales``), dequantise (FP8 -> FLOAT,
+    ``a_scales``) or requantise (FP8 -> the same FP8, both; the block shapes may differ) while
+    redistributing, one fp32 scale per 1 x 128, 128 x 1 or 128 x 128 block.  ``a_scales`` is indexed by
+    A's matrix as stored (before ``trans``), ``c_scales`` by C's; ``rounding`` is "exact"
+    (S = amax / fmax) or "pow2" (the next power of two).  beta must be 0 with ``c_scales``, and no
+    tile may split a block of C (CostaError with "scale block").  With ``stream`` the call is
+    stream-ordered and the tensors must stay valid until the stream has passed it.  With several ranks
+    each rank writes the ``c_scales`` of its own blocks only (merge zero-initialised tensors with a
+    MAX all-reduce) and needs the ``a_scales`` of every block it reads."""
+    if not isinstance(A, Layout) or not isinstance(Cl, Layout):
+        raise CostaError(1, "costa: batches of block-scaled layout pairs are not supported")
+    code = _scalar_code(A.dtype, Cl.dtype)
+    ab, bb = _scalar_bytes(code, alpha), _scalar_bytes(code, beta)
+    args = (A.handle, Cl.handle, _chr(trans), ab, bb, _block_arg(a_scales, "a_scales", A.shape()),
+            _block_arg(c_scales, "c_scales", Cl.shape()), _block_rounding(rounding), comm.handle)
+    if stream is None:
+        _check(lib().costa_hip_transform_block_scaled(*args))
+    else:
+        s = getattr(stream, "cuda_stream", stream) or 0
+        _check(lib().costa_hip_transform_block_scaled_async(*args, C.c_void_p(s)))
+
+
+def execute_tiles_block_scaled(src_dtype, dst_dtype, ops: np.ndarray, scalars: np.ndarray, m: int, n: int,
+                               src_base=0, dst_base=0, a_scales=None, c_scales=None, rounding="exact",
+                               a_transposed: bool = False, device: int = 0):
+    """Run a list of scaled ops (SCALED_OP_DTYPE) in one launch of the block-scaled kernel; ``m`` x ``n``
+    is C's matrix, fp32 ``scalars``; with ``a_transposed`` A's matrix is n x m and ``a_scales`` is
+    indexed by it (costa_hip_execute_tiles_block_scaled)."""
+    sc_, dc_ = element_code(src_dtype), element_code(dst_dtype)
+    ops = np.ascontiguousarray(ops, dtype=SCALED_OP_DTYPE)
+    sc = np.ascontiguousarray(scalars, dtype=np.float32).reshape(-1)
+    assert sc.size % 2 == 0
+    _check(lib().costa_hip_execute_tiles_block_scaled(
+        sc_, dc_, ops.ctypes.data_as(C.POINTER(ScaledOp)), ops.size, C.c_void_p(_ptr(src_base)),
+        C.c_void_p(_ptr(dst_base)), sc.ctypes.data, sc.size // 2, _block_arg(a_scales, "a_scales"),
+        _block_arg(c_scales, "c_scales"), _block_rounding(rounding), m, n, int(a_transposed), device))
+
+
+def block_items(reset: bool = False) -> int:
+    """Work items run by the block-scaled kernels since the last reset (64 x 64 sub-tiles of
+    dequantising lists, 128 x 128 regions of quantising ones)."""
+    v = C.c_int64(0)
+    _check(lib().costa_hip_block_items(C.byref(v), int(reset)))
+    return v.value
+
+
+def block_check_ops(ops: np.ndarray, block, m: int, n: int):
+    """The tile-boundary rule of ``c_scales`` on scaled ops (host only): CostaError with "scale block"
+    when an op splits a ``block`` = (rows, cols) block of C's m x n matrix."""
+    ops = np.ascontiguousarray(ops, dtype=SCALED_OP_DTYPE)
+    _check(lib().costa_hip_block_check_ops(ops.ctypes.data_as(C.POINTER(ScaledOp)), ops.size, int(block[0]),
+                                           int(block[1]), m, n))
+
+
+def block_check_scales(d: BlockScales, rows: int, cols: int):
+    """The rules of a descriptor for a rows x cols matrix (host only): the block shape, 4-byte aligned
+    data, positive strides, no two blocks on one float."""
+    _check(lib().costa_hip_block_check_scales(C.byref(d), rows, cols))
 
 
 @dataclass

@@ -738,6 +738,90 @@ int costa_hip_mx_check_scales(const costa_mx_scales_t* s, int64_t rows, int64_t 
     });
 }
 
+namespace {
+// the one job of costa_hip_transform_block_scaled: a scaled job (the scaled plan, unchanged) whose
+// lists run on block_kernel; an absent descriptor (NULL, or NULL data) is all zeros
+std::vector<job> make_block_job(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                                const void* beta, const costa_block_scales_t* a_scales,
+                                const costa_block_scales_t* c_scales, int rounding) {
+    check_handles(1, &A, &C);
+    const costa_dtype_t a = A->e.dtype, c = C->e.dtype;
+    if (!costa::engine::block_pair(a, c))  // (before the scaled job's own pair check)
+        throw costa::engine::error(COSTA_ERR_ARG,
+                                   std::string("costa_hip_transform_block_scaled: no block-scaled transform for ") +
+                                       costa::engine::dtype_name(a) + " -> " + costa::engine::dtype_name(c) +
+                                       " (FLOAT -> FP8, FP8 -> FLOAT, FP8 -> the same FP8)");
+    auto jobs = make_scaled_job(A, C, trans, alpha, beta, nullptr, nullptr);
+    jobs[0].blk = true;
+    if (a_scales && a_scales->data) jobs[0].a_blocks = *a_scales;
+    if (c_scales && c_scales->data) jobs[0].c_blocks = *c_scales;
+    jobs[0].blk_rounding = rounding;
+    return jobs;
+}
+}  // namespace
+
+int costa_hip_transform_block_scaled(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                                     const void* beta, const costa_block_scales_t* a_scales,
+                                     const costa_block_scales_t* c_scales, int rounding, costa_comm_t comm) {
+    static_assert(sizeof(costa_block_scales_t) == 32, "descriptor size");
+    return gpu_guarded([&] {
+        if (!comm || !alpha || !beta) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::transform(make_block_job(A, C, trans, alpha, beta, a_scales, c_scales, rounding), comm->c);
+    });
+}
+
+int costa_hip_transform_block_scaled_async(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                                           const void* beta, const costa_block_scales_t* a_scales,
+                                           const costa_block_scales_t* c_scales, int rounding,
+                                           costa_comm_t comm, void* stream) {
+    return gpu_guarded([&] {
+        if (!comm || !alpha || !beta) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::transform(make_block_job(A, C, trans, alpha, beta, a_scales, c_scales, rounding), comm->c,
+                                 stream, true);
+    });
+}
+
+int costa_hip_execute_tiles_block_scaled(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
+                                         const costa_scaled_op_t* ops, int64_t n_ops, const void* src_base,
+                                         void* dst_base, const void* scalars, int n_slots,
+                                         const costa_block_scales_t* a_scales,
+                                         const costa_block_scales_t* c_scales, int rounding, int64_t m,
+                                         int64_t n, int a_transposed, int device) {
+    return gpu_guarded([&] {
+        if (n_ops < 0 || (n_ops > 0 && (!ops || !scalars)))
+            throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::execute_tiles_block(src_dtype, dst_dtype, ops, n_ops, src_base, dst_base, scalars, n_slots,
+                                           a_scales, c_scales, rounding, m, n, a_transposed, device);
+    });
+}
+
+int costa_hip_block_items(int64_t* items, int reset) {
+    return guarded([&] {
+        if (!items) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        *items = costa::engine::block_items(reset != 0);
+    });
+}
+
+int costa_hip_block_check_ops(const costa_scaled_op_t* ops, int64_t n_ops, int block_rows, int block_cols,
+                              int64_t m, int64_t n) {
+    return guarded([&] {
+        if (n_ops < 0 || (n_ops > 0 && !ops)) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa_block_scales_t shape{};
+        shape.block_rows = block_rows;
+        shape.block_cols = block_cols;
+        shape.row_stride = shape.col_stride = 1;
+        costa::engine::check_block_scales(shape, 1, 1, "costa_hip_block_check_ops");  // (the block shape)
+        costa::engine::check_block_ops(std::vector<costa_scaled_op_t>(ops, ops + n_ops), block_rows, block_cols, m, n);
+    });
+}
+
+int costa_hip_block_check_scales(const costa_block_scales_t* desc, int64_t rows, int64_t cols) {
+    return guarded([&] {
+        if (!desc) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::check_block_scales(*desc, rows, cols, "costa_hip_block_check_scales");
+    });
+}
+
 int costa_hip_plan_export_scaled(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
                                  const void* beta, int rank, int nranks,
                                  costa_scaled_plan_info_t* info, costa_tile_op_t* pack_ops,

@@ -1843,6 +1843,12 @@ struct cached_plan {
     strip_list s_local;
     // the tile-boundary rule of MX calls per c_scales axis: 0 not checked yet, 1 holds, -1 fails
     int mx_rule[2] = {0, 0};
+    // block-scaled FP8 calls (block_kernels.hip): the 128 x 128 regions of the quantising kernel over the
+    // ops of d_local_sc (plans whose C holds FP8), and the tile-boundary rule per block shape of
+    // c_scales ((1,128), (128,1), (128,128)), kept as mx_rule
+    dbuf w_local_blk;
+    strip_list b_local;
+    int blk_rule[3] = {0, 0, 0};
     struct xround {  // one exchange round: its pack ops (by their first element) and unpack
                      // ops (by their last element)
         dbuf d_pack, w_pack, d_unpack, w_unpack;
@@ -1852,6 +1858,8 @@ struct cached_plan {
         strip_list t_unpack;
         dbuf d_unpack_sc, w_unpack_sc;
         strip_list s_unpack;
+        dbuf w_unpack_blk;  // (the regions of block-scaled calls over d_unpack_sc)
+        strip_list b_unpack;
         bool tr_unpack = false, ax_unpack = false;
     };
     std::vector<std::unique_ptr<xround>> rounds;
@@ -2275,13 +2283,19 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
     // a scaled plan's LOCAL list, its sub-tiles in destination-address order (COSTA_SCALED_ORDER=0,
     // tuning: list order; DESIGN 3h has both)
     std::vector<costa_scaled_op_t> ord_ls;
-    std::vector<uint64_t> w_ls;
+    std::vector<uint64_t> w_ls, w_lb;
+    // (a scaled plan into FP8 also serves block-scaled calls: the regions of its quantising kernel)
+    const bool blk_regions = block_pair(p.src_dtype, p.dtype) && dtype_is_fp8(p.dtype);
     if (!p.local_scaled.empty()) {
         static const bool by_dst = [] {
             const char* e = tuning_env("COSTA_SCALED_ORDER");
             return !e || std::atoi(e) != 0;
         }();
         cp->s_local = build_scaled_work(p.src_dtype, p.dtype, p.local_scaled, 0, 0, ord_ls, w_ls, by_dst);
+        if (blk_regions) {
+            std::vector<costa_scaled_op_t> same;  // (the ops of ord_ls)
+            cp->b_local = build_block_work(p.src_dtype, p.dtype, p.local_scaled, 0, 0, same, w_lb, by_dst);
+        }
     }
     // exchange rounds: pack ops go to the round of their first element (every element a round
     // sends is packed by then), unpack ops to the round of their last (every element they read
@@ -2302,7 +2316,7 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
         for (size_t i = 0; i < p.unpack_tri.size(); ++i) upt[size_t(tr[i])].push_back(p.unpack_tri[i]);
     }
     std::vector<std::vector<costa_scaled_op_t>> ups(static_cast<size_t>(R)), ord_us(static_cast<size_t>(R));
-    std::vector<std::vector<uint64_t>> w_us(static_cast<size_t>(R));
+    std::vector<std::vector<uint64_t>> w_us(static_cast<size_t>(R)), w_ub(static_cast<size_t>(R));
     if (!p.unpack_scaled.empty()) {
         std::vector<int> sr;
         exchange_round_of_scaled(p, R, sr);
@@ -2332,6 +2346,10 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
         if (!ups[size_t(r)].empty())  // (package offsets are relative to the 256-byte aligned buffer)
             x->s_unpack = build_scaled_work(p.pkg_dtype, p.dtype, ups[size_t(r)], 0, 0, ord_us[size_t(r)],
                                             w_us[size_t(r)], false);
+        if (!ups[size_t(r)].empty() && blk_regions) {
+            std::vector<costa_scaled_op_t> same;
+            x->b_unpack = build_block_work(p.pkg_dtype, p.dtype, ups[size_t(r)], 0, 0, same, w_ub[size_t(r)], false);
+        }
         cp->rounds.push_back(std::move(x));
     }
     t_work = now() - t0 - t_resid - t_plan;
@@ -2345,6 +2363,7 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
         cp->d_local_sc.upload(ord_ls, dc.main);
         cp->w_local_sc.upload(w_ls, dc.main);
     }
+    if (cp->b_local.n_items) cp->w_local_blk.upload(w_lb, dc.main);
     for (int r = 0; r < R; ++r) {
         auto& x = *cp->rounds[size_t(r)];
         const device_section& su = sec_u[size_t(r)];
@@ -2352,6 +2371,7 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
             x.d_unpack_sc.upload(ord_us[size_t(r)], dc.main);
             x.w_unpack_sc.upload(w_us[size_t(r)], dc.main);
         }
+        if (x.b_unpack.n_items) x.w_unpack_blk.upload(w_ub[size_t(r)], dc.main);
         x.d_pack.upload(ord_p[size_t(r)], dc.main);
         x.w_pack.upload(w_p[size_t(r)], dc.main);
         upload_list(x.d_unpack, ord_u[size_t(r)], su.d_ordered, su.at_ordered, su.n_ordered, dc.main);
@@ -2412,6 +2432,7 @@ double g_tri_ms = 0;
 int64_t g_scaled_items = 0;  // sub-tiles run by scaled_kernel (kept beside costa_stats_t)
 int64_t g_amax_items = 0;    // ... by its AMAX instantiations and by amax_kernel (likewise)
 int64_t g_mx_items = 0;      // ... by mx_kernel (likewise; not counted as scaled items)
+int64_t g_blk_items = 0;     // sub-tiles and regions run by block_kernel (likewise)
 
 struct phase_timer {
     device_ctx& dc;
@@ -2533,6 +2554,11 @@ struct scaled_args {
     bool mx = false;
     mx_side a_scales, c_scales;
     bool ceil = false;
+    // a block-scaled call (costa_hip_transform_block_scaled): the same ops on block_kernel
+    bool blk = false;
+    block_side a_blocks, c_blocks;
+    bool pow2 = false;
+    bool blk_quant() const { return blk && c_blocks.data; }
 };
 
 // the matrix a layout describes
@@ -2621,6 +2647,79 @@ void mx_args(const job& j, cached_plan& cp, scaled_args& sv) {
     sv.ceil = j.mx_rounding == COSTA_MX_CEIL;
 }
 
+// The argument checks of costa_hip_transform_block_scaled that need no plan and no device (as
+// check_mx_job): the pair, which descriptors it wants, the rounding mode, beta, shapes and strides.
+void check_block_job(const job& j) {
+    const std::string who = "costa_hip_transform_block_scaled: ";
+    const costa_dtype_t a = j.A->dtype, c = j.C->dtype;
+    const std::string pair = std::string(dtype_name(a)) + " -> " + dtype_name(c);
+    if (!block_pair(a, c))
+        throw error(COSTA_ERR_ARG, who + "no block-scaled transform for " + pair +
+                                       " (FLOAT -> FP8, FP8 -> FLOAT, FP8 -> the same FP8)");
+    if (j.uplo != 'A') throw error(COSTA_ERR_ARG, who + "no triangular mask");
+    if (j.A == j.C) throw error(COSTA_ERR_ARG, who + "in-place calls are not supported");
+    const bool want_a = dtype_is_fp8(a), want_c = dtype_is_fp8(c);
+    if (want_a && !j.a_blocks.data) throw error(COSTA_ERR_ARG, who + "a_scales is required for " + pair);
+    if (!want_a && j.a_blocks.data)
+        throw error(COSTA_ERR_ARG, who + "a_scales given for a FLOAT source (" + pair + ")");
+    if (want_c && !j.c_blocks.data) throw error(COSTA_ERR_ARG, who + "c_scales is required for " + pair);
+    if (!want_c && j.c_blocks.data)
+        throw error(COSTA_ERR_ARG, who + "c_scales given for a FLOAT destination (" + pair + ")");
+    if (j.blk_rounding != COSTA_BLOCK_EXACT && j.blk_rounding != COSTA_BLOCK_POW2)
+        throw error(COSTA_ERR_ARG, who + "rounding must be COSTA_BLOCK_EXACT or COSTA_BLOCK_POW2");
+    if (want_c) {
+        float beta;
+        std::memcpy(&beta, j.s.beta.data(), sizeof beta);
+        if (!(beta == 0.0f)) throw error(COSTA_ERR_ARG, who + "beta must be 0 with c_scales");
+    }
+    int64_t r, k;
+    if (want_a) {
+        layout_extent(*j.A, r, k);
+        check_block_scales(j.a_blocks, r, k, who + "a_scales");
+    }
+    if (want_c) {
+        layout_extent(*j.C, r, k);
+        check_block_scales(j.c_blocks, r, k, who + "c_scales");
+    }
+}
+
+// a descriptor as the kernel sees it, in target coordinates (`swap`: indexed by A's matrix of a
+// transposing job, whose rows are target columns)
+block_side block_side_of(const costa_block_scales_t& s, bool swap) {
+    block_side o;
+    o.data = s.data;
+    if (!s.data) return o;
+    o.row_stride = swap ? s.col_stride : s.row_stride;
+    o.col_stride = swap ? s.row_stride : s.col_stride;
+    o.row_shift = (swap ? s.block_cols : s.block_rows) == 128 ? 7 : 0;
+    o.col_shift = (swap ? s.block_rows : s.block_cols) == 128 ? 7 : 0;
+    return o;
+}
+
+// ... and those that need them: device residency and the tile-boundary rule (kept per plan and block
+// shape); fills sv
+void block_args(const job& j, cached_plan& cp, scaled_args& sv) {
+    for (const void* v : {static_cast<const void*>(j.a_blocks.data), static_cast<const void*>(j.c_blocks.data)})
+        if (v && !is_device_ptr(v))
+            throw error(COSTA_ERR_ARG, "costa_hip_transform_block_scaled: the scale tensors must be device-resident");
+    if (j.c_blocks.data) {
+        int& ok = cp.blk_rule[j.c_blocks.block_rows == 1 ? 0 : j.c_blocks.block_cols == 1 ? 1 : 2];
+        int64_t m, n;
+        layout_extent(*j.C, m, n);
+        if (ok <= 0) {  // (a failing plan is checked again: the error carries the op)
+            ok = -1;
+            check_block_ops(cp.p->local_scaled, j.c_blocks.block_rows, j.c_blocks.block_cols, m, n);
+            check_block_ops(cp.p->unpack_scaled, j.c_blocks.block_rows, j.c_blocks.block_cols, m, n);
+            ok = 1;
+        }
+    }
+    sv = scaled_args{};
+    sv.blk = true;
+    sv.a_blocks = block_side_of(j.a_blocks, std::toupper(static_cast<unsigned char>(j.trans)) != 'N');
+    sv.c_blocks = block_side_of(j.c_blocks, false);
+    sv.pow2 = j.blk_rounding == COSTA_BLOCK_POW2;
+}
+
 // The launch blocks of a transform: LOCAL, one round's PACK, one round's UNPACK.  transform() calls
 // them for an RCCL communicator (on the context's three streams, around issue_exchange) and for the
 // selected part of an emulated one (on main, against the caller's package).
@@ -2651,7 +2750,12 @@ void launch_local(const cached_plan& cp, const scaled_args& sv, phase_timer& tm,
 
     if (cp.s_local.n_items) {  // the LOCAL list of a scaled plan
         tm.start(PH_LOCAL, ls);
-        if (sv.mx)
+        if (sv.blk)
+            launch_block(p.src_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(cp.d_local_sc.p),
+                         static_cast<const uint64_t*>(sv.blk_quant() ? cp.w_local_blk.p : cp.w_local_sc.p),
+                         sv.blk_quant() ? cp.b_local : cp.s_local, nullptr, nullptr, cp.d_scal.p, sv.a_blocks,
+                         sv.c_blocks, sv.pow2, ls);
+        else if (sv.mx)
             launch_mx(p.src_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(cp.d_local_sc.p),
                       static_cast<const uint64_t*>(cp.w_local_sc.p), cp.s_local, nullptr, nullptr,
                       cp.d_scal.p, sv.a_scales, sv.c_scales, sv.ceil, ls);
@@ -2717,7 +2821,12 @@ void launch_unpack_round(const cached_plan& cp, const cached_plan::xround& x, co
     if (x.s_unpack.n_items) {  // the round's unpack list of a scaled plan
         if (moved) HIP_CHECK(hipStreamWaitEvent(s, moved, 0));
         tm.start(PH_UNPACK, s);
-        if (sv.mx)
+        if (sv.blk)
+            launch_block(p.pkg_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(x.d_unpack_sc.p),
+                         static_cast<const uint64_t*>(sv.blk_quant() ? x.w_unpack_blk.p : x.w_unpack_sc.p),
+                         sv.blk_quant() ? x.b_unpack : x.s_unpack, rb, nullptr, cp.d_scal.p, sv.a_blocks,
+                         sv.c_blocks, sv.pow2, s);
+        else if (sv.mx)
             launch_mx(p.pkg_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(x.d_unpack_sc.p),
                       static_cast<const uint64_t*>(x.w_unpack_sc.p), x.s_unpack, rb, nullptr,
                       cp.d_scal.p, sv.a_scales, sv.c_scales, sv.ceil, s);
@@ -2739,10 +2848,13 @@ void count_items(const plan& p, const work_split& w) {
         g_stats.fused_pieces += w.n_tiny;
 }
 
-void count_local(const cached_plan& cp, bool amax, bool mx) {
+void count_local(const cached_plan& cp, bool amax, bool mx, int blk = 0) {
     const plan& p = *cp.p;
     g_stats.tri_items += cp.t_local.n_items;
-    (mx ? g_mx_items : g_scaled_items) += cp.s_local.n_items;
+    if (blk)
+        g_blk_items += blk == 2 ? cp.b_local.n_items : cp.s_local.n_items;
+    else
+        (mx ? g_mx_items : g_scaled_items) += cp.s_local.n_items;
     if (amax) g_amax_items += cp.s_local.n_items;
     if (cp.l_local.n_items() || cp.c_local.n_items || cp.t_local.n_items || cp.s_local.n_items) {
         g_stats.local_launches++;
@@ -2758,11 +2870,14 @@ void count_pack_round(const cached_plan& cp, const cached_plan::xround& x) {
     g_stats.convert_items += x.c_pack.n_items;
 }
 
-void count_unpack_round(const cached_plan& cp, const cached_plan::xround& x, bool amax, bool mx) {
+void count_unpack_round(const cached_plan& cp, const cached_plan::xround& x, bool amax, bool mx, int blk = 0) {
     g_stats.unpack_launches +=
         x.l_unpack.n_items() || x.c_unpack.n_items || x.t_unpack.n_items || x.s_unpack.n_items ? 1 : 0;
     g_stats.tri_items += x.t_unpack.n_items;
-    (mx ? g_mx_items : g_scaled_items) += x.s_unpack.n_items;
+    if (blk)
+        g_blk_items += blk == 2 ? x.b_unpack.n_items : x.s_unpack.n_items;
+    else
+        (mx ? g_mx_items : g_scaled_items) += x.s_unpack.n_items;
     if (amax) g_amax_items += x.s_unpack.n_items;
     count_items(*cp.p, x.l_unpack);
     g_stats.convert_items += x.c_unpack.n_items;
@@ -2792,7 +2907,7 @@ void run_emulated_part(const comm* c, device_ctx& dc, const cached_plan& cp, con
     const int r0 = c->round < 0 ? 0 : c->round, r1 = c->round < 0 ? R : c->round + 1;
     if (c->part == COSTA_EMULATE_LOCAL) {
         launch_local(cp, sv, tm, dc.main);
-        count_local(cp, sv.amax(), sv.mx);
+        count_local(cp, sv.amax(), sv.mx, sv.blk ? 1 + sv.blk_quant() : 0);
         g_stats.transforms++;
     } else if (c->part == COSTA_EMULATE_PACK) {
         if (!buffer_holds(c->buffer, size_t(p.send_elems) * E))
@@ -2808,7 +2923,7 @@ void run_emulated_part(const comm* c, device_ctx& dc, const cached_plan& cp, con
         for (int r = r0; r < r1; ++r) {
             launch_unpack_round(cp, *cp.rounds[size_t(r)], static_cast<const char*>(c->buffer), sv, tm,
                                 dc.main, nullptr);
-            count_unpack_round(cp, *cp.rounds[size_t(r)], sv.amax(), sv.mx);
+            count_unpack_round(cp, *cp.rounds[size_t(r)], sv.amax(), sv.mx, sv.blk ? 1 + sv.blk_quant() : 0);
         }
         if (r1 == R) g_stats.unpack_bytes += p.unpack_bytes;
     }
@@ -2839,6 +2954,8 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
         check_jobs(jobs, c->size, a, b);
     }
     if (mx) check_mx_job(jobs[0]);  // pair, descriptors, beta, strides: before the plan
+    const bool blk = !jobs.empty() && jobs[0].blk;
+    if (blk) check_block_job(jobs[0]);
     cached_plan& cp = *get_plan(jobs, c, dc);
     const plan& p = *cp.p;
     const size_t E = pkg_unit_size(p.pkg_dtype);  // of the send / receive packages
@@ -2854,7 +2971,9 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
     sv.col_scale = col_scale;
     sv.row_amax = row_amax;
     sv.col_amax = col_amax;
-    if (mx) {
+    if (blk) {
+        block_args(jobs[0], cp, sv);
+    } else if (mx) {
         mx_args(jobs[0], cp, sv);
     } else if (p.scaled) {
         if (!row_scale && !col_scale && !amax)
@@ -2960,11 +3079,11 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
     }
 
     g_stats.transforms++;
-    count_local(cp, amax, sv.mx);
+    count_local(cp, amax, sv.mx, sv.blk ? 1 + sv.blk_quant() : 0);
     if (exchange) {
         for (const auto& x : cp.rounds) {
             count_pack_round(cp, *x);
-            count_unpack_round(cp, *x, amax, sv.mx);
+            count_unpack_round(cp, *x, amax, sv.mx, sv.blk ? 1 + sv.blk_quant() : 0);
         }
         g_stats.pack_bytes += p.pack_bytes;
         g_stats.unpack_bytes += p.unpack_bytes;
@@ -3365,6 +3484,103 @@ int64_t mx_items(bool reset) {
     std::lock_guard<std::recursive_mutex> lk(g_mutex);
     const int64_t v = g_mx_items;
     if (reset) g_mx_items = 0;
+    return v;
+}
+
+// ---------------------------------------------------------------- block-scaled FP8 transforms
+void check_block_scales(const costa_block_scales_t& s, int64_t rows, int64_t cols, const std::string& what) {
+    const bool shape_ok = (s.block_rows == 1 && s.block_cols == 128) || (s.block_rows == 128 && s.block_cols == 1) ||
+                          (s.block_rows == 128 && s.block_cols == 128);
+    if (!shape_ok)
+        throw error(COSTA_ERR_ARG, what + ": the block shape must be (1, 128), (128, 1) or (128, 128), not (" +
+                                       std::to_string(s.block_rows) + ", " + std::to_string(s.block_cols) + ")");
+    if (reinterpret_cast<uintptr_t>(s.data) % 4 != 0) throw error(COSTA_ERR_ARG, what + ": data must be 4-byte aligned");
+    if (s.row_stride <= 0 || s.col_stride <= 0) throw error(COSTA_ERR_ARG, what + ": the strides must be positive");
+    const int64_t nbr = (rows + s.block_rows - 1) / s.block_rows, nbc = (cols + s.block_cols - 1) / s.block_cols;
+    // (as check_mx_scales: the smallest coincidence of two positive strides is dr = cs / g, dc = rs / g)
+    if (nbr > 1 && nbc > 1) {
+        const int64_t g = std::gcd(s.row_stride, s.col_stride);
+        if (s.col_stride / g < nbr && s.row_stride / g < nbc)
+            throw error(COSTA_ERR_ARG, what + ": the strides make two blocks share a float");
+    }
+}
+
+void check_block_ops(const std::vector<costa_scaled_op_t>& ops, int block_rows, int block_cols, int64_t m,
+                     int64_t n) {
+    for (const costa_scaled_op_t& t : ops) {
+        if (t.op.nf <= 0 || t.op.ns <= 0) continue;
+        const bool frow = t.op.flags & COSTA_SCALED_F_ROWS;
+        for (int rows = 1; rows >= 0; --rows) {
+            const int64_t b = rows ? block_rows : block_cols;
+            const int64_t at = rows ? t.row0 : t.col0, len = rows == int(frow) ? t.op.nf : t.op.ns;
+            const int64_t edge = rows ? m : n;
+            if (at % b != 0 || (len % b != 0 && at + len != edge) || at + len > edge)
+                throw error(COSTA_ERR_ARG,
+                            "costa: a tile boundary splits a scale block of C: a tile covers " +
+                                std::string(rows ? "rows " : "columns ") + std::to_string(at) + " .. " +
+                                std::to_string(at + len) + " of " + std::to_string(edge) +
+                                " (block sizes and split points of both layouts must be multiples of " +
+                                std::to_string(b) + " along " + (rows ? "rows" : "columns") + ")");
+        }
+    }
+}
+
+void execute_tiles_block(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* ops,
+                         int64_t n_ops, const void* src_base, void* dst_base, const void* scalars, int n_slots,
+                         const costa_block_scales_t* a_scales, const costa_block_scales_t* c_scales,
+                         int rounding, int64_t m, int64_t n, int a_transposed, int device) {
+    std::lock_guard<std::recursive_mutex> lk(g_mutex);
+    const std::string who = "costa_hip_execute_tiles_block_scaled";
+    if (!block_pair(src_dtype, dst_dtype))
+        throw error(COSTA_ERR_ARG, who + ": no block-scaled kernel for " + dtype_name(src_dtype) + " -> " +
+                                       dtype_name(dst_dtype));
+    const costa_block_scales_t none{};
+    const costa_block_scales_t& sa = a_scales && a_scales->data ? *a_scales : none;
+    const costa_block_scales_t& sc = c_scales && c_scales->data ? *c_scales : none;
+    if ((sa.data != nullptr) != (src_dtype != COSTA_FLOAT) || (sc.data != nullptr) != (dst_dtype != COSTA_FLOAT))
+        throw error(COSTA_ERR_ARG, who + ": a scale tensor is needed exactly on the FP8 sides of " +
+                                       dtype_name(src_dtype) + " -> " + dtype_name(dst_dtype));
+    if (rounding != COSTA_BLOCK_EXACT && rounding != COSTA_BLOCK_POW2)
+        throw error(COSTA_ERR_ARG, who + ": rounding must be COSTA_BLOCK_EXACT or COSTA_BLOCK_POW2");
+    if (m < 0 || n < 0) throw error(COSTA_ERR_ARG, who + ": negative matrix extent");
+    if (sa.data) check_block_scales(sa, a_transposed ? n : m, a_transposed ? m : n, who + ": a_scales");
+    std::vector<costa_scaled_op_t> v(ops, ops + n_ops);
+    for (const costa_scaled_op_t& t : v) {
+        if (t.op.nf <= 0 || t.op.ns <= 0) continue;
+        if (t.row0 < 0 || t.col0 < 0) throw error(COSTA_ERR_ARG, who + ": negative target coordinate");
+        const bool frow = t.op.flags & COSTA_SCALED_F_ROWS;
+        if (t.row0 + int64_t(frow ? t.op.nf : t.op.ns) > m || t.col0 + int64_t(frow ? t.op.ns : t.op.nf) > n)
+            throw error(COSTA_ERR_ARG, who + ": an op reaches past the m x n matrix");
+    }
+    if (sc.data) {
+        check_block_scales(sc, m, n, who + ": c_scales");
+        for (const costa_scaled_op_t& t : v)
+            if (((t.op.flags & COSTA_SCALE_MASK) >> COSTA_SCALE_SHIFT) == COSTA_SCALE_AXPBY)
+                throw error(COSTA_ERR_ARG, who + ": beta must be 0 with c_scales (an op of kind AXPBY)");
+        check_block_ops(v, sc.block_rows, sc.block_cols, m, n);
+    }
+    ctx(device);  // (is_device_ptr needs the device's context)
+    for (const void* p : {static_cast<const void*>(sa.data), static_cast<const void*>(sc.data)})
+        if (p && !is_device_ptr(p)) throw error(COSTA_ERR_ARG, who + ": the scale tensors must be device-resident");
+    const block_side da = block_side_of(sa, a_transposed != 0), dc_ = block_side_of(sc, false);
+    const uintptr_t sb = reinterpret_cast<uintptr_t>(src_base), db = reinterpret_cast<uintptr_t>(dst_base);
+    const bool quant = sc.data != nullptr;
+    g_blk_items += run_strip_tiles(
+        who, v.data(), n_ops, scalars, n_slots, sizeof(float), device,
+        [&](const auto& l, auto& ord, auto& w) {
+            return quant ? build_block_work(src_dtype, dst_dtype, l, sb, db, ord, w, false)
+                         : build_scaled_work(src_dtype, dst_dtype, l, sb, db, ord, w, false);
+        },
+        [&](const costa_scaled_op_t* d_ops, const uint64_t* d_work, const strip_list& l, const void* d_scal, void* s) {
+            launch_block(src_dtype, dst_dtype, d_ops, d_work, l, static_cast<const char*>(src_base),
+                         static_cast<char*>(dst_base), d_scal, da, dc_, rounding == COSTA_BLOCK_POW2, s);
+        });
+}
+
+int64_t block_items(bool reset) {
+    std::lock_guard<std::recursive_mutex> lk(g_mutex);
+    const int64_t v = g_blk_items;
+    if (reset) g_blk_items = 0;
     return v;
 }
 

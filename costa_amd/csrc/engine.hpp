@@ -122,6 +122,12 @@ struct job {
     costa_mx_scales_t a_scales{};
     costa_mx_scales_t c_scales{};
     int mx_rounding = 0;
+    // block-scaled FP8 transforms (costa_hip_transform_block_scaled): likewise a scaled job, its lists
+    // on block_kernel
+    bool blk = false;
+    costa_block_scales_t a_blocks{};
+    costa_block_scales_t c_blocks{};
+    int blk_rounding = 0;
 };
 
 // The three tile-op lists of one rank plus the exchange geometry.  Addresses of pack
@@ -420,6 +426,44 @@ void execute_tiles_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const co
                       int64_t m, int64_t n, int a_transposed, int device);
 // sub-tiles run by mx_kernel since the last reset
 int64_t mx_items(bool reset);
+// ---- block-scaled FP8 transforms (block_kernels.hip; costa_hip.h, "Block-scaled FP8 transforms") ----
+// block_kernel<Es, Ed, QUANT> on the scaled ops of a scaled plan: dequantising lists run the plan's
+// 64 x 64 work items (build_scaled_work), quantising ones 128 x 128 regions (build_block_work, whose
+// `ordered` equals build_scaled_work's: the same ops, order and VEC flags).  A scale tensor as the
+// kernel sees it, in TARGET coordinates (A's descriptor has rows and columns swapped when the job
+// transposes): the float of target (i, j) at data[(i >> row_shift) * row_stride + (j >> col_shift) *
+// col_stride], a shift 0 or 7.  data == nullptr: none.
+struct block_side {
+    void* data = nullptr;
+    int64_t row_stride = 0, col_stride = 0;
+    int32_t row_shift = 0, col_shift = 0;
+};
+// FLOAT -> Q (quantise), Q -> FLOAT (dequantise), Q -> Q of one Q (requantise); Q an FP8 type
+bool block_pair(costa_dtype_t src, costa_dtype_t dst);
+strip_list build_block_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
+                            const std::vector<costa_scaled_op_t>& ops, uint64_t src_base, uint64_t dst_base,
+                            std::vector<costa_scaled_op_t>& ordered, std::vector<uint64_t>& work, bool dst_order);
+// a scale tensor on exactly the FP8 sides of the pair; `d_work` / `l`: regions when c_scales is
+// given, sub-tiles otherwise; `pow2`: COSTA_BLOCK_POW2
+void launch_block(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* d_ops,
+                  const uint64_t* d_work, const strip_list& l, const char* src_base, char* dst_base,
+                  const void* d_scalars, const block_side& a_scales, const block_side& c_scales, bool pow2,
+                  void* stream /* hipStream_t */);
+// a descriptor's block shape is (1, 128), (128, 1) or (128, 128), data is 4-byte aligned, the strides
+// are positive and no two blocks of a rows x cols matrix share a float (throws COSTA_ERR_ARG naming
+// `what`); host only
+void check_block_scales(const costa_block_scales_t& s, int64_t rows, int64_t cols, const std::string& what);
+// the tile-boundary rule: every op starts at a multiple of the block shape in C's coordinates and
+// spans a multiple of it or ends at the edge of C's m x n matrix (throws COSTA_ERR_ARG, "scale block")
+void check_block_ops(const std::vector<costa_scaled_op_t>& ops, int block_rows, int block_cols, int64_t m,
+                     int64_t n);
+// costa_hip_execute_tiles_block_scaled: as execute_tiles_mx
+void execute_tiles_block(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* ops,
+                         int64_t n_ops, const void* src_base, void* dst_base, const void* scalars, int n_slots,
+                         const costa_block_scales_t* a_scales, const costa_block_scales_t* c_scales,
+                         int rounding, int64_t m, int64_t n, int a_transposed, int device);
+// work items (sub-tiles and regions) run by block_kernel since the last reset
+int64_t block_items(bool reset);
 // ... of every scaled unpack op (plan::unpack_scaled), by the rule of exchange_round_of_ops
 void exchange_round_of_scaled(const struct plan& p, int rounds, std::vector<int>& unpack_round);
 

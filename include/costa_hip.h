@@ -639,6 +639,84 @@ int costa_hip_mx_check_scales(const costa_mx_scales_t* s, int64_t rows, int64_t 
  * Not covered: NVFP4, bf16 / fp16 sides, host-resident packed layouts, batches, masks, in-place
  * calls, extents off the grid of 4 (2 for FP4), swizzled scales, FP6 <-> FP4 / FP8 requantise. */
 
+/* ---- Block-scaled FP8 transforms (fp32 scales) (MI355X-native): 1 x 128 / 128 x 128 blocks, fused ----
+ * FP8 data with one fp32 scale per 1 x 128 group of a row, 128 x 1 group of a column or 128 x 128
+ * tile ("blockwise" / DeepSeek-style scaling), produced or consumed in the pass that redistributes
+ * or transposes.
+ *
+ * Scale tensor.  A DEVICE array of fp32 described by costa_block_scales_t.  Block (bi, bj) covers rows
+ * bi*block_rows .. and columns bj*block_cols .. of the layout's matrix; its scale is
+ * ((float*)data)[bi*row_stride + bj*col_stride] (strides count floats).  The block shapes are (1, 128),
+ * (128, 1) and (128, 128); any other is COSTA_ERR_ARG.  The last block along either dimension may be
+ * partial and reduces over the elements that exist.  Both strides must be positive, no two blocks of
+ * the matrix may share a float, data must be 4-byte aligned.  As in the MX calls, a_scales is indexed by
+ * A's matrix as stored (before trans), c_scales by C's matrix.
+ *
+ * Arithmetic (bit-exact).  w() / cvt() are the FP8 codecs, g() the ZERO / ALPHA / AXPBY arithmetic in
+ * fp32 with contraction off.  Per element x = w(a), times SA[block of a] when A is FP8 (one rounded
+ * fp32 product); v = g(x, w(c_old)).
+ *   dequantise (no c_scales): store v.
+ *   quantise / requantise, per block of C: amax = the unsigned maximum of the bit patterns of |v|.  If
+ *     its exponent field is 255 (an inf or a NaN in the block) S = NaN (0x7FC00000) and every
+ *     q = cvt(NaN).  Otherwise amax_c = max(amax, 2^-40) (bits 0x2B800000), so S and R are finite and
+ *     normal; an all-zero block stores zeros and S = 2^-40 / fmax.
+ *       COSTA_BLOCK_EXACT: S = amax_c / fmax, R = fmax / amax_c, two correctly rounded fp32 divisions
+ *         per block.
+ *       COSTA_BLOCK_POW2: E = the MX CEIL rule applied to amax_c; S = 2^(E-127), R = 2^(127-E), exact.
+ *     q = cvt(clamp(v * R, -fmax, +fmax)) (one rounded product per element; under EXACT amax * R may
+ *     round above fmax, so the clamp matters); SC[block] = S.  fmax is 448 (e4m3) / 57344 (e5m2).
+ *
+ * Accepted calls (everything else is COSTA_ERR_ARG naming what was wrong, C and the tensors untouched):
+ *   quantise    COSTA_FLOAT -> FP8      c_scales           beta = 0
+ *   dequantise  FP8 -> COSTA_FLOAT      a_scales           alpha, beta free
+ *   requantise  FP8 -> the same FP8     both (shapes may differ)   beta = 0
+ * FP8 is COSTA_FP8_E4M3 or COSTA_FP8_E5M2.  Refused: every other pair ("no block-scaled transform",
+ * naming both types), a missing or superfluous descriptor, an unknown rounding value, a triangular
+ * mask, an in-place call, a host-resident layout or tensor.
+ *
+ * Tile-boundary rule.  A block of C must not be split between tiles: every split point of both
+ * layouts (A's seen through trans) must be a multiple of c_scales.block_rows along rows and of
+ * c_scales.block_cols along columns (an extent of 1 holds trivially).  A violation is COSTA_ERR_ARG
+ * containing "scale block" and the offending interval, raised before anything is written.  a_scales
+ * imposes no rule: any layout pair dequantises.
+ *
+ * Several ranks: as for MX.  The exchange is the ordinary scaled plan of the FP8 pair (fp32 -> Q sends
+ * fp32 and quantises in UNPACK; Q -> .. sends Q bytes); only LOCAL and UNPACK touch scale tensors.  A
+ * rank writes only the scales of blocks it owns in C (zero the tensor and merge with all_reduce(MAX));
+ * it needs the a_scales of every block it reads -- the library moves no scales.
+ *
+ * Not covered: bf16 / fp16 sides, other block sizes, packed types, batches, masks, in-place calls, host
+ * staging, swizzled scales, the C++ overloads and ScaLAPACK shims. */
+#define COSTA_BLOCK_EXACT 0
+#define COSTA_BLOCK_POW2 1
+typedef struct {
+    void* data;                     /* device array of fp32 */
+    int32_t block_rows, block_cols; /* (1, 128), (128, 1) or (128, 128) */
+    int64_t row_stride, col_stride; /* floats between vertically / horizontally adjacent blocks */
+} costa_block_scales_t; /* 32 bytes */
+int costa_hip_transform_block_scaled(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                                     const void* beta, const costa_block_scales_t* a_scales,
+                                     const costa_block_scales_t* c_scales, int rounding, costa_comm_t comm);
+int costa_hip_transform_block_scaled_async(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                                           const void* beta, const costa_block_scales_t* a_scales,
+                                           const costa_block_scales_t* c_scales, int rounding,
+                                           costa_comm_t comm, void* stream);
+/* ops as for costa_hip_execute_tiles_mx: m x n is C's matrix, a_transposed: A's matrix is n x m and
+ * a_scales is indexed by it; with c_scales the ops obey the tile-boundary rule and have beta = 0 */
+int costa_hip_execute_tiles_block_scaled(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
+                                         const costa_scaled_op_t* ops, int64_t n_ops, const void* src_base,
+                                         void* dst_base, const void* scalars, int n_slots,
+                                         const costa_block_scales_t* a_scales,
+                                         const costa_block_scales_t* c_scales, int rounding, int64_t m,
+                                         int64_t n, int a_transposed, int device);
+/* work items run by the block-scaled kernels since the last reset: 64 x 64 sub-tiles of dequantising
+ * lists, 128 x 128 regions of quantising ones */
+int costa_hip_block_items(int64_t* items, int reset);
+/* host only: the tile-boundary rule on caller-given ops / the checks of a descriptor */
+int costa_hip_block_check_ops(const costa_scaled_op_t* ops, int64_t n_ops, int block_rows, int block_cols,
+                              int64_t m, int64_t n);
+int costa_hip_block_check_scales(const costa_block_scales_t* desc, int64_t rows, int64_t cols);
+
 /* ---- stream-ordered variants (MI355X-native; no reference counterpart) ----
  * Enqueue the transform and return.  Layouts must be device-resident.  `stream` (a hipStream_t,
  * may be NULL) is joined at entry and made to wait for the result, so work queued on it after
