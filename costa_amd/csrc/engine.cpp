@@ -347,44 +347,41 @@ size_t peer_of(const std::vector<int64_t>& displs, int64_t o) {
 }
 }  // namespace
 
+namespace {
+// The one round-assignment rule: the round of the op at byte `offset` of the send (pack) or receive
+// (unpack) package that covers `units` package units.  A pack op goes by its first unit (everything a
+// round sends is packed by then), an unpack op by its last (everything it reads has arrived); an op
+// lies inside one peer's package.  (tools/work_check.cpp rounds)
+int round_of_op(const plan& p, int rounds, bool unpack, uint64_t offset, int64_t units) {
+    const size_t E = pkg_unit_size(p.pkg_dtype);  // package offsets are in package elements (units)
+    const std::vector<int64_t>& displs = unpack ? p.recv_displs : p.send_displs;
+    const std::vector<int64_t>& counts = unpack ? p.recv_counts : p.send_counts;
+    const int64_t first = int64_t(offset / E);
+    const size_t q = peer_of(displs, first);
+    return round_of((unpack ? first + units - 1 : first) - displs[q], counts[q], E, rounds);
+}
+}  // namespace
+
 void exchange_round_of_ops(const plan& p, int rounds, std::vector<int>& pack_round,
                            std::vector<int>& unpack_round) {
-    const size_t E = pkg_unit_size(p.pkg_dtype);  // package offsets are in package elements (units)
     pack_round.clear();
     unpack_round.clear();
-    for (const auto& op : p.pack_ops) {
-        const int64_t o = int64_t(op.dst / E);
-        const size_t q = peer_of(p.send_displs, o);
-        pack_round.push_back(round_of(o - p.send_displs[q], p.send_counts[q], E, rounds));
-    }
-    for (const auto& op : p.unpack_ops) {
-        const int64_t first = int64_t(op.src / E);
-        const int64_t last = first + int64_t(op.nf) * op.ns - 1;
-        const size_t q = peer_of(p.recv_displs, first);
-        unpack_round.push_back(round_of(last - p.recv_displs[q], p.recv_counts[q], E, rounds));
-    }
+    for (const auto& op : p.pack_ops) pack_round.push_back(round_of_op(p, rounds, false, op.dst, 1));
+    for (const auto& op : p.unpack_ops)
+        unpack_round.push_back(round_of_op(p, rounds, true, op.src, int64_t(op.nf) * op.ns));
 }
 
 void exchange_round_of_tri(const plan& p, int rounds, std::vector<int>& unpack_tri_round) {
-    const size_t E = pkg_unit_size(p.pkg_dtype);
     unpack_tri_round.clear();
-    for (const auto& t : p.unpack_tri) {  // by its last element, like every unpack op
-        const int64_t first = int64_t(t.op.src / E);
-        const int64_t last = first + int64_t(t.op.nf) * t.op.ns - 1;
-        const size_t q = peer_of(p.recv_displs, first);
-        unpack_tri_round.push_back(round_of(last - p.recv_displs[q], p.recv_counts[q], E, rounds));
-    }
+    for (const auto& t : p.unpack_tri)
+        unpack_tri_round.push_back(round_of_op(p, rounds, true, t.op.src, int64_t(t.op.nf) * t.op.ns));
 }
 
 void exchange_round_of_scaled(const plan& p, int rounds, std::vector<int>& unpack_round) {
-    const size_t E = pkg_unit_size(p.pkg_dtype);
     unpack_round.clear();
-    for (const auto& t : p.unpack_scaled) {  // by its last element, like every unpack op
-        const int64_t first = int64_t(t.op.src / E);
-        const int64_t last = first + pkg_units(p.pkg_dtype, int64_t(t.op.nf) * t.op.ns) - 1;
-        const size_t q = peer_of(p.recv_displs, first);
-        unpack_round.push_back(round_of(last - p.recv_displs[q], p.recv_counts[q], E, rounds));
-    }
+    for (const auto& t : p.unpack_scaled)  // (of a packed package: the bytes of its nf x ns elements)
+        unpack_round.push_back(
+            round_of_op(p, rounds, true, t.op.src, pkg_units(p.pkg_dtype, int64_t(t.op.nf) * t.op.ns)));
 }
 
 int comm_rank(const comm* c) { return c->rank; }
@@ -1821,6 +1818,39 @@ void set_layout_hash(elayout& L) { layout_hashes(L, L.hash, L.hash2); }
 
 namespace {
 
+// an uploaded op list with its work list
+struct dev_list {
+    dbuf ops, work;
+    template <typename Op>
+    const Op* list() const { return static_cast<const Op*>(ops.p); }
+    const uint64_t* items() const { return static_cast<const uint64_t*>(work.p); }
+};
+
+// What one phase of a plan launches (LOCAL, one exchange round's PACK, one round's UNPACK), in launch
+// order.  build_phase fills it, upload_phase brings the lists to the device, launch_phase runs them
+// and count_phase keeps the statistics: a new list kind is a member here and a step in those four.
+struct phase_lists {
+    // the ordinary ops: tile_kernel lists (`split`: how the work list divides over the kernel shapes), or
+    // the converting family's (`convert`) where the phase changes the element type -- LOCAL of a mixed
+    // plan, PACK of a narrowing pair, UNPACK of a widening one; at most one of the two is non-empty
+    dev_list tiles;
+    work_split split;
+    strip_list convert;
+    bool transposes = false, reads_c = false;  // any op of `tiles` transposes / reads C
+    // edge tiles of a triangular plan (tri_kernels.hip)
+    dev_list tri;
+    strip_list tri_items;
+    // the ops of a scaled plan (scaled_kernels.hip, mx_kernels.hip, block_kernels.hip by the call's scheme)
+    dev_list scaled;
+    strip_list scaled_items;
+    // the 128 x 128 regions of block_kernel's quantising form over scaled.ops (plans whose C holds FP8)
+    dbuf block_work;
+    strip_list block_items;
+    bool empty() const {
+        return !split.n_items() && !convert.n_items && !tri_items.n_items && !scaled_items.n_items;
+    }
+};
+
 struct cached_plan {
     std::unique_ptr<plan> p;
     int device = 0;
@@ -1828,39 +1858,15 @@ struct cached_plan {
     bool staged = false;
     std::vector<hrange> h2d_ranges, d2h_ranges;  // uploaded / copied back
     dbuf stage;
-    // device copies of the op lists and work lists
-    dbuf d_local, w_local, d_scal;
-    work_split l_local;                     // how the work list splits over the kernel shapes
-    bool tr_local = true, ax_local = true;  // any op of the list transposes / reads C
-    // converting lists of a mixed-precision plan (convert_kernels.hip) have a strip_list instead
-    // of a work_split: LOCAL; PACK of a narrowing pair; UNPACK of a widening pair
-    strip_list c_local;
-    // edge tiles of a triangular plan (tri_kernels.hip): LOCAL, and UNPACK per exchange round
-    dbuf d_local_tri, w_local_tri;
-    strip_list t_local;
-    // the lists of a scaled plan (scaled_kernels.hip): LOCAL, and UNPACK per exchange round
-    dbuf d_local_sc, w_local_sc;
-    strip_list s_local;
+    phase_lists local;  // LOCAL
+    dbuf d_scal;
     // the tile-boundary rule of MX calls per c_scales axis: 0 not checked yet, 1 holds, -1 fails
     int mx_rule[2] = {0, 0};
-    // block-scaled FP8 calls (block_kernels.hip): the 128 x 128 regions of the quantising kernel over the
-    // ops of d_local_sc (plans whose C holds FP8), and the tile-boundary rule per block shape of
-    // c_scales ((1,128), (128,1), (128,128)), kept as mx_rule
-    dbuf w_local_blk;
-    strip_list b_local;
+    // ... and of block-scaled FP8 calls per block shape of c_scales ((1,128), (128,1), (128,128))
     int blk_rule[3] = {0, 0, 0};
     struct xround {  // one exchange round: its pack ops (by their first element) and unpack
                      // ops (by their last element)
-        dbuf d_pack, w_pack, d_unpack, w_unpack;
-        work_split l_pack, l_unpack;
-        strip_list c_pack, c_unpack;
-        dbuf d_unpack_tri, w_unpack_tri;
-        strip_list t_unpack;
-        dbuf d_unpack_sc, w_unpack_sc;
-        strip_list s_unpack;
-        dbuf w_unpack_blk;  // (the regions of block-scaled calls over d_unpack_sc)
-        strip_list b_unpack;
-        bool tr_unpack = false, ax_unpack = false;
+        phase_lists pack, unpack;
     };
     std::vector<std::unique_ptr<xround>> rounds;
     std::vector<unsigned char> scal_host;
@@ -2037,7 +2043,150 @@ std::unique_ptr<plan> plan_jobs(const std::vector<job>& jobs, comm* c, hipStream
 costa_dtype_t pack_src(const plan& p) { return dtype_is_packed(p.src_dtype) ? COSTA_FP8_E4M3 : p.src_dtype; }
 costa_dtype_t pack_dst(const plan& p) { return dtype_is_packed(p.pkg_dtype) ? COSTA_FP8_E4M3 : p.pkg_dtype; }
 
-cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
+// the element types a phase reads and writes (its tile_kernel, edge-tile and same-type lists run on dst)
+struct dtype_pair {
+    costa_dtype_t src, dst;
+};
+dtype_pair phase_dtypes(const plan& p, list_kind kind) {
+    if (kind == list_pack) return {pack_src(p), pack_dst(p)};
+    return {kind == list_unpack ? p.pkg_dtype : p.src_dtype, p.dtype};
+}
+
+// The kernels a phase's ordinary ops run on.
+// (a mixed plan's LOCAL list converts; its package holds the narrower type, so PACK converts
+// for narrowing pairs and UNPACK for widening ones, the other being a same-type list; every
+// list of a half-precision plan runs on the converting family, its same-type H -> H lists too)
+// (an FP8 plan's package holds A's type: PACK is a byte copy on the FP8 family when A holds Q and
+// an ordinary FLOAT list when A is FLOAT; UNPACK always runs on the FP8 family, Q -> Q included)
+// (an FP4 / FP6 plan is a scaled plan, its ordinary LOCAL and UNPACK lists are empty; PACK is a byte
+// copy on the FP8 family when A holds the packed type -- pack_src / pack_dst -- and a FLOAT list
+// when A is FLOAT)
+enum class tiles_on { none, tile_kernel, converting };
+tiles_on phase_tiles(const plan& p, list_kind kind) {
+    bool cv;
+    if (kind == list_pack)
+        cv = p.half() || (p.packed() ? dtype_is_packed(p.src_dtype)
+                          : p.fp8()  ? dtype_is_fp8(p.src_dtype)
+                                     : p.mixed() && p.pkg_dtype != p.src_dtype);
+    else if (p.packed())
+        return tiles_on::none;
+    else if (kind == list_local)
+        cv = p.converting();
+    else
+        cv = p.half() || p.fp8() || (p.mixed() && p.pkg_dtype != p.dtype);
+    return cv ? tiles_on::converting : tiles_on::tile_kernel;
+}
+
+// a phase's lists in host memory, between build_phase and upload_phase (`into`: where they go)
+struct host_lists {
+    phase_lists* into;
+    std::vector<costa_tile_op_t> tiles;
+    std::vector<costa_tri_op_t> tri;
+    std::vector<costa_scaled_op_t> scaled;
+    std::vector<uint64_t> tiles_work, tri_work, scaled_work, block_work;
+    // the destination-block groups of long lists are built on the GPU and stay there
+    device_section sec;
+    host_lists(phase_lists& ph, int device, hipStream_t s) : into(&ph) {
+        sec.device = device;
+        sec.stream = s;
+    }
+};
+
+// One phase's lists from its ops (package offsets are relative to the 256-byte aligned send / receive
+// buffers): the counts and flags into *h.into, the lists into h.
+void build_phase(const plan& p, list_kind kind, bool masked, const std::vector<costa_tile_op_t>& tiles,
+                 const std::vector<costa_tri_op_t>& tri, const std::vector<costa_scaled_op_t>& scaled,
+                 host_lists& h) {
+    phase_lists& ph = *h.into;
+    const dtype_pair t = phase_dtypes(p, kind);
+    // (a pack list is launched as one that neither transposes nor reads C)
+    ph.transposes = kind != list_pack && any_transpose(tiles);
+    ph.reads_c = kind != list_pack && any_axpby(tiles);
+    switch (phase_tiles(p, kind)) {
+    case tiles_on::converting:
+        ph.convert = build_convert_work(t.src, t.dst, tiles, 0, 0, h.tiles, h.tiles_work);
+        break;
+    case tiles_on::tile_kernel:
+        // The wholly kept tiles of a triangular plan merge into row bands of unequal widths, one
+        // sub-tile tall: in list order consecutive workgroups walk along a band, a sub-tile's
+        // columns apart, and a copy list ran at 3.8 TB/s against 6.7 for the full rectangle;
+        // in destination-address order 6.2 (16384^2 fp64 'N', DESIGN 3e).
+        ph.split = build_work(t.dst, tiles, h.tiles, h.tiles_work, kind, kind == list_pack ? nullptr : &h.sec,
+                              kind == list_local && masked);
+        break;
+    case tiles_on::none:
+        break;
+    }
+    if (!tri.empty()) ph.tri_items = build_tri_work(t.dst, tri, 0, 0, h.tri, h.tri_work);
+    if (scaled.empty()) return;
+    // a scaled plan's LOCAL list, its sub-tiles in destination-address order (COSTA_SCALED_ORDER=0,
+    // tuning: list order; DESIGN 3h has both)
+    static const bool local_by_dst = [] {
+        const char* e = tuning_env("COSTA_SCALED_ORDER");
+        return !e || std::atoi(e) != 0;
+    }();
+    const bool by_dst = kind == list_local && local_by_dst;
+    ph.scaled_items = build_scaled_work(t.src, t.dst, scaled, 0, 0, h.scaled, h.scaled_work, by_dst);
+    // (a scaled plan into FP8 also serves block-scaled calls: the regions of its quantising kernel)
+    if (block_pair(p.src_dtype, p.dtype) && dtype_is_fp8(p.dtype)) {
+        std::vector<costa_scaled_op_t> same;  // (the ops of h.scaled)
+        ph.block_items = build_block_work(t.src, t.dst, scaled, 0, 0, same, h.block_work, by_dst);
+    }
+}
+
+void upload_phase(const host_lists& h, hipStream_t s) {
+    phase_lists& ph = *h.into;
+    upload_list(ph.tiles.ops, h.tiles, h.sec.d_ordered, h.sec.at_ordered, h.sec.n_ordered, s);
+    upload_list(ph.tiles.work, h.tiles_work, h.sec.d_work, h.sec.at_work, h.sec.n_work, s);
+    if (ph.tri_items.n_items) {
+        ph.tri.ops.upload(h.tri, s);
+        ph.tri.work.upload(h.tri_work, s);
+    }
+    if (ph.scaled_items.n_items) {
+        ph.scaled.ops.upload(h.scaled, s);
+        ph.scaled.work.upload(h.scaled_work, s);
+    }
+    if (ph.block_items.n_items) ph.block_work.upload(h.block_work, s);
+}
+
+// the ops of each of R exchange rounds, in list order
+template <typename Op>
+std::vector<std::vector<Op>> by_round(const std::vector<Op>& ops, const std::vector<int>& round, int R) {
+    std::vector<std::vector<Op>> out(static_cast<size_t>(R));
+    for (size_t i = 0; i < ops.size(); ++i) out[size_t(round[i])].push_back(ops[i]);
+    return out;
+}
+
+// Every phase of cp's plan: LOCAL, and PACK and UNPACK of each exchange round.  Pack ops go to the
+// round of their first element (every element a round sends is packed by then), unpack ops to the
+// round of their last (every element they read has arrived).
+std::vector<host_lists> build_lists(cached_plan& cp, comm* c, hipStream_t s, bool masked) {
+    const plan& p = *cp.p;
+    if (p.packed() && (!p.local_ops.empty() || !p.unpack_ops.empty()))
+        throw error(COSTA_ERR_INTERNAL, "costa: an FP4 / FP6 plan with ordinary LOCAL / UNPACK ops");
+    const int R = c->exchanges() ? exchange_rounds() : 1;
+    std::vector<int> pr, ur, tr, sr;
+    exchange_round_of_ops(p, R, pr, ur);
+    exchange_round_of_tri(p, R, tr);
+    exchange_round_of_scaled(p, R, sr);
+    const auto pack = by_round(p.pack_ops, pr, R), unpack = by_round(p.unpack_ops, ur, R);
+    const auto unpack_tri = by_round(p.unpack_tri, tr, R);
+    const auto unpack_scaled = by_round(p.unpack_scaled, sr, R);
+    std::vector<host_lists> h;
+    h.reserve(1 + 2 * size_t(R));
+    h.emplace_back(cp.local, cp.device, s);
+    build_phase(p, list_local, masked, p.local_ops, p.local_tri, p.local_scaled, h.back());
+    for (size_t r = 0; r < size_t(R); ++r) {
+        cp.rounds.push_back(std::make_unique<cached_plan::xround>());
+        h.emplace_back(cp.rounds.back()->pack, cp.device, s);
+        build_phase(p, list_pack, false, pack[r], {}, {}, h.back());
+        h.emplace_back(cp.rounds.back()->unpack, cp.device, s);
+        build_phase(p, list_unpack, false, unpack[r], unpack_tri[r], unpack_scaled[r], h.back());
+    }
+    return h;
+}
+
+std::vector<uint64_t> plan_key(const std::vector<job>& jobs, const comm* c) {
     std::vector<uint64_t> key;
     key.reserve(4 + jobs.size() * 30);
     key.push_back(uint64_t(uint32_t(c->rank)) | uint64_t(uint32_t(c->size)) << 32);
@@ -2057,6 +2206,213 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
         key.push_back(uint64_t(uint8_t(std::toupper(static_cast<unsigned char>(j.uplo)))) << 32 |
                       uint64_t(j.scaled) << 40 | uint64_t(uint32_t(j.k)));
     }
+    return key;
+}
+
+double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+
+// why a batch takes device-resident layouts only, or nullptr
+const char* device_only(const std::vector<job>& jobs) {
+    const bool packed = any_packed(jobs);
+    if (packed && (dtype_is_fp6(jobs[0].A->dtype) || dtype_is_fp6(jobs[0].C->dtype)))
+        return "costa: FP6 transforms (A or C of a packed 6-bit element type) need "
+               "device-resident layouts";
+    if (packed)
+        return "costa: FP4 transforms (A or C of the packed 4-bit element type) need "
+               "device-resident layouts";
+    if (any_fp8(jobs))  // 1-byte element types: treated like mixed pairs here
+        return "costa: FP8 transforms (A or C of a 1-byte element type) need "
+               "device-resident layouts";
+    if (any_half(jobs))  // 2-byte element types: the same
+        return "costa: half-precision transforms (A or C of a 2-byte element type) need "
+               "device-resident layouts";
+    if (any_mixed(jobs))
+        return "costa: mixed-precision transforms (A and C of different element types) need "
+               "device-resident layouts";
+    if (any_scaled(jobs)) return "costa: scaled transforms need device-resident layouts";
+    return nullptr;
+}
+
+// the host-resident layouts of a batch, staged in cp.stage: the jobs on their device copies
+struct staging {
+    std::vector<job> jobs;
+    std::vector<elayout> remapped;
+    std::vector<hrange> ranges;
+    // per merged range: holds A data (bit 0), C data (bit 1), C blocks of more than one
+    // job (bit 2); C ranges are copied back, A ranges and C ranges the kernels do not
+    // overwrite completely are uploaded (decided once the ops are known: staged_copies)
+    std::vector<uint8_t> flags;
+};
+
+// Residency: all device, or stage the host-resident layouts (cp.staged, cp.stage, st).  -> true when
+// the batch takes the pipelined scheme instead (host_pipe.cpp): cp is then complete.
+bool stage_host_layouts(const std::vector<job>& jobs, comm* c, device_ctx& dc, bool masked, cached_plan& cp,
+                        staging& st) {
+    bool all_dev = true;
+    std::vector<bool> on_dev;
+    for (const auto& j : jobs)
+        for (const elayout* L : {j.A, j.C}) {
+            bool d = layout_on_device(*L);
+            on_dev.push_back(d);
+            all_dev = all_dev && d;
+        }
+    st.jobs = jobs;
+    if (all_dev) return false;
+    if (const char* why = device_only(jobs)) throw error(COSTA_ERR_ARG, why);
+    cp.staged = true;
+    std::vector<const elayout*> As, Cs;
+    size_t k = 0;
+    for (const auto& j : jobs) {
+        if (!on_dev[k++]) As.push_back(j.A);
+        if (!on_dev[k++]) Cs.push_back(j.C);
+    }
+    std::vector<const elayout*> all = As;
+    all.insert(all.end(), Cs.begin(), Cs.end());
+    auto ranges = collect_ranges(all);
+    size_t off = 0;
+    for (auto& r : ranges) {
+        r.dev_off = off;
+        off += ((r.hi - r.lo) + 255) & ~size_t(255);
+    }
+    st.flags.assign(ranges.size(), 0);
+    std::vector<int> c_job(ranges.size(), -1);
+    auto range_of = [&](uintptr_t p) {
+        auto it = std::upper_bound(ranges.begin(), ranges.end(), p,
+                                   [](uintptr_t v, const hrange& r) { return v < r.lo; });
+        return size_t(it - ranges.begin()) - 1;
+    };
+    k = 0;
+    for (size_t t = 0; t < jobs.size(); ++t) {
+        const bool a_host = !on_dev[k++], c_host = !on_dev[k++];
+        for (int side = 0; side < 2; ++side) {
+            if (!(side == 0 ? a_host : c_host)) continue;
+            const elayout* L = side == 0 ? jobs[t].A : jobs[t].C;
+            const size_t E = dtype_size(L->dtype);
+            for (const auto& b : L->blocks) {
+                if (!block_extent_bytes(b, L->ordering, E)) continue;
+                const size_t i = range_of(reinterpret_cast<uintptr_t>(b.data));
+                if (side == 0) {
+                    st.flags[i] |= 1;
+                } else {
+                    st.flags[i] |= 2;
+                    if (c_job[i] >= 0 && c_job[i] != int(t)) st.flags[i] |= 4;
+                    c_job[i] = int(t);
+                }
+            }
+        }
+    }
+    // Pipelined staging (host_pipe.cpp) when every layout is host-resident, no range holds
+    // both source and target data (in-place) and no target range is shared by two jobs
+    // (their updates would have to be applied in order).
+    // (triangular transforms always take the mirror scheme)
+    bool pipe_ok = host_staging_mode() == 1 && !masked &&
+                   std::none_of(on_dev.begin(), on_dev.end(), [](bool d) { return d; });
+    for (uint8_t f : st.flags)
+        if ((f & 3) == 3 || (f & 4)) pipe_ok = false;
+    if (pipe_ok) {
+        const double tp = now_ms();
+        auto hplan = plan_jobs(jobs, c, dc.main);  // host addresses
+        g_stats.plan_ms += now_ms() - tp;
+        if (host_pipeline_accepts(hplan->dtype, hplan->pack_ops)) {
+            cp.staged = false;
+            cp.p = std::move(hplan);
+            const int R = c->exchanges() ? exchange_rounds() : 1;
+            std::vector<int> pr, ur;
+            exchange_round_of_ops(*cp.p, R, pr, ur);
+            cp.pipe = make_host_pipeline(cp.p->dtype, cp.p->pack_ops, cp.p->local_ops,
+                                         cp.p->unpack_ops, pr, ur, R);
+            return true;
+        }
+    }
+    cp.stage.reserve(std::max<size_t>(off, 256));
+    st.remapped.reserve(jobs.size() * 2);
+    k = 0;
+    for (auto& j : st.jobs) {
+        if (!on_dev[k++]) {
+            st.remapped.push_back(remap(*j.A, ranges, static_cast<char*>(cp.stage.p)));
+            j.A = &st.remapped.back();
+        }
+        if (!on_dev[k++]) {
+            st.remapped.push_back(remap(*j.C, ranges, static_cast<char*>(cp.stage.p)));
+            j.C = &st.remapped.back();
+        }
+    }
+    st.ranges = std::move(ranges);
+    return false;
+}
+
+// The copies of a staged plan: C ranges come back (d2h_ranges); A ranges go up, and C ranges unless
+// the kernels overwrite every byte of them (h2d_ranges): one job's C blocks only, no op reading C
+// (beta = 0), and the ops' writes (disjoint: each C element is written once per job) add up to the
+// whole range.
+void staged_copies(cached_plan& cp, const staging& st, bool masked) {
+    const plan& p = *cp.p;
+    const size_t E = dtype_size(p.dtype);
+    const uintptr_t base = reinterpret_cast<uintptr_t>(cp.stage.p);
+    std::vector<size_t> written(st.ranges.size(), 0);
+    std::vector<bool> reads_c(st.ranges.size(), false);
+    auto account = [&](const std::vector<costa_tile_op_t>& ops) {
+        for (const auto& op : ops) {
+            if (op.dst < base) continue;  // device-resident destination
+            const size_t off = size_t(op.dst - base);
+            auto it = std::upper_bound(st.ranges.begin(), st.ranges.end(), off,
+                                       [](size_t v, const hrange& r) { return v < r.dev_off; });
+            if (it == st.ranges.begin()) continue;
+            const size_t i = size_t(it - st.ranges.begin()) - 1;
+            if (off >= st.ranges[i].dev_off + (st.ranges[i].hi - st.ranges[i].lo)) continue;
+            written[i] += size_t(op.nf) * size_t(op.ns) * E;
+            if (((op.flags & COSTA_SCALE_MASK) >> COSTA_SCALE_SHIFT) == COSTA_SCALE_AXPBY)
+                reads_c[i] = true;
+        }
+    };
+    account(p.local_ops);
+    account(p.unpack_ops);
+    for (size_t i = 0; i < st.ranges.size(); ++i) {
+        const hrange& r = st.ranges[i];
+        const uint8_t f = st.flags[i];
+        // (a masked plan never overwrites a range completely: dropped elements keep their bytes)
+        const bool overwritten = !masked && f == 2 && !reads_c[i] && written[i] == r.hi - r.lo;
+        if ((f & 1) || ((f & 2) && !overwritten)) cp.h2d_ranges.push_back(r);
+        if (f & 2) cp.d2h_ranges.push_back(r);
+    }
+}
+
+// a plan-cache miss: residency, the plan, its lists, their upload
+std::unique_ptr<cached_plan> build_cached_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
+    // COSTA_PLAN_TRACE=1: where a plan-cache miss spends its host time (stderr)
+    static const bool trace = std::getenv("COSTA_PLAN_TRACE") != nullptr;
+    const double t0 = now_ms();
+    const bool masked = any_masked(jobs);
+    if (masked || device_only(jobs)) {  // an unsupported pair is reported as such, whatever the residency
+        costa_dtype_t a, b;
+        check_jobs(jobs, c->size, a, b);
+    }
+    auto cp = std::make_unique<cached_plan>();
+    cp->device = c->device;
+    staging st;
+    if (stage_host_layouts(jobs, c, dc, masked, *cp, st)) return cp;
+    const double t_resid = now_ms() - t0;
+    cp->p = plan_jobs(st.jobs, c, dc.main);
+    const double t_plan = now_ms() - t0 - t_resid;
+    g_stats.plan_ms += t_plan;
+    if (cp->staged) staged_copies(*cp, st, masked);
+    const std::vector<host_lists> lists = build_lists(*cp, c, dc.main, masked);
+    const double t_work = now_ms() - t0 - t_resid - t_plan;
+    for (const host_lists& h : lists) upload_phase(h, dc.main);
+    HIP_CHECK(hipStreamSynchronize(dc.main));  // the host lists are temporaries
+    if (trace)
+        std::fprintf(stderr,
+                     "[costa plan] %zu local / %zu pack / %zu unpack ops: residency %.2f ms, "
+                     "planning %.2f, work lists %.2f, upload %.2f, total %.2f\n",
+                     cp->p->local_ops.size(), cp->p->pack_ops.size(), cp->p->unpack_ops.size(), t_resid, t_plan,
+                     t_work, now_ms() - t0 - t_resid - t_plan - t_work, now_ms() - t0);
+    return cp;
+}
+
+cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
+    std::vector<uint64_t> key = plan_key(jobs, c);
     hasher h;
     for (uint64_t w : key) h.mix(w);
     for (auto it = g_plans.begin(); it != g_plans.end(); ++it) {
@@ -2067,328 +2423,7 @@ cached_plan* get_plan(const std::vector<job>& jobs, comm* c, device_ctx& dc) {
         }
     }
     g_stats.plan_misses++;
-    // COSTA_PLAN_TRACE=1: where a plan-cache miss spends its host time (stderr)
-    static const bool trace = std::getenv("COSTA_PLAN_TRACE") != nullptr;
-    auto now = [] {
-        return std::chrono::duration<double, std::milli>(
-                   std::chrono::steady_clock::now().time_since_epoch()).count();
-    };
-    const double t0 = now();
-    double t_resid = 0, t_plan = 0, t_work = 0;
-
-    const bool half = any_half(jobs);  // 2-byte element types: treated like mixed pairs here
-    const bool fp8 = any_fp8(jobs);    // 1-byte element types: the same
-    const bool packed = any_packed(jobs);  // the packed 4-bit and 6-bit types: the same
-    const bool fp6 = packed && (dtype_is_fp6(jobs[0].A->dtype) || dtype_is_fp6(jobs[0].C->dtype));
-    const bool mixed = any_mixed(jobs) || half || fp8 || packed;
-    const bool masked = any_masked(jobs);
-    const bool scaled = any_scaled(jobs);
-    if (mixed || masked || scaled) {  // an unsupported pair is reported as such, whatever the residency
-        costa_dtype_t a, b;
-        check_jobs(jobs, c->size, a, b);
-    }
-    auto cp = std::make_unique<cached_plan>();
-    cp->device = c->device;
-    // residency: all device, or stage the host-resident layouts
-    bool all_dev = true;
-    std::vector<const elayout*> host_layouts;
-    std::vector<bool> on_dev;
-    for (const auto& j : jobs)
-        for (const elayout* L : {j.A, j.C}) {
-            bool d = layout_on_device(*L);
-            on_dev.push_back(d);
-            all_dev = all_dev && d;
-        }
-    std::vector<elayout> remapped;
-    std::vector<job> pj = jobs;
-    std::vector<hrange> staged_ranges;
-    std::vector<uint8_t> range_flags;
-    if (!all_dev && mixed)
-        throw error(COSTA_ERR_ARG,
-                    fp6  ? "costa: FP6 transforms (A or C of a packed 6-bit element type) need "
-                           "device-resident layouts"
-                    : packed ? "costa: FP4 transforms (A or C of the packed 4-bit element type) need "
-                           "device-resident layouts"
-                    : fp8 ? "costa: FP8 transforms (A or C of a 1-byte element type) need "
-                           "device-resident layouts"
-                    : half ? "costa: half-precision transforms (A or C of a 2-byte element type) need "
-                           "device-resident layouts"
-                         : "costa: mixed-precision transforms (A and C of different element types) need "
-                           "device-resident layouts");
-    if (!all_dev && scaled)
-        throw error(COSTA_ERR_ARG, "costa: scaled transforms need device-resident layouts");
-    if (!all_dev) {
-        cp->staged = true;
-        std::vector<const elayout*> As, Cs;
-        size_t k = 0;
-        for (const auto& j : jobs) {
-            if (!on_dev[k++]) As.push_back(j.A);
-            if (!on_dev[k++]) Cs.push_back(j.C);
-        }
-        std::vector<const elayout*> all = As;
-        all.insert(all.end(), Cs.begin(), Cs.end());
-        auto ranges = collect_ranges(all);
-        size_t off = 0;
-        for (auto& r : ranges) {
-            r.dev_off = off;
-            off += ((r.hi - r.lo) + 255) & ~size_t(255);
-        }
-        // per merged range: holds A data (bit 0), C data (bit 1), C blocks of more than one
-        // job (bit 2); C ranges are copied back, A ranges and C ranges the kernels do not
-        // overwrite completely are uploaded (decided once the ops are known, below)
-        range_flags.assign(ranges.size(), 0);
-        std::vector<int> c_job(ranges.size(), -1);
-        auto range_of = [&](uintptr_t p) {
-            auto it = std::upper_bound(ranges.begin(), ranges.end(), p,
-                                       [](uintptr_t v, const hrange& r) { return v < r.lo; });
-            return size_t(it - ranges.begin()) - 1;
-        };
-        k = 0;
-        for (size_t t = 0; t < jobs.size(); ++t) {
-            const bool a_host = !on_dev[k++], c_host = !on_dev[k++];
-            for (int side = 0; side < 2; ++side) {
-                if (!(side == 0 ? a_host : c_host)) continue;
-                const elayout* L = side == 0 ? jobs[t].A : jobs[t].C;
-                const size_t E = dtype_size(L->dtype);
-                for (const auto& b : L->blocks) {
-                    if (!block_extent_bytes(b, L->ordering, E)) continue;
-                    const size_t i = range_of(reinterpret_cast<uintptr_t>(b.data));
-                    if (side == 0) {
-                        range_flags[i] |= 1;
-                    } else {
-                        range_flags[i] |= 2;
-                        if (c_job[i] >= 0 && c_job[i] != int(t)) range_flags[i] |= 4;
-                        c_job[i] = int(t);
-                    }
-                }
-            }
-        }
-        // Pipelined staging (host_pipe.cpp) when every layout is host-resident, no range holds
-        // both source and target data (in-place) and no target range is shared by two jobs
-        // (their updates would have to be applied in order).
-        // (triangular transforms always take the mirror scheme)
-        bool pipe_ok = host_staging_mode() == 1 && !masked &&
-                       std::none_of(on_dev.begin(), on_dev.end(), [](bool d) { return d; });
-        for (uint8_t f : range_flags)
-            if ((f & 3) == 3 || (f & 4)) pipe_ok = false;
-        if (pipe_ok) {
-            const double tp = now();
-            auto hplan = plan_jobs(jobs, c, dc.main);  // host addresses
-            g_stats.plan_ms += now() - tp;
-            if (host_pipeline_accepts(hplan->dtype, hplan->pack_ops)) {
-                cp->staged = false;
-                cp->p = std::move(hplan);
-                const int R = c->exchanges() ? exchange_rounds() : 1;
-                std::vector<int> pr, ur;
-                exchange_round_of_ops(*cp->p, R, pr, ur);
-                cp->pipe = make_host_pipeline(cp->p->dtype, cp->p->pack_ops, cp->p->local_ops,
-                                              cp->p->unpack_ops, pr, ur, R);
-                g_plans.push_front({h.h, std::move(key), std::move(cp)});
-                while (g_plans.size() > kMaxPlans) g_plans.pop_back();
-                return g_plans.front().plan.get();
-            }
-        }
-        cp->stage.reserve(std::max<size_t>(off, 256));
-        staged_ranges = ranges;
-        remapped.reserve(jobs.size() * 2);
-        k = 0;
-        for (auto& j : pj) {
-            if (!on_dev[k++]) {
-                remapped.push_back(remap(*j.A, ranges, static_cast<char*>(cp->stage.p)));
-                j.A = &remapped.back();
-            }
-            if (!on_dev[k++]) {
-                remapped.push_back(remap(*j.C, ranges, static_cast<char*>(cp->stage.p)));
-                j.C = &remapped.back();
-            }
-        }
-    }
-    t_resid = now() - t0;
-    cp->p = plan_jobs(pj, c, dc.main);
-    const plan& p = *cp->p;
-    t_plan = now() - t0 - t_resid;
-    g_stats.plan_ms += t_plan;
-    if (cp->staged) {
-        // A C-only range needs no upload when the kernels overwrite every byte of it: one job's
-        // C blocks only, no op reading C (beta = 0), and the ops' writes (disjoint: each C
-        // element is written once per job) add up to the whole range.
-        const size_t E = dtype_size(p.dtype);
-        const uintptr_t base = reinterpret_cast<uintptr_t>(cp->stage.p);
-        std::vector<size_t> written(staged_ranges.size(), 0);
-        std::vector<bool> reads_c(staged_ranges.size(), false);
-        auto account = [&](const std::vector<costa_tile_op_t>& ops) {
-            for (const auto& op : ops) {
-                if (op.dst < base) continue;  // device-resident destination
-                const size_t off = size_t(op.dst - base);
-                auto it = std::upper_bound(staged_ranges.begin(), staged_ranges.end(), off,
-                                           [](size_t v, const hrange& r) { return v < r.dev_off; });
-                if (it == staged_ranges.begin()) continue;
-                const size_t i = size_t(it - staged_ranges.begin()) - 1;
-                if (off >= staged_ranges[i].dev_off + (staged_ranges[i].hi - staged_ranges[i].lo))
-                    continue;
-                written[i] += size_t(op.nf) * size_t(op.ns) * E;
-                if (((op.flags & COSTA_SCALE_MASK) >> COSTA_SCALE_SHIFT) == COSTA_SCALE_AXPBY)
-                    reads_c[i] = true;
-            }
-        };
-        account(p.local_ops);
-        account(p.unpack_ops);
-        for (size_t i = 0; i < staged_ranges.size(); ++i) {
-            const hrange& r = staged_ranges[i];
-            const uint8_t f = range_flags[i];
-            // (a masked plan never overwrites a range completely: dropped elements keep their bytes)
-            const bool overwritten = !masked && f == 2 && !reads_c[i] && written[i] == r.hi - r.lo;
-            if ((f & 1) || ((f & 2) && !overwritten)) cp->h2d_ranges.push_back(r);
-            if (f & 2) cp->d2h_ranges.push_back(r);
-        }
-    }
-    cp->tr_local = any_transpose(p.local_ops);
-    cp->ax_local = any_axpby(p.local_ops);
-    std::vector<costa_tile_op_t> ord_l;
-    std::vector<uint64_t> w_l;
-    // the destination-block groups of long lists are built on the GPU and stay there (sec_*)
-    auto section = [&] {
-        device_section d;
-        d.device = c->device;
-        d.stream = dc.main;
-        return d;
-    };
-    device_section sec_l = section();
-    // (a mixed plan's LOCAL list converts; its package holds the narrower type, so PACK converts
-    // for narrowing pairs and UNPACK for widening ones, the other being a same-type list; every
-    // list of a half-precision plan runs on the converting family, its same-type H -> H lists too)
-    // (an FP8 plan's package holds A's type: PACK is a byte copy on the FP8 family when A holds Q and
-    // an ordinary FLOAT list when A is FLOAT; UNPACK always runs on the FP8 family, Q -> Q included)
-    // (an FP4 / FP6 plan is a scaled plan, its ordinary LOCAL and UNPACK lists are empty; PACK is a byte
-    // copy on the FP8 family when A holds the packed type -- pack_src / pack_dst -- and a FLOAT list
-    // when A is FLOAT)
-    const bool cv_pack = p.half() || (p.packed() ? dtype_is_packed(p.src_dtype)
-                                      : p.fp8() ? dtype_is_fp8(p.src_dtype)
-                                                : p.mixed() && p.pkg_dtype != p.src_dtype);
-    const bool cv_unpack = !p.packed() && (p.half() || p.fp8() || (p.mixed() && p.pkg_dtype != p.dtype));
-    if (p.packed()) {
-        if (!p.local_ops.empty() || !p.unpack_ops.empty())
-            throw error(COSTA_ERR_INTERNAL, "costa: an FP4 / FP6 plan with ordinary LOCAL / UNPACK ops");
-    } else if (p.converting())
-        cp->c_local = build_convert_work(p.src_dtype, p.dtype, p.local_ops, 0, 0, ord_l, w_l);
-    else
-        // The wholly kept tiles of a triangular plan merge into row bands of unequal widths, one
-        // sub-tile tall: in list order consecutive workgroups walk along a band, a sub-tile's
-        // columns apart, and a copy list ran at 3.8 TB/s against 6.7 for the full rectangle;
-        // in destination-address order 6.2 (16384^2 fp64 'N', DESIGN 3e).
-        cp->l_local = build_work(p.dtype, p.local_ops, ord_l, w_l, list_local, &sec_l, masked);
-    std::vector<costa_tri_op_t> ord_lt;
-    std::vector<uint64_t> w_lt;
-    if (!p.local_tri.empty()) cp->t_local = build_tri_work(p.dtype, p.local_tri, 0, 0, ord_lt, w_lt);
-    // a scaled plan's LOCAL list, its sub-tiles in destination-address order (COSTA_SCALED_ORDER=0,
-    // tuning: list order; DESIGN 3h has both)
-    std::vector<costa_scaled_op_t> ord_ls;
-    std::vector<uint64_t> w_ls, w_lb;
-    // (a scaled plan into FP8 also serves block-scaled calls: the regions of its quantising kernel)
-    const bool blk_regions = block_pair(p.src_dtype, p.dtype) && dtype_is_fp8(p.dtype);
-    if (!p.local_scaled.empty()) {
-        static const bool by_dst = [] {
-            const char* e = tuning_env("COSTA_SCALED_ORDER");
-            return !e || std::atoi(e) != 0;
-        }();
-        cp->s_local = build_scaled_work(p.src_dtype, p.dtype, p.local_scaled, 0, 0, ord_ls, w_ls, by_dst);
-        if (blk_regions) {
-            std::vector<costa_scaled_op_t> same;  // (the ops of ord_ls)
-            cp->b_local = build_block_work(p.src_dtype, p.dtype, p.local_scaled, 0, 0, same, w_lb, by_dst);
-        }
-    }
-    // exchange rounds: pack ops go to the round of their first element (every element a round
-    // sends is packed by then), unpack ops to the round of their last (every element they read
-    // has arrived)
-    const int R = c->exchanges() ? exchange_rounds() : 1;
-    std::vector<std::vector<costa_tile_op_t>> pk(static_cast<size_t>(R)), up(static_cast<size_t>(R));
-    {
-        std::vector<int> pr, ur;
-        exchange_round_of_ops(p, R, pr, ur);
-        for (size_t i = 0; i < p.pack_ops.size(); ++i) pk[size_t(pr[i])].push_back(p.pack_ops[i]);
-        for (size_t i = 0; i < p.unpack_ops.size(); ++i) up[size_t(ur[i])].push_back(p.unpack_ops[i]);
-    }
-    std::vector<std::vector<costa_tri_op_t>> upt(static_cast<size_t>(R)), ord_ut(static_cast<size_t>(R));
-    std::vector<std::vector<uint64_t>> w_ut(static_cast<size_t>(R));
-    if (!p.unpack_tri.empty()) {
-        std::vector<int> tr;
-        exchange_round_of_tri(p, R, tr);
-        for (size_t i = 0; i < p.unpack_tri.size(); ++i) upt[size_t(tr[i])].push_back(p.unpack_tri[i]);
-    }
-    std::vector<std::vector<costa_scaled_op_t>> ups(static_cast<size_t>(R)), ord_us(static_cast<size_t>(R));
-    std::vector<std::vector<uint64_t>> w_us(static_cast<size_t>(R)), w_ub(static_cast<size_t>(R));
-    if (!p.unpack_scaled.empty()) {
-        std::vector<int> sr;
-        exchange_round_of_scaled(p, R, sr);
-        for (size_t i = 0; i < p.unpack_scaled.size(); ++i) ups[size_t(sr[i])].push_back(p.unpack_scaled[i]);
-    }
-    std::vector<std::vector<costa_tile_op_t>> ord_p(static_cast<size_t>(R)), ord_u(static_cast<size_t>(R));
-    std::vector<std::vector<uint64_t>> w_p(static_cast<size_t>(R)), w_u(static_cast<size_t>(R));
-    std::vector<device_section> sec_u(static_cast<size_t>(R), section());
-    for (int r = 0; r < R; ++r) {
-        auto x = std::make_unique<cached_plan::xround>();
-        x->tr_unpack = any_transpose(up[size_t(r)]);
-        x->ax_unpack = any_axpby(up[size_t(r)]);
-        // (package offsets are relative to the 256-byte aligned send / receive buffers)
-        if (cv_pack)
-            x->c_pack = build_convert_work(pack_src(p), pack_dst(p), pk[size_t(r)], 0, 0, ord_p[size_t(r)],
-                                           w_p[size_t(r)]);
-        else
-            x->l_pack = build_work(p.pkg_dtype, pk[size_t(r)], ord_p[size_t(r)], w_p[size_t(r)], list_pack);
-        if (cv_unpack)
-            x->c_unpack = build_convert_work(p.pkg_dtype, p.dtype, up[size_t(r)], 0, 0, ord_u[size_t(r)],
-                                             w_u[size_t(r)]);
-        else if (!p.packed())  // (an FP4 / FP6 plan has no ordinary UNPACK list)
-            x->l_unpack = build_work(p.dtype, up[size_t(r)], ord_u[size_t(r)], w_u[size_t(r)], list_unpack,
-                                     &sec_u[size_t(r)]);
-        if (!upt[size_t(r)].empty())
-            x->t_unpack = build_tri_work(p.dtype, upt[size_t(r)], 0, 0, ord_ut[size_t(r)], w_ut[size_t(r)]);
-        if (!ups[size_t(r)].empty())  // (package offsets are relative to the 256-byte aligned buffer)
-            x->s_unpack = build_scaled_work(p.pkg_dtype, p.dtype, ups[size_t(r)], 0, 0, ord_us[size_t(r)],
-                                            w_us[size_t(r)], false);
-        if (!ups[size_t(r)].empty() && blk_regions) {
-            std::vector<costa_scaled_op_t> same;
-            x->b_unpack = build_block_work(p.pkg_dtype, p.dtype, ups[size_t(r)], 0, 0, same, w_ub[size_t(r)], false);
-        }
-        cp->rounds.push_back(std::move(x));
-    }
-    t_work = now() - t0 - t_resid - t_plan;
-    upload_list(cp->d_local, ord_l, sec_l.d_ordered, sec_l.at_ordered, sec_l.n_ordered, dc.main);
-    upload_list(cp->w_local, w_l, sec_l.d_work, sec_l.at_work, sec_l.n_work, dc.main);
-    if (cp->t_local.n_items) {
-        cp->d_local_tri.upload(ord_lt, dc.main);
-        cp->w_local_tri.upload(w_lt, dc.main);
-    }
-    if (cp->s_local.n_items) {
-        cp->d_local_sc.upload(ord_ls, dc.main);
-        cp->w_local_sc.upload(w_ls, dc.main);
-    }
-    if (cp->b_local.n_items) cp->w_local_blk.upload(w_lb, dc.main);
-    for (int r = 0; r < R; ++r) {
-        auto& x = *cp->rounds[size_t(r)];
-        const device_section& su = sec_u[size_t(r)];
-        if (x.s_unpack.n_items) {
-            x.d_unpack_sc.upload(ord_us[size_t(r)], dc.main);
-            x.w_unpack_sc.upload(w_us[size_t(r)], dc.main);
-        }
-        if (x.b_unpack.n_items) x.w_unpack_blk.upload(w_ub[size_t(r)], dc.main);
-        x.d_pack.upload(ord_p[size_t(r)], dc.main);
-        x.w_pack.upload(w_p[size_t(r)], dc.main);
-        upload_list(x.d_unpack, ord_u[size_t(r)], su.d_ordered, su.at_ordered, su.n_ordered, dc.main);
-        upload_list(x.w_unpack, w_u[size_t(r)], su.d_work, su.at_work, su.n_work, dc.main);
-        if (x.t_unpack.n_items) {
-            x.d_unpack_tri.upload(ord_ut[size_t(r)], dc.main);
-            x.w_unpack_tri.upload(w_ut[size_t(r)], dc.main);
-        }
-    }
-    HIP_CHECK(hipStreamSynchronize(dc.main));  // host vectors above are temporaries
-    if (trace)
-        std::fprintf(stderr,
-                     "[costa plan] %zu local / %zu pack / %zu unpack ops: residency %.2f ms, "
-                     "planning %.2f, work lists %.2f, upload %.2f, total %.2f\n",
-                     p.local_ops.size(), p.pack_ops.size(), p.unpack_ops.size(), t_resid, t_plan,
-                     t_work, now() - t0 - t_resid - t_plan - t_work, now() - t0);
-
+    auto cp = build_cached_plan(jobs, c, dc);
     g_plans.push_front({h.h, std::move(key), std::move(cp)});
     while (g_plans.size() > kMaxPlans) g_plans.pop_back();
     return g_plans.front().plan.get();
@@ -2544,27 +2579,66 @@ void issue_exchange(comm* c, const plan& p, char* sb, char* rb, hipStream_t s, i
     NCCL_CHECK(ncclGroupEnd());
 }
 
-// the vectors of a scaled transform: arguments of the call, read (scales) and updated (amax) by
-// its LOCAL / UNPACK kernels
+// The scale scheme of a call over a scaled plan and its arguments (of the call, not of the plan).  The
+// kernel family the plan's scaled LOCAL / UNPACK lists run on (launch_phase) and the item counter they
+// add to (count_phase) follow from the tag: a new scheme is a tag with its payload here and a case in
+// each of those two.
+enum class scale_scheme { none, vectors, mx, block };
 struct scaled_args {
-    const void *row_scale = nullptr, *col_scale = nullptr;
-    void *row_amax = nullptr, *col_amax = nullptr;
-    bool amax() const { return row_amax || col_amax; }
-    // an MX call (costa_hip_transform_mx): the same lists on mx_kernel, its tensors in target coordinates
-    bool mx = false;
-    mx_side a_scales, c_scales;
-    bool ceil = false;
-    // a block-scaled call (costa_hip_transform_block_scaled): the same ops on block_kernel
-    bool blk = false;
-    block_side a_blocks, c_blocks;
-    bool pow2 = false;
-    bool blk_quant() const { return blk && c_blocks.data; }
+    scale_scheme scheme = scale_scheme::none;
+    struct {  // vectors (costa_hip_transform_scaled, _amax): scaled_kernel reads the scales, updates the amax outputs
+        const void *row_scale = nullptr, *col_scale = nullptr;
+        void *row_amax = nullptr, *col_amax = nullptr;
+    } vec;
+    struct {  // mx (costa_hip_transform_mx): mx_kernel, its tensors in target coordinates
+        mx_side a_scales, c_scales;
+        bool ceil = false;
+    } mx;
+    struct {  // block (costa_hip_transform_block_scaled): block_kernel
+        block_side a_scales, c_scales;
+        bool pow2 = false;
+    } blk;
+    bool amax() const { return vec.row_amax || vec.col_amax; }
+    // block_kernel's quantising form: over the 128 x 128 regions instead of the plan's sub-tiles
+    bool quantises() const { return scheme == scale_scheme::block && blk.c_scales.data; }
 };
 
 // the matrix a layout describes
 void layout_extent(const elayout& L, int64_t& rows, int64_t& cols) {
     rows = L.rows_split.empty() ? 0 : int64_t(L.rows_split.back()) - L.rows_split.front();
     cols = L.cols_split.empty() ? 0 : int64_t(L.cols_split.back()) - L.cols_split.front();
+}
+
+// The argument checks that costa_hip_transform_mx and costa_hip_transform_block_scaled (`who`) share,
+// behind the pair's own: mask, aliasing, a descriptor on exactly the wanted sides, the rounding mode,
+// beta, and each descriptor against its matrix (`check`: check_mx_scales / check_block_scales).
+template <typename Scales>
+void check_scale_job(const std::string& who, const job& j, bool want_a, bool want_c, const Scales& sa,
+                     const Scales& sc, bool rounding_ok, const char* rounding_modes,
+                     void (*check)(const Scales&, int64_t, int64_t, const std::string&)) {
+    const std::string pair = std::string(dtype_name(j.A->dtype)) + " -> " + dtype_name(j.C->dtype);
+    if (j.uplo != 'A') throw error(COSTA_ERR_ARG, who + "no triangular mask");
+    if (j.A == j.C) throw error(COSTA_ERR_ARG, who + "in-place calls are not supported");
+    if (want_a && !sa.data) throw error(COSTA_ERR_ARG, who + "a_scales is required for " + pair);
+    if (!want_a && sa.data) throw error(COSTA_ERR_ARG, who + "a_scales given for a FLOAT source (" + pair + ")");
+    if (want_c && !sc.data) throw error(COSTA_ERR_ARG, who + "c_scales is required for " + pair);
+    if (!want_c && sc.data)
+        throw error(COSTA_ERR_ARG, who + "c_scales given for a FLOAT destination (" + pair + ")");
+    if (!rounding_ok) throw error(COSTA_ERR_ARG, who + "rounding must be " + rounding_modes);
+    if (want_c) {
+        float beta;
+        std::memcpy(&beta, j.s.beta.data(), sizeof beta);
+        if (!(beta == 0.0f)) throw error(COSTA_ERR_ARG, who + "beta must be 0 with c_scales");
+    }
+    int64_t r, k;
+    if (want_a) {
+        layout_extent(*j.A, r, k);
+        check(sa, r, k, who + "a_scales");
+    }
+    if (want_c) {
+        layout_extent(*j.C, r, k);
+        check(sc, r, k, who + "c_scales");
+    }
 }
 
 // The argument checks of costa_hip_transform_mx that need no plan and no device: the pair, which
@@ -2579,37 +2653,22 @@ void check_mx_job(const job& j) {
                                         : dtype_is_fp4(a) || dtype_is_fp4(c)
                                             ? " (FLOAT -> FP4_E2M1, FP4_E2M1 -> FLOAT, FP4_E2M1 -> FP4_E2M1)"
                                             : " (FLOAT -> FP8, FP8 -> FLOAT, FP8 -> the same FP8)"));
-    if (j.uplo != 'A') throw error(COSTA_ERR_ARG, "costa_hip_transform_mx: no triangular mask");
-    if (j.A == j.C) throw error(COSTA_ERR_ARG, "costa_hip_transform_mx: in-place calls are not supported");
-    const bool want_a = dtype_is_fp8(a) || dtype_is_packed(a), want_c = dtype_is_fp8(c) || dtype_is_packed(c);
-    if (want_a && !j.a_scales.data)
-        throw error(COSTA_ERR_ARG, std::string("costa_hip_transform_mx: a_scales is required for ") + dtype_name(a) +
-                                       " -> " + dtype_name(c));
-    if (!want_a && j.a_scales.data)
-        throw error(COSTA_ERR_ARG, std::string("costa_hip_transform_mx: a_scales given for a FLOAT source (") +
-                                       dtype_name(a) + " -> " + dtype_name(c) + ")");
-    if (want_c && !j.c_scales.data)
-        throw error(COSTA_ERR_ARG, std::string("costa_hip_transform_mx: c_scales is required for ") + dtype_name(a) +
-                                       " -> " + dtype_name(c));
-    if (!want_c && j.c_scales.data)
-        throw error(COSTA_ERR_ARG, std::string("costa_hip_transform_mx: c_scales given for a FLOAT destination (") +
-                                       dtype_name(a) + " -> " + dtype_name(c) + ")");
-    if (j.mx_rounding != COSTA_MX_FLOOR && j.mx_rounding != COSTA_MX_CEIL)
-        throw error(COSTA_ERR_ARG, "costa_hip_transform_mx: rounding must be COSTA_MX_FLOOR or COSTA_MX_CEIL");
-    if (want_c) {
-        float beta;
-        std::memcpy(&beta, j.s.beta.data(), sizeof beta);
-        if (!(beta == 0.0f)) throw error(COSTA_ERR_ARG, "costa_hip_transform_mx: beta must be 0 with c_scales");
-    }
-    int64_t r, k;
-    if (want_a) {
-        layout_extent(*j.A, r, k);
-        check_mx_scales(j.a_scales, r, k, "costa_hip_transform_mx: a_scales");
-    }
-    if (want_c) {
-        layout_extent(*j.C, r, k);
-        check_mx_scales(j.c_scales, r, k, "costa_hip_transform_mx: c_scales");
-    }
+    check_scale_job("costa_hip_transform_mx: ", j, dtype_is_fp8(a) || dtype_is_packed(a),
+                    dtype_is_fp8(c) || dtype_is_packed(c), j.a_scales, j.c_scales,
+                    j.mx_rounding == COSTA_MX_FLOOR || j.mx_rounding == COSTA_MX_CEIL,
+                    "COSTA_MX_FLOOR or COSTA_MX_CEIL", check_mx_scales);
+}
+
+// ... and of costa_hip_transform_block_scaled
+void check_block_job(const job& j) {
+    const std::string who = "costa_hip_transform_block_scaled: ";
+    const costa_dtype_t a = j.A->dtype, c = j.C->dtype;
+    if (!block_pair(a, c))
+        throw error(COSTA_ERR_ARG, who + "no block-scaled transform for " + dtype_name(a) + " -> " + dtype_name(c) +
+                                       " (FLOAT -> FP8, FP8 -> FLOAT, FP8 -> the same FP8)");
+    check_scale_job(who, j, dtype_is_fp8(a), dtype_is_fp8(c), j.a_blocks, j.c_blocks,
+                    j.blk_rounding == COSTA_BLOCK_EXACT || j.blk_rounding == COSTA_BLOCK_POW2,
+                    "COSTA_BLOCK_EXACT or COSTA_BLOCK_POW2", check_block_scales);
 }
 
 // a descriptor as the kernel sees it: in target coordinates (`swap`: the tensor is indexed by A's
@@ -2623,68 +2682,6 @@ mx_side mx_side_of(const costa_mx_scales_t& s, bool swap) {
     return o;
 }
 
-// ... and those that need them: device residency and the tile-boundary rule (kept per plan and
-// axis); fills sv
-void mx_args(const job& j, cached_plan& cp, scaled_args& sv) {
-    for (const void* v : {static_cast<const void*>(j.a_scales.data), static_cast<const void*>(j.c_scales.data)})
-        if (v && !is_device_ptr(v))
-            throw error(COSTA_ERR_ARG, "costa_hip_transform_mx: the scale tensors must be device-resident");
-    if (j.c_scales.data) {
-        int& ok = cp.mx_rule[j.c_scales.axis == COSTA_MX_ROWS ? 0 : 1];
-        int64_t m, n;
-        layout_extent(*j.C, m, n);
-        if (ok <= 0) {  // (a failing plan is checked again: the error carries the op)
-            ok = -1;
-            check_mx_ops(cp.p->local_scaled, j.c_scales.axis, m, n);
-            check_mx_ops(cp.p->unpack_scaled, j.c_scales.axis, m, n);
-            ok = 1;
-        }
-    }
-    sv = scaled_args{};
-    sv.mx = true;
-    sv.a_scales = mx_side_of(j.a_scales, std::toupper(static_cast<unsigned char>(j.trans)) != 'N');
-    sv.c_scales = mx_side_of(j.c_scales, false);
-    sv.ceil = j.mx_rounding == COSTA_MX_CEIL;
-}
-
-// The argument checks of costa_hip_transform_block_scaled that need no plan and no device (as
-// check_mx_job): the pair, which descriptors it wants, the rounding mode, beta, shapes and strides.
-void check_block_job(const job& j) {
-    const std::string who = "costa_hip_transform_block_scaled: ";
-    const costa_dtype_t a = j.A->dtype, c = j.C->dtype;
-    const std::string pair = std::string(dtype_name(a)) + " -> " + dtype_name(c);
-    if (!block_pair(a, c))
-        throw error(COSTA_ERR_ARG, who + "no block-scaled transform for " + pair +
-                                       " (FLOAT -> FP8, FP8 -> FLOAT, FP8 -> the same FP8)");
-    if (j.uplo != 'A') throw error(COSTA_ERR_ARG, who + "no triangular mask");
-    if (j.A == j.C) throw error(COSTA_ERR_ARG, who + "in-place calls are not supported");
-    const bool want_a = dtype_is_fp8(a), want_c = dtype_is_fp8(c);
-    if (want_a && !j.a_blocks.data) throw error(COSTA_ERR_ARG, who + "a_scales is required for " + pair);
-    if (!want_a && j.a_blocks.data)
-        throw error(COSTA_ERR_ARG, who + "a_scales given for a FLOAT source (" + pair + ")");
-    if (want_c && !j.c_blocks.data) throw error(COSTA_ERR_ARG, who + "c_scales is required for " + pair);
-    if (!want_c && j.c_blocks.data)
-        throw error(COSTA_ERR_ARG, who + "c_scales given for a FLOAT destination (" + pair + ")");
-    if (j.blk_rounding != COSTA_BLOCK_EXACT && j.blk_rounding != COSTA_BLOCK_POW2)
-        throw error(COSTA_ERR_ARG, who + "rounding must be COSTA_BLOCK_EXACT or COSTA_BLOCK_POW2");
-    if (want_c) {
-        float beta;
-        std::memcpy(&beta, j.s.beta.data(), sizeof beta);
-        if (!(beta == 0.0f)) throw error(COSTA_ERR_ARG, who + "beta must be 0 with c_scales");
-    }
-    int64_t r, k;
-    if (want_a) {
-        layout_extent(*j.A, r, k);
-        check_block_scales(j.a_blocks, r, k, who + "a_scales");
-    }
-    if (want_c) {
-        layout_extent(*j.C, r, k);
-        check_block_scales(j.c_blocks, r, k, who + "c_scales");
-    }
-}
-
-// a descriptor as the kernel sees it, in target coordinates (`swap`: indexed by A's matrix of a
-// transposing job, whose rows are target columns)
 block_side block_side_of(const costa_block_scales_t& s, bool swap) {
     block_side o;
     o.data = s.data;
@@ -2696,146 +2693,111 @@ block_side block_side_of(const costa_block_scales_t& s, bool swap) {
     return o;
 }
 
-// ... and those that need them: device residency and the tile-boundary rule (kept per plan and block
-// shape); fills sv
-void block_args(const job& j, cached_plan& cp, scaled_args& sv) {
-    for (const void* v : {static_cast<const void*>(j.a_blocks.data), static_cast<const void*>(j.c_blocks.data)})
-        if (v && !is_device_ptr(v))
-            throw error(COSTA_ERR_ARG, "costa_hip_transform_block_scaled: the scale tensors must be device-resident");
-    if (j.c_blocks.data) {
-        int& ok = cp.blk_rule[j.c_blocks.block_rows == 1 ? 0 : j.c_blocks.block_cols == 1 ? 1 : 2];
-        int64_t m, n;
-        layout_extent(*j.C, m, n);
-        if (ok <= 0) {  // (a failing plan is checked again: the error carries the op)
-            ok = -1;
-            check_block_ops(cp.p->local_scaled, j.c_blocks.block_rows, j.c_blocks.block_cols, m, n);
-            check_block_ops(cp.p->unpack_scaled, j.c_blocks.block_rows, j.c_blocks.block_cols, m, n);
-            ok = 1;
-        }
-    }
-    sv = scaled_args{};
-    sv.blk = true;
-    sv.a_blocks = block_side_of(j.a_blocks, std::toupper(static_cast<unsigned char>(j.trans)) != 'N');
-    sv.c_blocks = block_side_of(j.c_blocks, false);
-    sv.pow2 = j.blk_rounding == COSTA_BLOCK_POW2;
+// the scale tensors of an MX or block-scaled entry point (`who`) are in device memory
+void scale_tensors_on_device(const std::string& who, const void* a_scales, const void* c_scales) {
+    for (const void* v : {a_scales, c_scales})
+        if (v && !is_device_ptr(v)) throw error(COSTA_ERR_ARG, who + ": the scale tensors must be device-resident");
 }
 
-// The launch blocks of a transform: LOCAL, one round's PACK, one round's UNPACK.  transform() calls
-// them for an RCCL communicator (on the context's three streams, around issue_exchange) and for the
-// selected part of an emulated one (on main, against the caller's package).
-void launch_local(const cached_plan& cp, const scaled_args& sv, phase_timer& tm, hipStream_t ls) {
-    const plan& p = *cp.p;
-    if (cp.c_local.n_items) {
-        tm.start(PH_LOCAL, ls);
-        launch_convert(p.src_dtype, p.dtype, static_cast<const costa_tile_op_t*>(cp.d_local.p),
-                       static_cast<const uint64_t*>(cp.w_local.p), cp.c_local, nullptr, nullptr,
-                       cp.d_scal.p, ls);
-        tm.stop();
-    }
-    if (cp.l_local.n_items()) {
-        tm.start(PH_LOCAL, ls);
-        launch_tiles(p.dtype,
-                     make_launch(cp.l_local, cp.d_local.p, cp.w_local.p, nullptr, nullptr,
-                                 cp.d_scal.p, cp.tr_local, cp.ax_local),
-                     ls);
-        tm.stop();
-    }
-    if (cp.t_local.n_items) {  // the edge tiles of a triangular plan, behind its ordinary LOCAL list
-        tm.start(PH_TRI_LOCAL, ls);
-        launch_tri(p.dtype, static_cast<const costa_tri_op_t*>(cp.d_local_tri.p),
-                   static_cast<const uint64_t*>(cp.w_local_tri.p), cp.t_local, nullptr, nullptr,
-                   cp.d_scal.p, ls);
-        tm.stop();
-    }
-
-    if (cp.s_local.n_items) {  // the LOCAL list of a scaled plan
-        tm.start(PH_LOCAL, ls);
-        if (sv.blk)
-            launch_block(p.src_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(cp.d_local_sc.p),
-                         static_cast<const uint64_t*>(sv.blk_quant() ? cp.w_local_blk.p : cp.w_local_sc.p),
-                         sv.blk_quant() ? cp.b_local : cp.s_local, nullptr, nullptr, cp.d_scal.p, sv.a_blocks,
-                         sv.c_blocks, sv.pow2, ls);
-        else if (sv.mx)
-            launch_mx(p.src_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(cp.d_local_sc.p),
-                      static_cast<const uint64_t*>(cp.w_local_sc.p), cp.s_local, nullptr, nullptr,
-                      cp.d_scal.p, sv.a_scales, sv.c_scales, sv.ceil, ls);
-        else
-            launch_scaled(p.src_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(cp.d_local_sc.p),
-                          static_cast<const uint64_t*>(cp.w_local_sc.p), cp.s_local, nullptr, nullptr,
-                          cp.d_scal.p, sv.row_scale, sv.col_scale, sv.row_amax, sv.col_amax, ls);
-        tm.stop();
-    }
+// The tile-boundary rule of a plan's scaled ops for one kind of c_scales, `check` throwing where it
+// fails; `rule` keeps the outcome with the plan: 0 not checked yet, 1 holds, -1 fails (a failing plan
+// is checked again: the error carries the op).
+template <typename Check>
+void check_rule_once(int& rule, const cached_plan& cp, const elayout& C, Check check) {
+    if (rule > 0) return;
+    int64_t m, n;
+    layout_extent(C, m, n);
+    rule = -1;
+    check(cp.p->local_scaled, m, n);
+    check(cp.p->unpack_scaled, m, n);
+    rule = 1;
 }
 
-// round x's pack lists into the send package sb, on stream s
-void launch_pack_round(const cached_plan& cp, const cached_plan::xround& x, char* sb, phase_timer& tm,
-                       hipStream_t s) {
-    const plan& p = *cp.p;
-    if (x.c_pack.n_items) {
-        tm.start(PH_PACK, s);
-        launch_convert(pack_src(p), pack_dst(p), static_cast<const costa_tile_op_t*>(x.d_pack.p),
-                       static_cast<const uint64_t*>(x.w_pack.p), x.c_pack, nullptr, sb,
-                       cp.d_scal.p, s);
-        tm.stop();
-    }
-    if (x.l_pack.n_items()) {
-        tm.start(PH_PACK, s);
-        launch_tiles(p.pkg_dtype,
-                     make_launch(x.l_pack, x.d_pack.p, x.w_pack.p, nullptr, sb, cp.d_scal.p,
-                                 false, false),
-                     s);
-        tm.stop();
-    }
+// The checks of those two calls that need the plan and the device: residency of the tensors and the
+// tile-boundary rule (kept per plan and axis / block shape); -> the call's arguments
+scaled_args mx_args(const job& j, cached_plan& cp) {
+    scale_tensors_on_device("costa_hip_transform_mx", j.a_scales.data, j.c_scales.data);
+    if (j.c_scales.data)
+        check_rule_once(cp.mx_rule[j.c_scales.axis == COSTA_MX_ROWS ? 0 : 1], cp, *j.C,
+                        [&](const std::vector<costa_scaled_op_t>& ops, int64_t m, int64_t n) {
+                            check_mx_ops(ops, j.c_scales.axis, m, n);
+                        });
+    scaled_args sv;
+    sv.scheme = scale_scheme::mx;
+    sv.mx.a_scales = mx_side_of(j.a_scales, std::toupper(static_cast<unsigned char>(j.trans)) != 'N');
+    sv.mx.c_scales = mx_side_of(j.c_scales, false);
+    sv.mx.ceil = j.mx_rounding == COSTA_MX_CEIL;
+    return sv;
 }
 
-// round x's unpack lists from the receive package rb, on stream s; each launch waits for `moved`
-// (the round's exchange; null: the package is already there)
-void launch_unpack_round(const cached_plan& cp, const cached_plan::xround& x, const char* rb,
-                         const scaled_args& sv, phase_timer& tm, hipStream_t s, hipEvent_t moved) {
-    const plan& p = *cp.p;
-    if (x.c_unpack.n_items) {
-        if (moved) HIP_CHECK(hipStreamWaitEvent(s, moved, 0));
-        tm.start(PH_UNPACK, s);
-        launch_convert(p.pkg_dtype, p.dtype, static_cast<const costa_tile_op_t*>(x.d_unpack.p),
-                       static_cast<const uint64_t*>(x.w_unpack.p), x.c_unpack, rb, nullptr,
-                       cp.d_scal.p, s);
+scaled_args block_args(const job& j, cached_plan& cp) {
+    scale_tensors_on_device("costa_hip_transform_block_scaled", j.a_blocks.data, j.c_blocks.data);
+    if (j.c_blocks.data)
+        check_rule_once(cp.blk_rule[j.c_blocks.block_rows == 1 ? 0 : j.c_blocks.block_cols == 1 ? 1 : 2], cp, *j.C,
+                        [&](const std::vector<costa_scaled_op_t>& ops, int64_t m, int64_t n) {
+                            check_block_ops(ops, j.c_blocks.block_rows, j.c_blocks.block_cols, m, n);
+                        });
+    scaled_args sv;
+    sv.scheme = scale_scheme::block;
+    sv.blk.a_scales = block_side_of(j.a_blocks, std::toupper(static_cast<unsigned char>(j.trans)) != 'N');
+    sv.blk.c_scales = block_side_of(j.c_blocks, false);
+    sv.blk.pow2 = j.blk_rounding == COSTA_BLOCK_POW2;
+    return sv;
+}
+
+// One phase of a transform on stream s: LOCAL, one round's PACK into the send package (dst_base) or
+// one round's UNPACK from the receive package (src_base).  The launches keep their order -- converting
+// list, tile_kernel list, edge tiles, scaled list -- and each waits for `after` (a round's exchange;
+// null: nothing to wait for) and has its own timing bracket.  transform() calls it for an RCCL
+// communicator (on the context's three streams, around issue_exchange) and for the selected part of
+// an emulated one (on main, against the caller's package).
+void launch_phase(const cached_plan& cp, const phase_lists& ph, list_kind kind, const char* src_base,
+                  char* dst_base, const scaled_args& sv, phase_timer& tm, hipStream_t s,
+                  hipEvent_t after = nullptr) {
+    const dtype_pair t = phase_dtypes(*cp.p, kind);
+    const int id = kind == list_local ? PH_LOCAL : kind == list_pack ? PH_PACK : PH_UNPACK;
+    const void* scal = cp.d_scal.p;
+    auto launch = [&](int phase, auto&& run) {
+        if (after) HIP_CHECK(hipStreamWaitEvent(s, after, 0));
+        tm.start(phase, s);
+        run();
         tm.stop();
-    }
-    if (x.l_unpack.n_items()) {
-        if (moved) HIP_CHECK(hipStreamWaitEvent(s, moved, 0));
-        tm.start(PH_UNPACK, s);
-        launch_tiles(p.dtype,
-                     make_launch(x.l_unpack, x.d_unpack.p, x.w_unpack.p, rb, nullptr,
-                                 cp.d_scal.p, x.tr_unpack, x.ax_unpack),
-                     s);
-        tm.stop();
-    }
-    if (x.t_unpack.n_items) {  // the round's edge tiles, after its ordinary unpack launch
-        if (moved) HIP_CHECK(hipStreamWaitEvent(s, moved, 0));
-        tm.start(PH_TRI_UNPACK, s);
-        launch_tri(p.dtype, static_cast<const costa_tri_op_t*>(x.d_unpack_tri.p),
-                   static_cast<const uint64_t*>(x.w_unpack_tri.p), x.t_unpack, rb, nullptr,
-                   cp.d_scal.p, s);
-        tm.stop();
-    }
-    if (x.s_unpack.n_items) {  // the round's unpack list of a scaled plan
-        if (moved) HIP_CHECK(hipStreamWaitEvent(s, moved, 0));
-        tm.start(PH_UNPACK, s);
-        if (sv.blk)
-            launch_block(p.pkg_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(x.d_unpack_sc.p),
-                         static_cast<const uint64_t*>(sv.blk_quant() ? x.w_unpack_blk.p : x.w_unpack_sc.p),
-                         sv.blk_quant() ? x.b_unpack : x.s_unpack, rb, nullptr, cp.d_scal.p, sv.a_blocks,
-                         sv.c_blocks, sv.pow2, s);
-        else if (sv.mx)
-            launch_mx(p.pkg_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(x.d_unpack_sc.p),
-                      static_cast<const uint64_t*>(x.w_unpack_sc.p), x.s_unpack, rb, nullptr,
-                      cp.d_scal.p, sv.a_scales, sv.c_scales, sv.ceil, s);
-        else
-            launch_scaled(p.pkg_dtype, p.dtype, static_cast<const costa_scaled_op_t*>(x.d_unpack_sc.p),
-                          static_cast<const uint64_t*>(x.w_unpack_sc.p), x.s_unpack, rb, nullptr,
-                          cp.d_scal.p, sv.row_scale, sv.col_scale, sv.row_amax, sv.col_amax, s);
-        tm.stop();
-    }
+    };
+    if (ph.convert.n_items)
+        launch(id, [&] {
+            launch_convert(t.src, t.dst, ph.tiles.list<costa_tile_op_t>(), ph.tiles.items(), ph.convert, src_base,
+                           dst_base, scal, s);
+        });
+    if (ph.split.n_items())
+        launch(id, [&] {
+            launch_tiles(t.dst,
+                         make_launch(ph.split, ph.tiles.ops.p, ph.tiles.work.p, src_base, dst_base, scal,
+                                     ph.transposes, ph.reads_c),
+                         s);
+        });
+    if (ph.tri_items.n_items)  // the edge tiles of a triangular plan, behind its ordinary list
+        launch(kind == list_local ? PH_TRI_LOCAL : PH_TRI_UNPACK, [&] {
+            launch_tri(t.dst, ph.tri.list<costa_tri_op_t>(), ph.tri.items(), ph.tri_items, src_base, dst_base, scal, s);
+        });
+    if (ph.scaled_items.n_items)  // the list of a scaled plan, on the kernels of the call's scheme
+        launch(id, [&] {
+            const costa_scaled_op_t* ops = ph.scaled.list<costa_scaled_op_t>();
+            switch (sv.scheme) {
+            case scale_scheme::block:
+                launch_block(t.src, t.dst, ops,
+                             sv.quantises() ? static_cast<const uint64_t*>(ph.block_work.p) : ph.scaled.items(),
+                             sv.quantises() ? ph.block_items : ph.scaled_items, src_base, dst_base, scal,
+                             sv.blk.a_scales, sv.blk.c_scales, sv.blk.pow2, s);
+                break;
+            case scale_scheme::mx:
+                launch_mx(t.src, t.dst, ops, ph.scaled.items(), ph.scaled_items, src_base, dst_base, scal,
+                          sv.mx.a_scales, sv.mx.c_scales, sv.mx.ceil, s);
+                break;
+            default:
+                launch_scaled(t.src, t.dst, ops, ph.scaled.items(), ph.scaled_items, src_base, dst_base, scal,
+                              sv.vec.row_scale, sv.vec.col_scale, sv.vec.row_amax, sv.vec.col_amax, s);
+            }
+        });
 }
 
 // the statistics of those launches
@@ -2848,40 +2810,26 @@ void count_items(const plan& p, const work_split& w) {
         g_stats.fused_pieces += w.n_tiny;
 }
 
-void count_local(const cached_plan& cp, bool amax, bool mx, int blk = 0) {
-    const plan& p = *cp.p;
-    g_stats.tri_items += cp.t_local.n_items;
-    if (blk)
-        g_blk_items += blk == 2 ? cp.b_local.n_items : cp.s_local.n_items;
-    else
-        (mx ? g_mx_items : g_scaled_items) += cp.s_local.n_items;
-    if (amax) g_amax_items += cp.s_local.n_items;
-    if (cp.l_local.n_items() || cp.c_local.n_items || cp.t_local.n_items || cp.s_local.n_items) {
-        g_stats.local_launches++;
-        g_stats.local_bytes += p.local_bytes;
-        count_items(p, cp.l_local);
-        g_stats.convert_items += cp.c_local.n_items;
+// (a phase counts as one launch where any of its lists is non-empty; LOCAL's bytes with it, the
+// packages' bytes with the whole exchange)
+void count_phase(const plan& p, const phase_lists& ph, list_kind kind, const scaled_args& sv) {
+    if (!ph.empty()) {
+        (kind == list_local ? g_stats.local_launches : kind == list_pack ? g_stats.pack_launches
+                                                                         : g_stats.unpack_launches)++;
+        if (kind == list_local) g_stats.local_bytes += p.local_bytes;
     }
+    count_items(p, ph.split);
+    g_stats.convert_items += ph.convert.n_items;
+    g_stats.tri_items += ph.tri_items.n_items;
+    const int64_t n = ph.scaled_items.n_items;
+    switch (sv.scheme) {
+    case scale_scheme::block: g_blk_items += sv.quantises() ? ph.block_items.n_items : n; break;
+    case scale_scheme::mx: g_mx_items += n; break;
+    default: g_scaled_items += n;
+    }
+    if (sv.amax()) g_amax_items += n;
 }
 
-void count_pack_round(const cached_plan& cp, const cached_plan::xround& x) {
-    g_stats.pack_launches += x.l_pack.n_items() || x.c_pack.n_items ? 1 : 0;
-    count_items(*cp.p, x.l_pack);
-    g_stats.convert_items += x.c_pack.n_items;
-}
-
-void count_unpack_round(const cached_plan& cp, const cached_plan::xround& x, bool amax, bool mx, int blk = 0) {
-    g_stats.unpack_launches +=
-        x.l_unpack.n_items() || x.c_unpack.n_items || x.t_unpack.n_items || x.s_unpack.n_items ? 1 : 0;
-    g_stats.tri_items += x.t_unpack.n_items;
-    if (blk)
-        g_blk_items += blk == 2 ? x.b_unpack.n_items : x.s_unpack.n_items;
-    else
-        (mx ? g_mx_items : g_scaled_items) += x.s_unpack.n_items;
-    if (amax) g_amax_items += x.s_unpack.n_items;
-    count_items(*cp.p, x.l_unpack);
-    g_stats.convert_items += x.c_unpack.n_items;
-}
 
 // whether the device allocation around `buffer` has `bytes` bytes from it on (true where the
 // runtime cannot tell)
@@ -2906,24 +2854,25 @@ void run_emulated_part(const comm* c, device_ctx& dc, const cached_plan& cp, con
     const int R = int(cp.rounds.size());
     const int r0 = c->round < 0 ? 0 : c->round, r1 = c->round < 0 ? R : c->round + 1;
     if (c->part == COSTA_EMULATE_LOCAL) {
-        launch_local(cp, sv, tm, dc.main);
-        count_local(cp, sv.amax(), sv.mx, sv.blk ? 1 + sv.blk_quant() : 0);
+        launch_phase(cp, cp.local, list_local, nullptr, nullptr, sv, tm, dc.main);
+        count_phase(p, cp.local, list_local, sv);
         g_stats.transforms++;
     } else if (c->part == COSTA_EMULATE_PACK) {
         if (!buffer_holds(c->buffer, size_t(p.send_elems) * E))
             throw error(COSTA_ERR_ARG, "costa: the emulated send package is smaller than the plan's");
         for (int r = r0; r < r1; ++r) {
-            launch_pack_round(cp, *cp.rounds[size_t(r)], static_cast<char*>(c->buffer), tm, dc.main);
-            count_pack_round(cp, *cp.rounds[size_t(r)]);
+            const phase_lists& pack = cp.rounds[size_t(r)]->pack;
+            launch_phase(cp, pack, list_pack, nullptr, static_cast<char*>(c->buffer), sv, tm, dc.main);
+            count_phase(p, pack, list_pack, sv);
         }
         if (r1 == R) g_stats.pack_bytes += p.pack_bytes;
     } else {
         if (!buffer_holds(c->buffer, size_t(p.recv_elems) * E))
             throw error(COSTA_ERR_ARG, "costa: the emulated receive package is smaller than the plan's");
         for (int r = r0; r < r1; ++r) {
-            launch_unpack_round(cp, *cp.rounds[size_t(r)], static_cast<const char*>(c->buffer), sv, tm,
-                                dc.main, nullptr);
-            count_unpack_round(cp, *cp.rounds[size_t(r)], sv.amax(), sv.mx, sv.blk ? 1 + sv.blk_quant() : 0);
+            const phase_lists& unpack = cp.rounds[size_t(r)]->unpack;
+            launch_phase(cp, unpack, list_unpack, static_cast<const char*>(c->buffer), nullptr, sv, tm, dc.main);
+            count_phase(p, unpack, list_unpack, sv);
         }
         if (r1 == R) g_stats.unpack_bytes += p.unpack_bytes;
     }
@@ -2959,30 +2908,23 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
     cached_plan& cp = *get_plan(jobs, c, dc);
     const plan& p = *cp.p;
     const size_t E = pkg_unit_size(p.pkg_dtype);  // of the send / receive packages
-    // the vectors of a scaled transform: arguments of this call, read by its LOCAL / UNPACK kernels
-    const void* row_scale = p.scaled ? jobs[0].row_scale : nullptr;
-    const void* col_scale = p.scaled ? jobs[0].col_scale : nullptr;
-    // ... and its amax outputs, updated by the same kernels (costa_hip_transform_amax)
-    void* row_amax = p.scaled ? jobs[0].row_amax : nullptr;
-    void* col_amax = p.scaled ? jobs[0].col_amax : nullptr;
-    const bool amax = row_amax || col_amax;
     scaled_args sv;
-    sv.row_scale = row_scale;
-    sv.col_scale = col_scale;
-    sv.row_amax = row_amax;
-    sv.col_amax = col_amax;
     if (blk) {
-        block_args(jobs[0], cp, sv);
+        sv = block_args(jobs[0], cp);
     } else if (mx) {
-        mx_args(jobs[0], cp, sv);
+        sv = mx_args(jobs[0], cp);
     } else if (p.scaled) {
-        if (!row_scale && !col_scale && !amax)
+        // the vectors of a scaled transform: arguments of this call, read by its LOCAL / UNPACK kernels
+        // ... and its amax outputs, updated by the same kernels (costa_hip_transform_amax)
+        sv.scheme = scale_scheme::vectors;
+        sv.vec = {jobs[0].row_scale, jobs[0].col_scale, jobs[0].row_amax, jobs[0].col_amax};
+        if (!sv.vec.row_scale && !sv.vec.col_scale && !sv.amax())
             throw error(COSTA_ERR_ARG, "costa: a scaled transform without scale vectors (use costa_hip_transform)");
-        for (const void* v : {row_scale, col_scale})
+        for (const void* v : {sv.vec.row_scale, sv.vec.col_scale})
             if (v && !is_device_ptr(v))
                 throw error(COSTA_ERR_ARG, "costa: the scale vectors of a scaled transform must be "
                                            "device-resident");
-        for (const void* v : {row_amax, col_amax})
+        for (const void* v : {static_cast<const void*>(sv.vec.row_amax), static_cast<const void*>(sv.vec.col_amax)})
             if (v && !is_device_ptr(v))
                 throw error(COSTA_ERR_ARG, "costa: the amax vectors of a scaled transform must be "
                                            "device-resident");
@@ -3040,7 +2982,7 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
         HIP_CHECK(hipEventRecord(dc.ev_ready, dc.main));
         HIP_CHECK(hipStreamWaitEvent(dc.aux, dc.ev_ready, 0));
     }
-    launch_local(cp, sv, tm, ls);
+    launch_phase(cp, cp.local, list_local, nullptr, nullptr, sv, tm, ls);
 
     if (exchange) {
         dc.send.reserve(size_t(p.send_elems) * E + 256);
@@ -3052,7 +2994,7 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
         const int R = int(cp.rounds.size());
         dc.round_events(size_t(R));
         for (int r = 0; r < R; ++r) {
-            launch_pack_round(cp, *cp.rounds[size_t(r)], sb, tm, dc.main);
+            launch_phase(cp, cp.rounds[size_t(r)]->pack, list_pack, nullptr, sb, sv, tm, dc.main);
             HIP_CHECK(hipEventRecord(dc.ev_packed[size_t(r)], dc.main));
             HIP_CHECK(hipStreamWaitEvent(dc.xch, dc.ev_packed[size_t(r)], 0));
             tm.start(PH_EXCHANGE, dc.xch);
@@ -3061,7 +3003,8 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
             HIP_CHECK(hipEventRecord(dc.ev_moved[size_t(r)], dc.xch));
         }
         for (int r = 0; r < R; ++r)
-            launch_unpack_round(cp, *cp.rounds[size_t(r)], rb, sv, tm, dc.aux, dc.ev_moved[size_t(r)]);
+            launch_phase(cp, cp.rounds[size_t(r)]->unpack, list_unpack, rb, nullptr, sv, tm, dc.aux,
+                         dc.ev_moved[size_t(r)]);
         // the call ends on main once LOCAL, every unpack and every round of the exchange are done
         HIP_CHECK(hipEventRecord(dc.ev_local, dc.aux));
         HIP_CHECK(hipStreamWaitEvent(dc.main, dc.ev_local, 0));
@@ -3079,11 +3022,11 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
     }
 
     g_stats.transforms++;
-    count_local(cp, amax, sv.mx, sv.blk ? 1 + sv.blk_quant() : 0);
+    count_phase(p, cp.local, list_local, sv);
     if (exchange) {
         for (const auto& x : cp.rounds) {
-            count_pack_round(cp, *x);
-            count_unpack_round(cp, *x, amax, sv.mx, sv.blk ? 1 + sv.blk_quant() : 0);
+            count_phase(p, x->pack, list_pack, sv);
+            count_phase(p, x->unpack, list_unpack, sv);
         }
         g_stats.pack_bytes += p.pack_bytes;
         g_stats.unpack_bytes += p.unpack_bytes;
@@ -3430,6 +3373,25 @@ void check_packed_ops(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const st
     }
 }
 
+namespace {
+// the ops of costa_hip_execute_tiles_mx / _block_scaled (`who`) lie inside C's m x n matrix
+void check_ops_inside(const std::string& who, const std::vector<costa_scaled_op_t>& ops, int64_t m, int64_t n) {
+    for (const costa_scaled_op_t& t : ops) {
+        if (t.op.nf <= 0 || t.op.ns <= 0) continue;
+        if (t.row0 < 0 || t.col0 < 0) throw error(COSTA_ERR_ARG, who + ": negative target coordinate");
+        const bool frow = t.op.flags & COSTA_SCALED_F_ROWS;
+        if (t.row0 + int64_t(frow ? t.op.nf : t.op.ns) > m || t.col0 + int64_t(frow ? t.op.ns : t.op.nf) > n)
+            throw error(COSTA_ERR_ARG, who + ": an op reaches past the m x n matrix");
+    }
+}
+// ... and, under c_scales, none of them reads C
+void check_no_axpby(const std::string& who, const std::vector<costa_scaled_op_t>& ops) {
+    for (const costa_scaled_op_t& t : ops)
+        if (((t.op.flags & COSTA_SCALE_MASK) >> COSTA_SCALE_SHIFT) == COSTA_SCALE_AXPBY)
+            throw error(COSTA_ERR_ARG, who + ": beta must be 0 with c_scales (an op of kind AXPBY)");
+}
+}  // namespace
+
 void execute_tiles_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* ops,
                       int64_t n_ops, const void* src_base, void* dst_base, const void* scalars, int n_slots,
                       const costa_mx_scales_t* a_scales, const costa_mx_scales_t* c_scales, int rounding,
@@ -3451,24 +3413,15 @@ void execute_tiles_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const co
     if (m < 0 || n < 0) throw error(COSTA_ERR_ARG, who + ": negative matrix extent");
     if (sa.data) check_mx_scales(sa, a_transposed ? n : m, a_transposed ? m : n, who + ": a_scales");
     std::vector<costa_scaled_op_t> v(ops, ops + n_ops);
-    for (const costa_scaled_op_t& t : v) {
-        if (t.op.nf <= 0 || t.op.ns <= 0) continue;
-        if (t.row0 < 0 || t.col0 < 0) throw error(COSTA_ERR_ARG, who + ": negative target coordinate");
-        const bool frow = t.op.flags & COSTA_SCALED_F_ROWS;
-        if (t.row0 + int64_t(frow ? t.op.nf : t.op.ns) > m || t.col0 + int64_t(frow ? t.op.ns : t.op.nf) > n)
-            throw error(COSTA_ERR_ARG, who + ": an op reaches past the m x n matrix");
-    }
+    check_ops_inside(who, v, m, n);
     if (sc.data) {
         check_mx_scales(sc, m, n, who + ": c_scales");
-        for (const costa_scaled_op_t& t : v)
-            if (((t.op.flags & COSTA_SCALE_MASK) >> COSTA_SCALE_SHIFT) == COSTA_SCALE_AXPBY)
-                throw error(COSTA_ERR_ARG, who + ": beta must be 0 with c_scales (an op of kind AXPBY)");
+        check_no_axpby(who, v);
         check_mx_ops(v, sc.axis, m, n);
     }
     if (p4 || p6) check_packed_ops(src_dtype, dst_dtype, v);
     ctx(device);  // (is_device_ptr needs the device's context)
-    for (const void* p : {static_cast<const void*>(sa.data), static_cast<const void*>(sc.data)})
-        if (p && !is_device_ptr(p)) throw error(COSTA_ERR_ARG, who + ": the scale tensors must be device-resident");
+    scale_tensors_on_device(who, sa.data, sc.data);
     const mx_side da = mx_side_of(sa, a_transposed != 0), dc_ = mx_side_of(sc, false);
     const uintptr_t sb = reinterpret_cast<uintptr_t>(src_base), db = reinterpret_cast<uintptr_t>(dst_base);
     g_mx_items += run_strip_tiles(
@@ -3545,23 +3498,14 @@ void execute_tiles_block(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const
     if (m < 0 || n < 0) throw error(COSTA_ERR_ARG, who + ": negative matrix extent");
     if (sa.data) check_block_scales(sa, a_transposed ? n : m, a_transposed ? m : n, who + ": a_scales");
     std::vector<costa_scaled_op_t> v(ops, ops + n_ops);
-    for (const costa_scaled_op_t& t : v) {
-        if (t.op.nf <= 0 || t.op.ns <= 0) continue;
-        if (t.row0 < 0 || t.col0 < 0) throw error(COSTA_ERR_ARG, who + ": negative target coordinate");
-        const bool frow = t.op.flags & COSTA_SCALED_F_ROWS;
-        if (t.row0 + int64_t(frow ? t.op.nf : t.op.ns) > m || t.col0 + int64_t(frow ? t.op.ns : t.op.nf) > n)
-            throw error(COSTA_ERR_ARG, who + ": an op reaches past the m x n matrix");
-    }
+    check_ops_inside(who, v, m, n);
     if (sc.data) {
         check_block_scales(sc, m, n, who + ": c_scales");
-        for (const costa_scaled_op_t& t : v)
-            if (((t.op.flags & COSTA_SCALE_MASK) >> COSTA_SCALE_SHIFT) == COSTA_SCALE_AXPBY)
-                throw error(COSTA_ERR_ARG, who + ": beta must be 0 with c_scales (an op of kind AXPBY)");
+        check_no_axpby(who, v);
         check_block_ops(v, sc.block_rows, sc.block_cols, m, n);
     }
     ctx(device);  // (is_device_ptr needs the device's context)
-    for (const void* p : {static_cast<const void*>(sa.data), static_cast<const void*>(sc.data)})
-        if (p && !is_device_ptr(p)) throw error(COSTA_ERR_ARG, who + ": the scale tensors must be device-resident");
+    scale_tensors_on_device(who, sa.data, sc.data);
     const block_side da = block_side_of(sa, a_transposed != 0), dc_ = block_side_of(sc, false);
     const uintptr_t sb = reinterpret_cast<uintptr_t>(src_base), db = reinterpret_cast<uintptr_t>(dst_base);
     const bool quant = sc.data != nullptr;

@@ -57,6 +57,28 @@ def test_work_lists_cfg5(tmp_path):
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr
 
 
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
+def test_exchange_rounds_of_ops(tmp_path):
+    """The exchange round of every pack op (by its first package unit) and of every ordinary, edge and
+    scaled unpack op (by its last) lies in round_range() of its peer's package, and no op straddles
+    two peers' packages: block-cyclic pairs over 2 and 4 ranks, a ragged custom pair, a triangular, a
+    scaled FLOAT -> FP8_E4M3 and a packed FP4 job, packages above and below round_min_bytes(), for
+    exchange_rounds() and for one round (`work_check rounds`).  A wrong round is a race between the
+    exchange and the unpack kernels that no emulated-rank test can see."""
+    if not os.path.exists(os.path.join(LIB, "libcosta_amd.so")):
+        pytest.skip("libcosta_amd.so not built (run __graft_entry__.build())")
+    exe = tmp_path / "work_check"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
+                    "-I" + os.path.join(ROOT, "costa_amd", "csrc"),
+                    os.path.join(ROOT, "tools", "work_check.cpp"), "-L" + LIB, "-lcosta_amd",
+                    "-Wl,-rpath," + LIB, "-o", str(exe)], check=True, timeout=300)
+    clean = {k: v for k, v in os.environ.items() if not k.startswith("COSTA_")}
+    for extra in ({}, {"COSTA_EXCHANGE_ROUNDS": "7"}):  # (the default 4, and parts that do not divide evenly)
+        r = subprocess.run([str(exe), "rounds"], capture_output=True, text=True, timeout=300,
+                           env=dict(clean, **extra))
+        assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stdout + r.stderr
+
+
 TUNING = {"COSTA_TINY_SORT": "0", "COSTA_FORCE_SQ": "1", "COSTA_LARGE_SORT": "0", "COSTA_XCD_BANDS": "0",
           "COSTA_WAVE_POLICY": "1", "COSTA_MERGE": "0", "COSTA_SKEW": "0", "COSTA_TINY_LDS": "1024",
           "COSTA_TINY_COPY": "512", "COSTA_TR_SIDE": "4", "COSTA_MISALIGNED_VEC": "3",

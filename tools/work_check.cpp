@@ -16,7 +16,8 @@
 //     pieces (the same checks), bigger ones stay on the large shape.
 //   run with COSTA_MERGE=0 (ops that continue each other stay apart: every op has one parent);
 //   `work_check merge` checks the merging itself; `work_check cover` that the sub-tiled work items
-//   of the default lists (panels, skew XCD groups, merged ragged blocks) cover their ops exactly.
+//   of the default lists (panels, skew XCD groups, merged ragged blocks) cover their ops exactly;
+//   `work_check rounds` the exchange round of every pack and unpack op of multi-rank plans.
 // Prints "ok" and exits 0, or prints the first violation and exits 1.
 #include <chrono>
 #include <complex>
@@ -765,8 +766,208 @@ static bool check_strips() {
     return true;
 }
 
+// ---- `work_check rounds`: the exchange round of every pack and unpack op (engine.cpp
+// exchange_round_of_ops / _tri / _scaled) against the rule, restated here: a peer's package of n units
+// moves in the parts round_range(n, E, R, r); a pack op belongs to the round that sends its FIRST unit
+// (everything a round sends is packed by then), an unpack op to the round that brings its LAST unit
+// (everything it reads has arrived); no op reaches into another peer's package.  A wrong round is a
+// race on the GPU that the emulated-rank tests cannot see (their package is whole before any unpack).
+static void set_one_zero(job& j, costa_dtype_t compute) {
+    const double d1 = 1.0, d0 = 0.0;
+    const float f1 = 1.f, f0 = 0.f;
+    if (compute == COSTA_DOUBLE) {
+        std::memcpy(j.s.alpha.data(), &d1, 8);
+        std::memcpy(j.s.beta.data(), &d0, 8);
+    } else {
+        std::memcpy(j.s.alpha.data(), &f1, 4);
+        std::memcpy(j.s.beta.data(), &f0, 4);
+    }
+}
+
+// `rank`'s part of an m x n matrix in bm x bn blocks dealt over a pm x pn rank grid
+template <typename T>
+static elayout cyclic(int m, int n, int bm, int bn, int pm, int pn, int rank, uint64_t base) {
+    return erase(block_cyclic_layout<T>(m, n, bm, bn, 1, 1, m, n, pm, pn, 'R', 0, 0, reinterpret_cast<T*>(base), m, 'C',
+                                        rank));
+}
+
+// ... of a matrix in ragged blocks whose owners favour the low ranks (packages of very different sizes)
+static elayout ragged(const std::vector<int>& rs, const std::vector<int>& cs, int n_ranks, int rank, uint64_t seed,
+                      uint64_t base) {
+    const int nr = int(rs.size()) - 1, nc = int(cs.size()) - 1;
+    std::mt19937_64 r(seed);
+    std::vector<int> own(size_t(nr) * size_t(nc));
+    for (int& o : own) {
+        const int x = int(r() % 16);
+        o = x < 9 ? 0 : x < 15 ? 1 % n_ranks : 2 % n_ranks;
+    }
+    std::vector<block_t> blocks;
+    uint64_t off = 0;
+    for (int i = 0; i < nr; ++i)
+        for (int j = 0; j < nc; ++j) {
+            if (own[size_t(i) * size_t(nc) + size_t(j)] != rank) continue;
+            const int rows = rs[size_t(i) + 1] - rs[size_t(i)], cols = cs[size_t(j) + 1] - cs[size_t(j)];
+            blocks.push_back({reinterpret_cast<void*>(base + 4 * off), rows, i, j});
+            off += (uint64_t(rows) * uint64_t(cols) + 63) / 64 * 64;
+        }
+    return erase(custom_layout<float>(nr, nc, rs.data(), cs.data(), own.data(), int(blocks.size()), blocks.data(), 'C'));
+}
+
+struct round_tally {
+    int64_t split = 0, whole = 0;  // peer packages at or above round_min_bytes() / below it
+    int64_t pack = 0, unpack = 0, tri = 0, scaled = 0;
+};
+
+static bool check_rounds_of(const std::string& name, const plan& p, int R, round_tally& n) {
+    const size_t E = pkg_unit_size(p.pkg_dtype);
+    std::vector<int> pr, ur, tr, sr;
+    exchange_round_of_ops(p, R, pr, ur);
+    exchange_round_of_tri(p, R, tr);
+    exchange_round_of_scaled(p, R, sr);
+    CHECK(pr.size() == p.pack_ops.size() && ur.size() == p.unpack_ops.size() && tr.size() == p.unpack_tri.size() &&
+              sr.size() == p.unpack_scaled.size(),
+          "a round per op: %zu / %zu / %zu / %zu", pr.size(), ur.size(), tr.size(), sr.size());
+    // an op over package units [first, first + units) of the buffer laid out by displs / counts, assigned
+    // round r: inside one peer's package, the unit that decides (first or last) in r's range
+    auto one = [&](const char* what, size_t i, const std::vector<int64_t>& displs, const std::vector<int64_t>& counts,
+                   int64_t first, int64_t units, bool by_last, int r) {
+        CHECK(units > 0 && r >= 0 && r < R, "%s op %zu: %lld units, round %d of %d", what, i, (long long)units, r, R);
+        size_t q = 0;
+        while (q < counts.size() && !(first >= displs[q] && first < displs[q] + counts[q])) ++q;
+        CHECK(q < counts.size(), "%s op %zu: unit %lld in no peer's package", what, i, (long long)first);
+        CHECK(first + units <= displs[q] + counts[q], "%s op %zu straddles the packages of peers %zu and %zu", what, i, q,
+              q + 1);
+        int64_t lo, hi;
+        round_range(counts[q], E, R, r, lo, hi);
+        const int64_t at = (by_last ? first + units - 1 : first) - displs[q];
+        CHECK(at >= lo && at < hi, "%s op %zu: its %s unit %lld of peer %zu is outside round %d's [%lld, %lld)", what, i,
+              by_last ? "last" : "first", (long long)at, q, r, (long long)lo, (long long)hi);
+        return true;
+    };
+    for (size_t i = 0; i < p.pack_ops.size(); ++i) {  // (a packed package's pack ops are byte ops: nf x ns units)
+        const costa_tile_op_t& op = p.pack_ops[i];
+        if (!one("pack", i, p.send_displs, p.send_counts, int64_t(op.dst / E), int64_t(op.nf) * op.ns, false, pr[i]))
+            return false;
+    }
+    for (size_t i = 0; i < p.unpack_ops.size(); ++i) {
+        const costa_tile_op_t& op = p.unpack_ops[i];
+        if (!one("unpack", i, p.recv_displs, p.recv_counts, int64_t(op.src / E), int64_t(op.nf) * op.ns, true, ur[i]))
+            return false;
+    }
+    for (size_t i = 0; i < p.unpack_tri.size(); ++i) {
+        const costa_tile_op_t& op = p.unpack_tri[i].op;
+        if (!one("tri unpack", i, p.recv_displs, p.recv_counts, int64_t(op.src / E), int64_t(op.nf) * op.ns, true, tr[i]))
+            return false;
+    }
+    for (size_t i = 0; i < p.unpack_scaled.size(); ++i) {  // (nf x ns elements: of a packed package, their bytes)
+        const costa_tile_op_t& op = p.unpack_scaled[i].op;
+        if (!one("scaled unpack", i, p.recv_displs, p.recv_counts, int64_t(op.src / E),
+                 pkg_units(p.pkg_dtype, int64_t(op.nf) * op.ns), true, sr[i]))
+            return false;
+    }
+    if (R > 1) {
+        for (const auto* counts : {&p.send_counts, &p.recv_counts})
+            for (int64_t c : *counts)
+                if (c > 0) ++(size_t(c) * E >= round_min_bytes() ? n.split : n.whole);
+        n.pack += int64_t(pr.size()), n.unpack += int64_t(ur.size()), n.tri += int64_t(tr.size());
+        n.scaled += int64_t(sr.size());
+    }
+    return true;
+}
+
+static bool check_rounds() {
+    const std::string name = "rounds";
+    const uint64_t A0 = uint64_t(1) << 40, C0 = uint64_t(1) << 42;
+    round_tally n;
+    // the plans of every rank of a case, checked for the library's rounds and for a single one
+    auto run = [&](const std::string& what, int n_ranks, auto make_job) {
+        for (int rank = 0; rank < n_ranks; ++rank) {
+            elayout a, c;
+            job j = make_job(rank, a, c);
+            j.A = &a, j.C = &c;
+            const auto p = make_plan({j}, rank, n_ranks);
+            for (int R : {exchange_rounds(), 1})
+                if (!check_rounds_of(what + ", rank " + std::to_string(rank) + ", R = " + std::to_string(R), *p, R, n))
+                    return false;
+        }
+        return true;
+    };
+    // block-cyclic pairs, fp64 4096^2: over 2 ranks 32 MiB per peer (moved in rounds), over 4 ranks 8 MiB (whole)
+    for (int ranks : {2, 4})
+        for (char op : {'N', 'T'})
+            if (!run(std::string("cyclic ") + op + " over " + std::to_string(ranks), ranks, [&](int rank, elayout& a, elayout& c) {
+                    a = cyclic<double>(4096, 4096, 128, 128, ranks / 2, 2, rank, A0);
+                    c = cyclic<double>(4096, 4096, 96, 160, 2, ranks / 2, rank, C0);
+                    job j;
+                    j.trans = op;
+                    set_one_zero(j, COSTA_DOUBLE);
+                    return j;
+                }))
+                return false;
+    // a ragged custom pair over 3 ranks, fp32 6000 x 5000, owners skewed: packages of both kinds
+    if (!run("ragged custom", 3, [&](int rank, elayout& a, elayout& c) {
+            a = ragged(splits(0xA1, 40, 300, 6000), splits(0xA2, 40, 300, 5000), 3, rank, 0xA3, A0);
+            c = ragged(splits(0xC1, 60, 500, 6000), splits(0xC2, 60, 500, 5000), 3, rank, 0xC3, C0);
+            job j;
+            set_one_zero(j, COSTA_FLOAT);
+            return j;
+        }))
+        return false;
+    // a triangular job (edge tiles in unpack_tri), fp64 4096^2 over 2 ranks
+    for (char uplo : {'U', 'L'})
+        if (!run(std::string("triangular ") + uplo, 2, [&](int rank, elayout& a, elayout& c) {
+                a = cyclic<double>(4096, 4096, 128, 128, 1, 2, rank, A0);
+                c = cyclic<double>(4096, 4096, 96, 160, 2, 1, rank, C0);
+                job j;
+                j.uplo = uplo;
+                j.k = uplo == 'U' ? 3 : -5;
+                set_one_zero(j, COSTA_DOUBLE);
+                return j;
+            }))
+            return false;
+    // a scaled fp32 -> e4m3 job (every unpack op in unpack_scaled; the package holds fp32), 4096^2 over 2 ranks
+    if (!run("scaled FLOAT -> FP8_E4M3", 2, [&](int rank, elayout& a, elayout& c) {
+            a = cyclic<float>(4096, 4096, 128, 128, 1, 2, rank, A0);
+            c = cyclic<fp8_e4m3_bits>(4096, 4096, 96, 160, 2, 1, rank, C0);
+            job j;
+            j.scaled = true;
+            set_one_zero(j, COSTA_FLOAT);
+            return j;
+        }))
+        return false;
+    // a packed FP4 job (the package holds A's bytes, two elements each: pkg_units), 16384^2 over 2 ranks: 32 MiB
+    // per peer; 'T' too, and 2048^2 (below the threshold)
+    for (int m : {16384, 2048})
+        for (char op : {'N', 'T'})
+            if (!run(std::string("MX FP4_E2M1 -> FLOAT ") + op + " " + std::to_string(m), 2, [&](int rank, elayout& a, elayout& c) {
+                    a = cyclic<fp8_e4m3_bits>(m, m, 256, 256, 1, 2, rank, A0);  // the geometry; then two elements a byte
+                    a.dtype = COSTA_FP4_E2M1;
+                    for (eblock& b : a.blocks) b.data = reinterpret_cast<char*>(A0 + (reinterpret_cast<uintptr_t>(b.data) - A0) / 2);
+                    c = cyclic<float>(m, m, 192, 320, 2, 1, rank, C0);
+                    job j;
+                    j.trans = op;
+                    j.scaled = j.mx = true;
+                    set_one_zero(j, COSTA_FLOAT);
+                    return j;
+                }))
+                return false;
+    CHECK(n.split > 0 && n.whole > 0, "%lld packages moved in rounds, %lld whole: both branches must run",
+          (long long)n.split, (long long)n.whole);
+    CHECK(n.pack > 0 && n.unpack > 0 && n.tri > 0 && n.scaled > 0, "ops checked: %lld pack, %lld unpack, %lld tri, %lld scaled",
+          (long long)n.pack, (long long)n.unpack, (long long)n.tri, (long long)n.scaled);
+    std::printf("rounds: R = %d, %lld packages in rounds, %lld whole; %lld pack, %lld unpack, %lld tri, %lld scaled ops\n",
+                exchange_rounds(), (long long)n.split, (long long)n.whole, (long long)n.pack, (long long)n.unpack,
+                (long long)n.tri, (long long)n.scaled);
+    return true;
+}
+
 int main(int argc, char** argv) {
     if (argc > 1 && std::string(argv[1]) == "digest") return digest();
+    if (argc > 1 && std::string(argv[1]) == "rounds") {
+        if (!check_rounds()) return 1;
+        std::printf("ok\n");
+        return 0;
+    }
     if (argc > 1 && std::string(argv[1]) == "strip") {
         if (!check_strips()) return 1;
         std::printf("ok\n");
