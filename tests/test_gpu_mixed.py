@@ -118,6 +118,65 @@ def test_convert_kernel_tile_lists(costa, ta, tc, transpose, variant):
     assert costa.get_stats()["convert_items"] - items0 == subs
 
 
+_SPECIAL_CASES = [pytest.param(ta, tc, sc, id=f"{NAMES[ta]}-{NAMES[tc]}-{sc}")
+                  for ta, tc in PAIRS for sc in ("drawn", "huge") if sc == "drawn" or tc in (CF, Z)]
+
+
+@pytest.mark.parametrize("variant", ["aligned", "src", "dst"])
+@pytest.mark.parametrize("transpose", [False, True], ids=["copy", "transpose"])
+@pytest.mark.parametrize("ta,tc,scalars", _SPECIAL_CASES)
+def test_convert_kernel_tile_lists_special_values(costa, ta, tc, transpose, variant, scalars):
+    """test_convert_kernel_tile_lists' list with oracle.add_specials over source and destination:
+    convert_kernel<cpx...> then leaves the strips whose naive products come out NaN in both parts to
+    the `redo` blocks of run_convert (copy: source and destination read again; transpose: the
+    staged tile of the narrower type), next to strips it stores as usual.  Asserted on the host
+    before the launch, from the data and the oracle alone (specials_common.redo_cells): the whole
+    sub-tile of the (bf + 1) x (bs + 1) ops and the guarded ones each hold a recovered element under
+    ALPHA and AXPBY, plain and CONJ; "huge" (alpha = 1e30 + 1e30i, or 1e300 + 1e300i where C is c128):
+    recoveries without an infinite input, the overflow branch.  The real pairs have no redo: inf /
+    NaN through conv, and ALPHA ops must not read a C full of them.  Every real part bit-equal or NaN
+    on both sides, at most 15 % of the written parts NaN."""
+    import specials_common as sc
+    gpu, ora, n_src, n_dst = _tile_list(ta, tc, transpose, variant)
+    cplx = tc in (CF, Z)
+    scal = np.array([1, 0, -1.5, 0, 0.75 - 0.5j if cplx else 0.75, 1.25 + 0.25j if cplx else 1.25],
+                    oracle.NP[tc])
+    if scalars == "huge":
+        a, b = sc.HUGE[np.dtype(oracle.NP[tc])]
+        scal[2:] = (a, 0, a, b)
+    src = oracle.add_specials(oracle.gen(ta, 0xA1, 0, n_src), ta, 0xA5, 0)
+    dst0 = oracle.add_specials(oracle.gen(tc, 0xC1, 0, n_dst), tc, 0xC5, 0)
+    exp = dst0.copy()
+    conv = convert(src, tc)
+    # (the oracle, each op as the kind it carries: the list's ALPHA op with alpha = 1 is a product on
+    # copy ops too, where the oracle's own rule would memcpy)
+    sc.exec_ops(tc, ora, scal, conv.ctypes.data, exp.ctypes.data)
+    what = f"{NAMES[ta]}->{NAMES[tc]} {'T' if transpose else 'N'} {variant} {scalars}"
+    share = sc.assert_nan_share(exp, sc.written(ora, n_dst, ESIZE[tc]), what)
+    bf, bs = costa.convert_subtile(ta, tc)
+    if cplx:
+        # strip_work.hpp strip_alignment: 16 bytes on the c128 side, 8 on the c64 side, so both VEC
+        # flags hold for every op and a sub-tile is whole exactly when it is bf x bs; a strip of
+        # cshape is 8 bytes of the narrower type: one element
+        subs = sc.strip_subs("convert", ora, bf, bs, lambda op, f0, s0, tf, ts: tf == bf and ts == bs)
+        cells = sc.redo_cells(subs, conv, dst0, exp, scal, 1)
+        for fill in ("whole", "guarded"):
+            for kind in ("ALPHA", "AXPBY"):
+                for cj in ("plain", "conj"):
+                    c = sc.total(cells, fill=fill, kind=kind, conj=cj)
+                    assert c["recovered"] > 0 and c["not_redone"] > 0, f"{what}: {fill} {kind} {cj}: {dict(c)}"
+        if scalars == "huge":
+            # (AXPBY: beta * y overflows on C's own 3e38 / 1e308; a c128 source's 1e308 is inf once
+            # converted to c64, so ALPHA ops overflow only where the source is c64)
+            for kind in ("ALPHA", "AXPBY") if tc == Z else ("AXPBY",):
+                assert sc.total(cells, kind=kind)["overflow"] > 0, f"{what}: {kind}: no overflow-branch recovery"
+    print(f"{what}: {share:.1%} of the written real parts are NaN")
+    ds, dd = dev(src), dev(dst0)
+    costa.execute_tiles_mixed(ta, tc, gpu, scal, ds.data_ptr(), dd.data_ptr())
+    got = dd.cpu().numpy().view(oracle.NP[tc])
+    sc.assert_parts(got, exp, what)
+
+
 def _rounding_values():
     flt_max = float(np.finfo(np.float32).max)
     half = flt_max + 2.0 ** 103          # halfway between FLT_MAX and 2^128: ties to even = inf

@@ -231,6 +231,44 @@ def test_special_values_vs_oracle(gpu, dtype, trans, ab, ords):
     assert_bits_equal_or_both_nan(got, expected)
 
 
+@pytest.mark.parametrize("dtype", [2, 3], ids=["c64", "c128"])
+@pytest.mark.parametrize("trans", ["T", "C"])
+@pytest.mark.parametrize("ab", [(0.75 - 0.5j, 1.25 + 0.25j), (1, 0)], ids=["axpby", "copy-over-nan"])
+def test_special_values_shaped_launch(gpu, dtype, trans, ab):
+    """test_special_values_vs_oracle's blocks are wavefront ops, whose Annex G recovery is inline;
+    here the planned path reaches a shaped tile launch (A one block of 260 x 300, C in 96 x 96
+    blocks), whose complex kernels recompute the strips that need the recovery after their main
+    loop.  oracle.add_specials over A and C; beta = 0 over a C of NaN (no op may read it).  Every
+    real part bit-equal to oracle.transform's or NaN on both sides, at most 15 % of them NaN."""
+    import specials_common
+    alpha, beta = ab
+    a_case, c_case = BC(260, 300, 260, 300), BC(300, 260, 96, 96)
+    npd = oracle.NP[dtype]
+    na, nc = a_case.buf_elems(0, 1), c_case.buf_elems(0, 1)
+    a = oracle.add_specials(oracle.gen(dtype, 0x71, 0, na), dtype, 0x72, 0)
+    c = np.full(nc, np.nan, npd) if beta == 0 else oracle.add_specials(oracle.gen(dtype, 0x73, 0, nc), dtype, 0x74, 0)
+    expected = c.copy()
+    oracle.transform(dtype, trans, alpha, beta, a_case.geom(1), [a], c_case.geom(1), [expected])
+    # (no padding in either layout: the transform writes every element of C)
+    assert nc == 300 * 260
+    share = specials_common.assert_nan_share(expected, np.ones(nc, bool), f"{trans} {ab}")
+    # the redo has something to do: elements the naive product flags whose oracle value is not NaN + NaN i
+    x = a.reshape(300, 260).T.reshape(-1)  # op(A) in C's column-major order, before conjugation
+    fl = specials_common.flagged(specials_common.AXPBY if beta != 0 else specials_common.ALPHA, trans == "C",
+                                 npd(alpha), npd(beta), x, c)
+    rec = fl & ~(np.isnan(expected.real) & np.isnan(expected.imag))
+    assert rec.sum() > 0 and (~fl).sum() > 0
+    print(f"{trans} {ab}: {fl.mean():.1%} flagged, {rec.mean():.1%} recovered, {share:.1%} NaN parts")
+    da, dc = dev(a), dev(c)
+    A = a_case.make_layout(0, da.data_ptr(), 1, dtype)
+    Cl = c_case.make_layout(0, dc.data_ptr(), 1, dtype)
+    items0 = gpu.get_stats()["tile_items"]
+    gpu.transform(A, Cl, gpu.Comm.self(0), trans, alpha, beta)
+    got = host(dc, npd)
+    assert gpu.get_stats()["tile_items"] > items0, "no shaped (non-tiny) work item ran"
+    specials_common.assert_parts(got, expected, f"{trans} {ab}")
+
+
 # ------------------------------------------------------------------ full-size properties
 def test_cfg2_full_size_transpose(gpu):
     """BASELINE cfg 2 at full size: pxtran fp64 16384^2, 256^2 blocks, alpha=1, beta=0.

@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import oracle
+import specials_common
 import tile_lists
 
 pytestmark = pytest.mark.gpu
@@ -64,6 +65,61 @@ def run_list(gpu, name):
     n = dst0.size
     bad = np.flatnonzero((got.view(np.uint8).reshape(n, E) != exp.view(np.uint8).reshape(n, E)).any(1))
     assert bad.size == 0, f"{bad.size} elements differ, first at {bad[0]}: {got[bad[0]]} vs {exp[bad[0]]}"
+
+
+# ---------------------------------------------------------------------------- special values
+# The real types' lists of test_list_with_special_values: one per shaped launch and per wavefront /
+# group launch of DESIGN §4a's table (no redo path there: inf / NaN through the arithmetic, and with
+# them in C, "ALPHA / ZERO ops do not read C" on every launch).  test_tile_variants_cpu.py asserts
+# that each list declares its launch and that no launch of the type is left out.
+REAL_SPECIALS = {
+    "f32": {"large": "mixed[copy-f32]", "large_tr": "mixed[1-f32]", "medium_tr": "medium[f32-64]",
+            "medium_tr_full": "medium[f32-64-full]", "small32_tr": "medium[f32-32]",
+            "skew": "skew[off16-f32]", "skew_wide": "skew[wide-off16-f32]",
+            "cblock_N": "group[N-f32]", "cblock_N+pieces": "group[N+p-f32]",
+            "cblock_T": "group[T-f32]", "cblock_T+pieces": "group[T+p-f32]",
+            "cblock_Nax": "group[Nax-f32]", "cblock_Nax+pieces": "group[Nax+p-f32]",
+            "cblock_Tax": "group[Tax-f32]", "cblock_Tax+pieces": "group[Tax+p-f32]",
+            "tiny_N": "wave[N-f32]", "tiny_T": "wave[T-f32]", "tiny_Nax": "unaligned[copy-f32]",
+            "tiny_Tax": "phase[1-f32]"},
+    "f64": {"large": "mixed[copy-f64]", "large_tr": "mixed[1-f64]", "small_tr": "square[1-f64]",
+            "medium_tr": "medium[f64-mix]", "small32_tr": "medium[f64-32]", "skew": "skew[off64-f64]",
+            "cblock_N": "group[N-f64]", "cblock_N+pieces": "group[N+p-f64]",
+            "cblock_T": "group[T-f64]", "cblock_T+pieces": "group[T+p-f64]",
+            "cblock_Nax": "group[Nax-f64]", "cblock_Nax+pieces": "group[Nax+p-f64]",
+            "cblock_Tax": "group[Tax-f64]", "cblock_Tax+pieces": "group[Tax+p-f64]",
+            "tiny_N": "wave[N-f64]", "tiny_T": "wave[T-f64]", "tiny_Nax": "unaligned[copy-f64]",
+            "tiny_Tax": "unaligned[mixed-f64]"},
+}
+# every c64 / c128 list in both modes ("huge": alpha * x overflows, the recovery's branch without an
+# infinite input); the real types' table in "drawn" mode
+SPECIAL_CASES = [(n, m) for n, (c, _, _) in tile_lists.LISTS.items() if tile_lists.NAMES[c] in ("c64", "c128")
+                 for m in ("drawn", "huge")]
+SPECIAL_CASES += [(n, "drawn") for t in REAL_SPECIALS for n in dict.fromkeys(REAL_SPECIALS[t].values())]
+
+
+@pytest.mark.parametrize("name,mode", SPECIAL_CASES, ids=[f"{n}-{m}" for n, m in SPECIAL_CASES])
+def test_list_with_special_values(gpu, name, mode):
+    """the registry list with oracle.add_specials over its source and initial destination (about one
+    element in 8 with parts from {+-inf, NaN, +-0, huge, -3, 0.5}): the complex shaped launches then
+    skip the stores of the strips whose naive products come out NaN in both parts and recompute them
+    after the main loop (the `redo` blocks of run_tile), next to strips they store as usual.  The
+    route first, one launch, then every real part of the whole destination bit-equal to the oracle's
+    or NaN on both sides (specials_common.assert_parts; at most 15 % of the written parts may be
+    NaN, asserted on the expected buffer).  test_tile_variants_cpu.py counts, from the data and the
+    oracle, that per launch x whole / guarded x copy / transpose x ALPHA / AXPBY these runs hold
+    recovered elements and strips left alone."""
+    code, ops, src, dst0, scal, _ = tile_lists.build(name, mode)
+    tile_lists.check_route(name, ops)
+    exp, mask = tile_lists.expected(code, ops, scal, src, dst0)
+    share = specials_common.assert_nan_share(exp, mask, f"{name} {mode}")
+    d_src = torch.from_numpy(src.view(np.uint8).copy()).cuda()
+    d_dst = torch.from_numpy(dst0.view(np.uint8).copy()).cuda()
+    gpu.execute_tiles(code, ops, scal, d_src.data_ptr(), d_dst.data_ptr())
+    torch.cuda.synchronize()
+    got = d_dst.cpu().numpy().view(dst0.dtype)
+    print(f"{name} {mode}: {share:.1%} of the written real parts are NaN")
+    specials_common.assert_parts(got, exp, f"{name} {mode}")
 
 
 @registry("mixed")

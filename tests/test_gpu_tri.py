@@ -131,6 +131,76 @@ def test_edge_ops(costa, dtype, transpose, variant):
     assert costa.get_stats()["tri_items"] - items0 == want_items
 
 
+_SPECIAL_DTYPES = [S, D, CF, Z]
+
+
+@pytest.mark.parametrize("variant", ["aligned", "dst", "src"])
+@pytest.mark.parametrize("transpose", [False, True], ids=["copy", "transpose"])
+@pytest.mark.parametrize("dtype", _SPECIAL_DTYPES, ids=[NAMES[t] for t in _SPECIAL_DTYPES])
+def test_edge_ops_special_values(costa, dtype, transpose, variant):
+    """test_edge_ops' list with oracle.add_specials over the kept positions of A and all of C (the
+    dropped positions of A stay NaN): tri_kernel<cpx...> then leaves the vectors whose naive
+    products come out NaN in both parts at a kept element to the `redo` blocks of run_tri, which
+    must recompute elements klo .. khi of the vector only.  Asserted on the host before the launch,
+    from the data and the oracle alone (specials_common.redo_cells): recovered elements in
+    sub-tiles that are kept whole and in sub-tiles the diagonal crosses; c64 (two elements a
+    vector): a redone vector that straddles the diagonal, a kept flagged element next to a dropped
+    one.  Real types have no redo: inf / NaN through the arithmetic, ALPHA / ZERO ops over a C full
+    of them.  Every real part of the whole buffer bit-equal or NaN on both sides (at most 15 % of
+    the written parts NaN), and every element no op writes -- dropped ones inside redone vectors
+    included -- keeps its initial bytes."""
+    import specials_common as sc
+    ops, n_src, n_dst = _edge_list(costa, dtype, transpose, variant)
+    E = np.dtype(oracle.NP[dtype]).itemsize
+    cplx = dtype in (CF, Z)
+    scal = np.array([1, 0, 0, 0, -1.5, 0, 0.75 - 0.5j if cplx else 0.75,
+                     1.25 + 0.25j if cplx else 1.25], oracle.NP[dtype])
+    src = oracle.add_specials(oracle.gen(dtype, 0xA7, 0, n_src), dtype, 0xA8, 0)
+    dst0 = oracle.add_specials(oracle.gen(dtype, 0xC7, 0, n_dst), dtype, 0xC8, 0)
+    for t in ops:  # NaN at every dropped position of A
+        _, kept = kept_of_op(t)
+        f, s = np.nonzero(~kept)
+        src[int(t["src"]) + s * int(t["lds"]) + f] = np.nan
+    exp = dst0.copy()
+    ora = ops.copy()
+    ora["src"] = ops["src"] * E
+    ora["dst"] = ops["dst"] * E + exp.ctypes.data
+    # (each op as the kind it carries: the list's BITCOPY ops are byte copies in transpose mode too,
+    # where the oracle's own rule would multiply by 1)
+    oracle_edge_ops(costa, dtype, ora, scal, exp, src.ctypes.data, sc.exec_ops)
+    gpu = ops.copy()
+    gpu["src"] = ops["src"] * E
+    gpu["dst"] = ops["dst"] * E
+    what = f"{NAMES[dtype]} {'T' if transpose else 'N'} {variant}"
+    kept_of = lambda t: kept_of_op(t)[1]  # noqa: E731
+    wr = sc.written(gpu, n_dst, E, kept_of)
+    share = sc.assert_nan_share(exp, wr, what)
+    assert same_bytes(exp[~wr], dst0[~wr])
+    if cplx:
+        bf, bs = costa.tri_subtile(dtype)
+
+        def whole_of(t, f0, s0, tf, ts):
+            """tri_kernels.hip build_tri_work: a sub-tile is listed when it holds a kept element,
+            with the `whole` bit when every element of it is kept"""
+            k = kept_of(t)[f0:f0 + tf, s0:s0 + ts]
+            return None if not k.any() else bool(k.all())
+        cells = sc.redo_cells(sc.strip_subs("tri", gpu, bf, bs, whole_of), src, dst0, exp, scal, 16 // E, kept_of)
+        for fill in ("whole", "guarded"):
+            for kind in ("ALPHA", "AXPBY"):
+                c = sc.total(cells, fill=fill, kind=kind)
+                assert c["recovered"] > 0 and c["not_redone"] > 0, f"{what}: {fill} {kind}: {dict(c)}"
+        assert sc.total(cells, conj="conj")["recovered"] > 0, what
+        if dtype == CF:
+            for kind in ("ALPHA", "AXPBY"):
+                assert sc.total(cells, kind=kind)["straddle"] > 0, f"{what}: {kind}: no redone vector across the diagonal"
+    print(f"{what}: {share:.1%} of the written real parts are NaN")
+    ds, dd = dev(src), dev(dst0)
+    costa.execute_tiles_tri(dtype, gpu, scal, ds.data_ptr(), dd.data_ptr())
+    got = host(dd, dtype)
+    sc.assert_parts(got, exp, what)
+    assert same_bytes(got[~wr], dst0[~wr]), f"{what}: an element no op writes changed"
+
+
 # ------------------------------------------------------------------ transform level
 OPS = [(D, "N"), (D, "T"), (CF, "N"), (CF, "T"), (CF, "C")]  # ('C' on real types is 'T')
 OP_IDS = [f"{NAMES[t]}-{o}" for t, o in OPS]

@@ -155,6 +155,118 @@ def test_sub_tile_mix():
             assert c["whole_tr"] > 0 and c["guarded_tr"] > 0, f"{t} {v}: among transposing ops: {c}"
 
 
+# ---------------------------------------------------------------------------- special values
+# sha256 over (ops, source, initial destination, scalars) of build(name) without specials: the
+# special-value modes must leave the default data of every list as it was
+_DEFAULT_SHA = {
+    "mixed[2-c64]": "fc07be6bc8a1091dc7fbeb0dd0c8c08afaace6d96d1c57ae1ea3ae4d2781f945",
+    "medium[f64-mix]": "cbb084a120f2993a952d0ed6a9743d034bc90fc4739af9986188f783dd87be5d",
+    "square[1-c128]": "de445e583d150167aa7c7c2bb22db6ee5d459361a203ecde7c07399ccf6cd90f",
+    "full[c128]": "c913a854b7bd97864b56ab2d9c7b2ddfeb2f55e25170d98aa52b721ac1d92c1c",
+    "group[Tax+p-f32]": "1e271c7cd5b6a9acc8ee25da5496d57160ddc2abeeb79206e2027d9898df8f6a",
+    "skew[off16-f64]": "b689934124acb177b4b95460982e1177bb963c046133f9221a4672b58f831d45",
+}
+
+
+@pytest.mark.parametrize("name", list(_DEFAULT_SHA))
+def test_default_list_data_is_unchanged(name):
+    import hashlib
+    _, ops, src, dst0, scal, _ = tile_lists.build(name)
+    h = hashlib.sha256()
+    for a in (ops, src, dst0, scal):
+        h.update(a.tobytes())
+    assert h.hexdigest() == _DEFAULT_SHA[name]
+    # and the special-value modes change the data, not the ops
+    _, ops2, src2, dst2, scal2, _ = tile_lists.build(name, "huge")
+    assert ops2.tobytes() == ops.tobytes() and scal2[:4].tobytes() == scal[:4].tobytes()
+    assert src2.tobytes() != src.tobytes() and dst2.tobytes() != dst0.tobytes() and scal2[7] != scal[7]
+
+
+def test_real_special_value_lists_cover_every_launch():
+    """test_gpu_tiles.REAL_SPECIALS names, per real floating type, one list for every launch the
+    type has, and each list declares that launch"""
+    pytest.importorskip("torch")
+    import test_gpu_tiles
+    for t, table in test_gpu_tiles.REAL_SPECIALS.items():
+        assert set(table) == REACHABLE[t], f"{t}: {sorted(set(table) ^ REACHABLE[t])}"
+        for v, name in table.items():
+            code, _, declared = tile_lists.LISTS[name]
+            assert tile_lists.NAMES[code] == t and v in declared, f"{name} does not declare {t} {v}"
+    want = [(n, m) for n, (c, _, _) in tile_lists.LISTS.items() if tile_lists.NAMES[c] in ("c64", "c128")
+            for m in _MODES]
+    assert test_gpu_tiles.SPECIAL_CASES[:len(want)] == want, "every complex list runs in both modes"
+
+
+_MODES = ("drawn", "huge")
+# the ops a shaped launch runs, where not both kinds: `large` is the copy shape (lists without a
+# transposing op), and the lists of the 32 x 32 shape hold transposing ops only (medium_list)
+_OP_MODES = {"large": ("copy",), "small32_tr": ("tr",)}
+# launches whose lists hold no conjugating op (medium_list draws none)
+_NO_CONJ = {"small32_tr"}
+# (type, launch) that cannot run a guarded sub-tile, with the reason (as WHOLE_ONLY above)
+_REDO_WHOLE_ONLY = {
+    # engine.cpp work_split::full: the launch is chosen only when every sub-tile of the list is whole
+    ("c128", "large_tr_full"),
+}
+
+
+@pytest.mark.parametrize("t", ["c64", "c128"])
+def test_redo_cells(t):
+    """the special-value runs of test_gpu_tiles.test_list_with_special_values reach every redo block
+    of run_tile: per shaped launch of the type, over the lists that declare it and both modes, each
+    of {whole, guarded} x {copy op, transposing op} x {ALPHA, AXPBY} holds at least one recovered
+    element (flagged by the naive product, not NaN in both parts in the oracle's result: the redo
+    must produce it) and one strip the main loop stores itself.  c64 (two elements a strip): per
+    launch a redone strip that also holds an unflagged finite element and, in a guarded cell, a
+    redone strip cut by the sub-tile's edge.  Per type: recoveries without an infinite input (the
+    overflow branch) on `large` and `large_tr` under the huge scalars; a recovered element of a
+    conjugating op per launch.  Counted by specials_common.redo_cells from the executor's work
+    items, the data and the oracle alone; at most 15 % NaN parts per list.  An empty cell names
+    itself: it is closed by another list or seed, never by dropping the cell."""
+    from specials_common import total
+    cells = {m: {} for m in _MODES}
+    for name, (code, _, declared) in tile_lists.LISTS.items():
+        if tile_lists.NAMES[code] != t:
+            continue
+        for m in _MODES:
+            got, share = tile_lists.special_cells(name, m)
+            assert not set(k[0] for k in got) - declared
+            for k, c in got.items():
+                cells[m].setdefault(k, c.__class__()).update(c)
+    both = {}
+    for m in _MODES:
+        for k, c in cells[m].items():
+            both.setdefault(k, c.__class__()).update(c)
+    for k in sorted(both):
+        print(t, *k, dict(both[k]))
+    launches = sorted(REACHABLE[t] & set(tile_lists.SHAPED))
+    assert {k[0] for k in both} == set(launches)
+    empty = []
+    for v in launches:
+        fills = ("whole",) if (t, v) in _REDO_WHOLE_ONLY else ("whole", "guarded")
+        for fill in fills:
+            for mode in _OP_MODES.get(v, ("copy", "tr")):
+                for kind in ("ALPHA", "AXPBY"):
+                    c = total(both, launch=v, fill=fill, mode=mode, kind=kind)
+                    for what in ("recovered", "not_redone"):
+                        if c[what] == 0:
+                            empty.append(f"{v} {fill} {mode} {kind}: no {what}")
+        if (t, v) in _REDO_WHOLE_ONLY:
+            assert total(both, launch=v, fill="guarded")["redone"] == 0, f"{t} {v} runs guarded sub-tiles"
+        if v not in _NO_CONJ and total(both, launch=v, conj="conj")["recovered"] == 0:
+            empty.append(f"{v}: no recovered element of a CONJ op")
+        if t == "c64":
+            if total(both, launch=v)["mixed"] == 0:
+                empty.append(f"{v}: no redone strip with an unflagged finite element")
+            if total(both, launch=v, fill="guarded")["partial"] == 0:
+                empty.append(f"{v} guarded: no redone partial strip")
+    for v in ("large", "large_tr"):
+        # (the drawn data's 3e38 / 1e308 overflow some products already; the huge scalars add to them)
+        if total(cells["huge"], launch=v)["overflow"] <= total(cells["drawn"], launch=v)["overflow"]:
+            empty.append(f"{v} (huge): no recovery through the overflow branch")
+    assert not empty, f"{t}: empty cells of the special-value runs:\n  " + "\n  ".join(empty)
+
+
 def test_golden_case_routes():
     """a record, not an assertion (-s): the launches the golden cases' local, pack and unpack lists take"""
     import costa_amd

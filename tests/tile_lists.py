@@ -23,6 +23,7 @@ import numpy as np
 
 import costa_amd
 import oracle
+import specials_common
 
 TINY_LDS = 4096  # engine.hpp kTinyLdsDefault
 CODES = {"f32": 0, "f64": 1, "c64": 2, "c128": 3, "i32": 4}
@@ -130,11 +131,13 @@ _DIMS = {
 SHAPED = ("large", "large_tr", "large_tr_full", "small_tr", "medium_tr", "medium_tr_full", "small32_tr")
 
 
-def subtiles(dtype, ops, kind="local"):
-    """the sub-tiles each tile_kernel launch of this list runs, as tile_kernel sorts them:
-    {variant: {"whole": n, "guarded": n, "whole_tr": n, "guarded_tr": n}}.  whole = the FULL
-    instantiation of run_tile (a BF x BS sub-tile of an op with both VEC flags, as the executor's
-    ordered list carries them), guarded = every other one; *_tr: those of transposing ops"""
+def subtile_items(dtype, ops, kind="local"):
+    """the sub-tiles each tile_kernel launch of this list runs, from the executor's own work items:
+    {variant: (op, f0, s0, tf, ts, whole)}, arrays with one entry per work item.  op = the item's
+    record of the executor's ordered list (offsets in bytes, both VEC flags as the executor set
+    them), (f0, s0) the sub-tile's origin in the op and (tf, ts) its extent as tile_kernel computes
+    them; whole = the FULL instantiation of run_tile (a BF x BS sub-tile of an op with both VEC
+    flags), every other one is guarded"""
     t = NAMES[int(dtype)]
     w = costa_amd.work_export(dtype, ops, kind)
     m = w.meta
@@ -151,11 +154,23 @@ def subtiles(dtype, ops, kind="local"):
         sub = (item & np.uint64(0xFFFFFFFF)).astype(np.int64)
         nf, ns = op["nf"].astype(np.int64), op["ns"].astype(np.int64)
         nbf = (nf + bf - 1) // bf
-        tf = np.minimum(bf, nf - sub % nbf * bf)
-        ts = np.minimum(bs, ns - sub // nbf * bs)
+        f0, s0 = sub % nbf * bf, sub // nbf * bs
+        tf = np.minimum(bf, nf - f0)
+        ts = np.minimum(bs, ns - s0)
         assert (tf > 0).all() and (ts > 0).all()
         both = (op["flags"] & (VEC_SRC | VEC_DST)) == (VEC_SRC | VEC_DST)
         whole = (tf == bf) & (ts == bs) & both
+        out[v] = (op, f0, s0, tf, ts, whole)
+    return out
+
+
+def subtiles(dtype, ops, kind="local"):
+    """the sub-tiles of subtile_items counted as tile_kernel sorts them:
+    {variant: {"whole": n, "guarded": n, "whole_tr": n, "guarded_tr": n}}.  whole = the FULL
+    instantiation of run_tile (a BF x BS sub-tile of an op with both VEC flags, as the executor's
+    ordered list carries them), guarded = every other one; *_tr: those of transposing ops"""
+    out = {}
+    for v, (op, _, _, _, _, whole) in subtile_items(dtype, ops, kind).items():
         tr = (op["flags"] & TR) != 0
         out[v] = {"whole": int(whole.sum()), "guarded": int((~whole).sum()),
                   "whole_tr": int((whole & tr).sum()), "guarded_tr": int((~whole & tr).sum())}
@@ -746,10 +761,49 @@ def extents(name):
     return code, ops, n_src, n_dst
 
 
-def build(name):
-    """-> (dtype code, ops, src, dst0, scalars, declared) of a registry list"""
+# oracle.add_specials seeds of the source and of the initial destination in the special-value modes
+SPECIAL_SEEDS = (0x5A11, 0x5C22)
+
+
+def build(name, specials=None):
+    """-> (dtype code, ops, src, dst0, scalars, declared) of a registry list.  specials = "drawn":
+    oracle.add_specials (about one element in 8 with parts from {+-inf, NaN, +-0, huge, -3, 0.5}, the
+    golden specials' rule) over the drawn source and initial destination, the drawn scalars kept;
+    "huge": slots 2 and 3 take specials_common.HUGE's pair besides (alpha * x overflows: Annex G's recovery with
+    no infinite input)"""
+    assert specials in (None, "drawn", "huge"), specials
     code, builder, declared = LISTS[name]
-    return (code,) + _data(*builder()) + (declared,)
+    ops, src, dst0, scal = _data(*builder())
+    if specials is not None:
+        assert NAMES[code] != "i32", "add_specials leaves integers as they are"
+        src = oracle.add_specials(src, code, SPECIAL_SEEDS[0], 0)
+        dst0 = oracle.add_specials(dst0, code, SPECIAL_SEEDS[1], 0)
+        if specials == "huge":
+            a, b = specials_common.HUGE[np.dtype(oracle.NP[code])]
+            scal = scal.copy()
+            scal[4:8] = (a, 0, a, b)
+    return code, ops, src, dst0, scal, declared
+
+
+def expected(code, ops, scal, src, dst0):
+    """the oracle's destination after the list, each op as the kind it carries
+    (specials_common.exec_ops: the lists draw ALPHA with alpha = 1 on copy ops too, which the oracle's
+    own rule would memcpy), and the mask of the elements its ops write"""
+    exp = dst0.copy()
+    specials_common.exec_ops(code, ops, scal, src.ctypes.data, exp.ctypes.data)
+    return exp, specials_common.written(ops, dst0.size, dst0.itemsize)
+
+
+def special_cells(name, specials):
+    """-> (specials_common.redo_cells of the shaped launches the list declares, share of NaN parts
+    among the expected real parts it writes): host and oracle only"""
+    code, ops, src, dst0, scal, declared = build(name, specials)
+    exp, mask = expected(code, ops, scal, src, dst0)
+    share = specials_common.assert_nan_share(exp, mask, f"{name} {specials}")
+    subs = (specials_common.Sub(v, op[i], int(f0[i]), int(s0[i]), int(tf[i]), int(ts[i]), bool(whole[i]))
+            for v, (op, f0, s0, tf, ts, whole) in subtile_items(code, ops).items() if v in declared
+            for i in range(f0.size))
+    return specials_common.redo_cells(subs, src, dst0, exp, scal, 16 // dst0.itemsize), share
 
 
 def check_route(name, ops=None):

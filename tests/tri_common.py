@@ -74,9 +74,10 @@ def as_tile_ops(costa, tri):
     return ops
 
 
-def oracle_edge_ops(costa, dtype, tri, scalars, dst_buf, src_base=0):
+def oracle_edge_ops(costa, dtype, tri, scalars, dst_buf, src_base=0, exec_ops=oracle.exec_tile_ops):
     """edge ops on host memory: the whole op through the oracle, then the dropped elements of the
-    destination (absolute addresses inside dst_buf) are restored, bit for bit"""
+    destination (absolute addresses inside dst_buf) are restored, bit for bit; exec_ops: the
+    executor of one op (specials_common.exec_ops for lists with op forms no plan holds)"""
     E = dst_buf.itemsize
     raw = dst_buf.view(f"V{E}")
     ops = as_tile_ops(costa, tri)
@@ -86,7 +87,7 @@ def oracle_edge_ops(costa, dtype, tri, scalars, dst_buf, src_base=0):
         idx = (int(t["dst"]) - dst_buf.ctypes.data) // E + off
         assert idx.min() >= 0 and idx.max() < dst_buf.size
         old = raw[idx[~kept]].copy()
-        oracle.exec_tile_ops(dtype, op.reshape(1), scalars, src_base, 0)
+        exec_ops(dtype, op.reshape(1), scalars, src_base, 0)
         raw[idx[~kept]] = old
 
 
