@@ -35,7 +35,7 @@ __all__ = [
     "execute_tiles_tri", "plan_export_tri", "tri_cut", "tri_subtile", "tri_phase_ms",
     "plan_export", "set_profiling", "get_stats", "release_caches", "TILE_OP_DTYPE",
     "ScaledOp", "SCALED_OP_DTYPE", "SCALED_F_ROWS", "transform_scaled", "execute_tiles_scaled",
-    "plan_export_scaled", "scaled_subtile", "scaled_items",
+    "plan_export_scaled", "scaled_subtile", "scaled_items", "mx_subtile", "block_subtile",
     "transform_amax", "layout_amax", "execute_tiles_amax", "amax_items",
     "MxScales", "MX_ROWS", "MX_COLS", "MX_FLOOR", "MX_CEIL", "mx_scales", "transform_mx",
     "execute_tiles_mx", "mx_items", "mx_check_ops", "mx_check_scales",
@@ -315,6 +315,8 @@ def lib():
         "costa_hip_transform_scaled_async": (i, [vp, vp, c, vp, vp, vp, vp, vp, vp]),
         "costa_hip_execute_tiles_scaled": (i, [i, i, C.POINTER(ScaledOp), i64, vp, vp, vp, i, vp, vp, i]),
         "costa_hip_scaled_subtile": (i, [i, i, C.POINTER(i), C.POINTER(i)]),
+        "costa_hip_mx_subtile": (i, [i, i, C.POINTER(i), C.POINTER(i)]),
+        "costa_hip_block_subtile": (i, [i, i, C.POINTER(i), C.POINTER(i)]),
         "costa_hip_scaled_items": (i, [C.POINTER(i64), i]),
         "costa_hip_transform_amax": (i, [vp, vp, c, vp, vp, vp, vp, vp, vp, vp]),
         "costa_hip_transform_amax_async": (i, [vp, vp, c, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -927,6 +929,21 @@ def scaled_subtile(src_dtype, dst_dtype) -> tuple:
     bf, bs = C.c_int(0), C.c_int(0)
     _check(lib().costa_hip_scaled_subtile(element_code(src_dtype), element_code(dst_dtype),
                                           C.byref(bf), C.byref(bs)))
+    return bf.value, bs.value
+
+
+def mx_subtile(src_dtype, dst_dtype) -> tuple:
+    """(bf, bs) of the sub-tile one workgroup runs for an MX pair (costa_hip_mx_subtile)"""
+    bf, bs = C.c_int(), C.c_int()
+    _check(lib().costa_hip_mx_subtile(element_code(src_dtype), element_code(dst_dtype), C.byref(bf), C.byref(bs)))
+    return bf.value, bs.value
+
+
+def block_subtile(src_dtype, dst_dtype) -> tuple:
+    """(bf, bs) of the sub-tile (a quantising pair: the region) one workgroup runs for a block-scaled
+    pair (costa_hip_block_subtile)"""
+    bf, bs = C.c_int(), C.c_int()
+    _check(lib().costa_hip_block_subtile(element_code(src_dtype), element_code(dst_dtype), C.byref(bf), C.byref(bs)))
     return bf.value, bs.value
 
 

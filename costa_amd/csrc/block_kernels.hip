@@ -468,6 +468,15 @@ bool block_pair(costa_dtype_t src, costa_dtype_t dst) {
     return dtype_is_fp8(src) && (dst == COSTA_FLOAT || dst == src);
 }
 
+void block_subtile(costa_dtype_t src, costa_dtype_t dst, int* bf, int* bs) {
+    if (!block_pair(src, dst))
+        throw error(COSTA_ERR_ARG, std::string("costa: no block-scaled kernel for ") + dtype_name(src) + " -> " +
+                                       dtype_name(dst));
+    const bool quant = dtype_is_fp8(dst);
+    *bf = quant ? BLK : SBF;
+    *bs = quant ? BLK : SBS;
+}
+
 strip_list build_block_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
                             const std::vector<costa_scaled_op_t>& ops, uint64_t src_base, uint64_t dst_base,
                             std::vector<costa_scaled_op_t>& ordered, std::vector<uint64_t>& work, bool dst_order) {

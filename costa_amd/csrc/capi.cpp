@@ -581,6 +581,20 @@ int costa_hip_scaled_subtile(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, i
     });
 }
 
+int costa_hip_mx_subtile(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, int* bf, int* bs) {
+    return guarded([&] {
+        if (!bf || !bs) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::mx_subtile(src_dtype, dst_dtype, bf, bs);
+    });
+}
+
+int costa_hip_block_subtile(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, int* bf, int* bs) {
+    return guarded([&] {
+        if (!bf || !bs) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::block_subtile(src_dtype, dst_dtype, bf, bs);
+    });
+}
+
 int costa_hip_scaled_items(int64_t* items, int reset) {
     return guarded([&] {
         if (!items) throw costa::engine::error(COSTA_ERR_ARG, "null argument");

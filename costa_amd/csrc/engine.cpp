@@ -443,8 +443,10 @@ int64_t tiny_lds_budget() {
 }
 
 static bool is_tiny(const costa_tile_op_t& op, int64_t E, bool local) {
-    if (op.flags & COSTA_TILE_TRANSPOSE) return int64_t(op.nf | 1) * op.ns * E <= tiny_lds_budget();
-    return int64_t(op.nf) * op.ns * E <= tiny_copy_budget(E, local);
+    // (elements against budget / E: nf * ns * E passes 2^63 for an op of 2^31 x 2^31, which then
+    // looked tiny instead of being refused as too large)
+    if (op.flags & COSTA_TILE_TRANSPOSE) return int64_t(op.nf | 1) * op.ns <= tiny_lds_budget() / E;
+    return int64_t(op.nf) * op.ns <= tiny_copy_budget(E, local) / E;
 }
 
 static uint32_t vec_flags(uint64_t src, int64_t lds, uint64_t dst, int64_t ldd, int64_t E) {
@@ -1463,7 +1465,7 @@ work_split build_work(costa_dtype_t dtype, const std::vector<costa_tile_op_t>& o
             const uint64_t i = ordered.size();
             if (i > 0xFFFFFFFFull) throw error(COSTA_ERR_ARG, "costa: too many tiles in one list");
             ordered.push_back(op);
-            const uint64_t n = uint64_t((op.nf + bf - 1) / bf) * uint64_t((op.ns + bs - 1) / bs);
+            const uint64_t n = uint64_t((int64_t(op.nf) + bf - 1) / bf) * uint64_t((int64_t(op.ns) + bs - 1) / bs);
             if (n > 0xFFFFFFFFull) throw error(COSTA_ERR_ARG, "costa: tile too large");
             for (uint64_t q = 0; q < n; ++q) work.push_back((i << 32) | q);
         }
@@ -1479,7 +1481,7 @@ work_split build_work(costa_dtype_t dtype, const std::vector<costa_tile_op_t>& o
             for (size_t x = 0; x < key.size(); ++x) {
                 const uint64_t wx = work[w0 + x];
                 const costa_tile_op_t& op = ordered[size_t(wx >> 32)];
-                const uint64_t q = wx & 0xFFFFFFFFull, nbf = uint64_t((op.nf + bf - 1) / bf);
+                const uint64_t q = wx & 0xFFFFFFFFull, nbf = uint64_t((int64_t(op.nf) + bf - 1) / bf);
                 const int64_t f0 = int64_t(q % nbf) * bf, s0 = int64_t(q / nbf) * bs;
                 const bool tr = op.flags & COSTA_TILE_TRANSPOSE;
                 key[x] = {op.dst + uint64_t((tr ? f0 * op.ldd + s0 : s0 * op.ldd + f0) * E), wx};
@@ -1527,7 +1529,7 @@ work_split build_work(costa_dtype_t dtype, const std::vector<costa_tile_op_t>& o
             for (size_t x = 0; x < key.size(); ++x) {
                 const uint64_t wx = work[w0 + x];
                 const costa_tile_op_t& op = ordered[size_t(wx >> 32)];
-                const uint64_t q = wx & 0xFFFFFFFFull, nbf = uint64_t((op.nf + bf - 1) / bf);
+                const uint64_t q = wx & 0xFFFFFFFFull, nbf = uint64_t((int64_t(op.nf) + bf - 1) / bf);
                 const int64_t f0 = int64_t(q % nbf) * bf, s0 = int64_t(q / nbf) * bs;
                 const int64_t fp = f0 / (bf * F) * (bf * F);
                 key[x] = {((op.dst + uint64_t((fp * op.ldd + s0) * E)) << 6) | uint64_t((f0 - fp) / bf), wx};

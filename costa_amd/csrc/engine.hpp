@@ -352,6 +352,10 @@ void execute_tiles_tri(costa_dtype_t dtype, const costa_tri_op_t* ops, int64_t n
 // One kernel family, scaled_kernel<Es, Ed>, one workgroup per sub-tile of one costa_scaled_op_t; the
 // work items are (op index << 32) | sub-tile.  `row_scale` / `col_scale` are kernel arguments.
 void scaled_subtile(costa_dtype_t src, costa_dtype_t dst, int* bf, int* bs);
+// ... of an MX pair (build_scaled_work lists them too) and of a block-scaled pair (build_block_work's
+// regions when it quantises, build_scaled_work's sub-tiles when it dequantises)
+void mx_subtile(costa_dtype_t src, costa_dtype_t dst, int* bf, int* bs);
+void block_subtile(costa_dtype_t src, costa_dtype_t dst, int* bf, int* bs);
 // `ordered` = the ops with each side's VEC flag set from its actual address (base + offset) and its
 // strip's alignment, `work` = every sub-tile of every op: in list order, or (dst_order) by the
 // address of the sub-tile's first destination element

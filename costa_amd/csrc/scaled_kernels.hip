@@ -545,6 +545,13 @@ void scaled_subtile(costa_dtype_t src, costa_dtype_t dst, int* bf, int* bs) {
     *bs = SBS;
 }
 
+void mx_subtile(costa_dtype_t src, costa_dtype_t dst, int* bf, int* bs) {
+    if (!mx_pair(src, dst))
+        throw error(COSTA_ERR_ARG, std::string("costa: no MX kernel for ") + dtype_name(src) + " -> " + dtype_name(dst));
+    *bf = SBF;
+    *bs = SBS;
+}
+
 strip_list build_scaled_work(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
                              const std::vector<costa_scaled_op_t>& ops, uint64_t src_base,
                              uint64_t dst_base, std::vector<costa_scaled_op_t>& ordered,

@@ -784,6 +784,10 @@ int costa_hip_execute_tiles_scaled(costa_dtype_t src_dtype, costa_dtype_t dst_dt
 /* the sub-tile one workgroup of scaled_kernel runs for an accepted pair: elements along the
  * source's fast (*bf) and slow (*bs) dimension */
 int costa_hip_scaled_subtile(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, int* bf, int* bs);
+/* ... of an MX pair (costa_hip_transform_mx) and of a block-scaled pair
+ * (costa_hip_transform_block_scaled: the 128 x 128 regions of a quantising pair) */
+int costa_hip_mx_subtile(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, int* bf, int* bs);
+int costa_hip_block_subtile(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, int* bf, int* bs);
 /* sub-tiles run by scaled_kernel since the last reset (scaled transforms and
  * costa_hip_execute_tiles_scaled); kept beside costa_stats_t, whose layout does not change */
 int costa_hip_scaled_items(int64_t* items, int reset);

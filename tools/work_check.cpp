@@ -17,7 +17,8 @@
 //   run with COSTA_MERGE=0 (ops that continue each other stay apart: every op has one parent);
 //   `work_check merge` checks the merging itself; `work_check cover` that the sub-tiled work items
 //   of the default lists (panels, skew XCD groups, merged ragged blocks) cover their ops exactly;
-//   `work_check rounds` the exchange round of every pack and unpack op of multi-rank plans.
+//   `work_check rounds` the exchange round of every pack and unpack op of multi-rank plans;
+//   `work_check extents` lists whose leading dimensions pass 2^32 bytes / 2^31 elements.
 // Prints "ok" and exits 0, or prints the first violation and exits 1.
 #include <chrono>
 #include <complex>
@@ -961,7 +962,316 @@ static bool check_rounds() {
     return true;
 }
 
+// ---- `work_check extents`: work lists of ops whose leading dimensions put part of them past 2^32
+// bytes / 2^31 elements (tests/test_extents_plan_cpu.py).  A plan of an m x n block-cyclic pair with
+// leading dimensions lda / ldc: every record of the executor's ordered list (sub-tiled ops, the ops of
+// destination-block groups, wavefront pieces), walked element by element in 64-bit arithmetic, moves
+// op(A)(i, j) to C(i, j), every element exactly once; the sub-tile items cover their ops exactly
+// (check_cover) where no group formed.
+template <typename T>
+static std::unique_ptr<plan> rect_plan(int m, int n, int nb, int64_t lda, int64_t ldc, char op, uint64_t A0, uint64_t C0) {
+    const int am = op == 'N' ? m : n, an = op == 'N' ? n : m;
+    auto A = block_cyclic_layout<T>(am, an, nb, nb, 1, 1, am, an, 1, 1, 'R', 0, 0, reinterpret_cast<T*>(A0), int(lda), 'C', 0);
+    auto C = block_cyclic_layout<T>(m, n, nb, nb, 1, 1, m, n, 1, 1, 'R', 0, 0, reinterpret_cast<T*>(C0), int(ldc), 'C', 0);
+    elayout ea = erase(A), ec = erase(C);
+    job j{&ea, &ec, op, {}};
+    const T one = T(1), zero = T(0);
+    std::memcpy(j.s.alpha.data(), &one, sizeof(T));
+    std::memcpy(j.s.beta.data(), &zero, sizeof(T));
+    return make_plan({j}, 0, 1);
+}
+
+struct extent_lists {
+    work_split w;
+    std::vector<costa_tile_op_t> ord;
+    std::vector<uint64_t> work;
+};
+
+template <typename T>
+static bool check_extent_case(const std::string& name, int m, int n, int nb, int64_t lda, int64_t ldc, char op,
+                              extent_lists* out = nullptr) {
+    const int64_t E = int64_t(sizeof(T));
+    const uint64_t A0 = uint64_t(1) << 40, C0 = uint64_t(1) << 44;
+    auto p = rect_plan<T>(m, n, nb, lda, ldc, op, A0, C0);
+    extent_lists l;
+    l.w = build_work(p->dtype, p->local_ops, l.ord, l.work, list_local);
+    const work_split& w = l.w;
+    std::vector<char> header(l.ord.size(), 0), hit(size_t(m) * size_t(n), 0);
+    for (int64_t x = w.n_large + w.n_medium + w.n_skew; x < int64_t(l.work.size()); ++x) header[size_t(l.work[size_t(x)])] = 1;
+    int64_t far = 0;
+    for (size_t x = 0; x < l.ord.size(); ++x) {
+        if (header[x]) continue;
+        const costa_tile_op_t& o = l.ord[x];
+        const bool tr = o.flags & COSTA_TILE_TRANSPOSE;
+        CHECK(tr == (op != 'N') && o.src >= A0 && o.dst >= C0 && (o.src - A0) % uint64_t(E) == 0 && (o.dst - C0) % uint64_t(E) == 0,
+              "record %zu: flags or base", x);
+        for (int64_t s = 0; s < o.ns; ++s)
+            for (int64_t f = 0; f < o.nf; ++f) {
+                const int64_t ea_ = int64_t(o.src - A0) / E + s * int64_t(o.lds) + f;
+                const int64_t ec_ = int64_t(o.dst - C0) / E + (tr ? f * int64_t(o.ldd) + s : s * int64_t(o.ldd) + f);
+                const int64_t ai = ea_ % lda, aj = ea_ / lda, i = ec_ % ldc, j = ec_ / ldc;
+                CHECK(i < m && j < n && (tr ? (ai == j && aj == i) : (ai == i && aj == j)),
+                      "record %zu: C(%lld, %lld) from A(%lld, %lld)", x, (long long)i, (long long)j, (long long)ai, (long long)aj);
+                CHECK(!hit[size_t(j) * size_t(m) + size_t(i)], "C(%lld, %lld) written twice", (long long)i, (long long)j);
+                hit[size_t(j) * size_t(m) + size_t(i)] = 1;
+                far = std::max(far, std::max(ea_, ec_));
+            }
+    }
+    int64_t n_hit = 0;
+    for (char h : hit) n_hit += h;
+    CHECK(n_hit == int64_t(m) * n, "%lld of %lld elements written", (long long)n_hit, (long long)int64_t(m) * n);
+    CHECK(far * E >= (int64_t(1) << 32), "nothing past 2^32 bytes (the case is not stretched)");
+    if (w.n_cblock == 0 && !check_cover("extents " + name, p->dtype, p->local_ops)) return false;
+    std::printf("extents %s: %zu records, %lld large + %lld medium + %lld skew items, %lld groups, %lld pieces, "
+                "last element %lld\n", name.c_str(), l.ord.size(), (long long)w.n_large, (long long)w.n_medium,
+                (long long)w.n_skew, (long long)w.n_cblock, (long long)w.n_tiny, (long long)far);
+    if (out) *out = std::move(l);
+    return true;
+}
+
+// ... and of any layout pair: every non-header record of the executor's ordered list walked element by
+// element, the (destination address, source address) pairs sorted and compared with `want` (the closed
+// form of the pair, sorted by destination address)
+using addr_pair = std::pair<uint64_t, uint64_t>;
+static bool check_extent_pairs(const std::string& name, const plan& p, int64_t E, std::vector<addr_pair> want,
+                               bool want_groups, bool want_medium) {
+    extent_lists l;
+    l.w = build_work(p.dtype, p.local_ops, l.ord, l.work, list_local);
+    const work_split& w = l.w;
+    CHECK(!want_groups || (w.n_cblock > 0 && w.n_tiny > 0), "%lld groups, %lld pieces: both wanted", (long long)w.n_cblock,
+          (long long)w.n_tiny);
+    CHECK(!want_medium || w.n_medium >= 4096, "%lld medium items", (long long)w.n_medium);
+    std::vector<char> header(l.ord.size(), 0);
+    for (int64_t x = w.n_large + w.n_medium + w.n_skew; x < int64_t(l.work.size()); ++x) header[size_t(l.work[size_t(x)])] = 1;
+    std::vector<addr_pair> got;
+    got.reserve(want.size());
+    uint64_t lo = ~uint64_t(0), hi = 0;
+    for (size_t x = 0; x < l.ord.size(); ++x) {
+        if (header[x]) continue;
+        const costa_tile_op_t& o = l.ord[x];
+        const bool tr = o.flags & COSTA_TILE_TRANSPOSE;
+        for (int64_t s = 0; s < o.ns; ++s)
+            for (int64_t f = 0; f < o.nf; ++f) {
+                const uint64_t sa = o.src + uint64_t((s * int64_t(o.lds) + f) * E);
+                got.push_back({o.dst + uint64_t((tr ? f * int64_t(o.ldd) + s : s * int64_t(o.ldd) + f) * E), sa});
+                lo = std::min(lo, sa), hi = std::max(hi, sa);
+            }
+    }
+    std::sort(got.begin(), got.end());
+    std::sort(want.begin(), want.end());
+    CHECK(got.size() == want.size(), "%zu elements moved, the matrix has %zu", got.size(), want.size());
+    for (size_t x = 0; x < got.size(); ++x)
+        CHECK(got[x] == want[x], "element %zu: %#llx <- %#llx, expected %#llx <- %#llx", x, (unsigned long long)got[x].first,
+              (unsigned long long)got[x].second, (unsigned long long)want[x].first, (unsigned long long)want[x].second);
+    uint64_t dlo = ~uint64_t(0), dhi = 0;
+    for (const auto& g : got) dlo = std::min(dlo, g.first), dhi = std::max(dhi, g.first);
+    CHECK(std::max(hi - lo, dhi - dlo) >= (uint64_t(1) << 32), "nothing past 2^32 bytes (the case is not stretched)");
+    // the groups' own invariants (each group's ops tile its range exactly once; check_cblock)
+    if (w.n_cblock > 0 && !check_cblock("extents " + name, p.dtype, p.local_ops, list_local, true)) return false;
+    if (w.n_cblock == 0 && !check_cover("extents " + name, p.dtype, p.local_ops)) return false;
+    std::printf("extents %s: %zu records, %lld large + %lld medium + %lld skew items, %lld groups, %lld pieces\n", name.c_str(),
+                l.ord.size(), (long long)w.n_large, (long long)w.n_medium, (long long)w.n_skew, (long long)w.n_cblock,
+                (long long)w.n_tiny);
+    return true;
+}
+
+// block (bi, bj)'s first element of layout()'s buffer, in elements (its blocks one after another)
+static std::vector<uint64_t> layout_offsets(const std::vector<int>& rs, const std::vector<int>& cs, uint64_t gap) {
+    std::vector<uint64_t> at;
+    uint64_t off = 0;
+    for (size_t i = 0; i + 1 < rs.size(); ++i)
+        for (size_t j = 0; j + 1 < cs.size(); ++j) {
+            at.push_back(off);
+            off += (uint64_t(rs[i + 1] - rs[i]) * uint64_t(cs[j + 1] - cs[j]) + 63) / 64 * 64 + gap;
+        }
+    return at;
+}
+
+static std::unique_ptr<plan> float_plan(const elayout& a, const elayout& c, char op) { return plan_of(a, c, op, 1.f, 0.f); }
+
+// destination-block groups and wavefront pieces fed from a source whose pitch is stretched: small
+// A blocks (block-cyclic, lda = 7158279) tiling the compact blocks of a ragged custom C
+static bool check_extent_groups(char op) {
+    const int m = 300, n = 400;
+    const int64_t lda = 7158279, E = 4;
+    const uint64_t A0 = uint64_t(1) << 40, C0 = uint64_t(1) << 44;
+    std::vector<int> rs = splits(21, 16, 60, m), cs = splits(22, 16, 60, n);
+    rs.insert(rs.begin() + 1, 3);  // a lone strip of 3 rows: its blocks stay wavefront pieces
+    const int am = op == 'N' ? m : n, an = op == 'N' ? n : m;
+    auto A = block_cyclic_layout<float>(am, an, 24, 24, 1, 1, am, an, 1, 1, 'R', 0, 0, reinterpret_cast<float*>(A0), int(lda), 'C', 0);
+    auto C = layout<float>(rs, cs, C0, 4);
+    elayout ea = erase(A), ec = erase(C);
+    auto p = float_plan(ea, ec, op);
+    const std::vector<uint64_t> at = layout_offsets(rs, cs, 4);
+    std::vector<addr_pair> want;
+    for (size_t bi = 0; bi + 1 < rs.size(); ++bi)
+        for (size_t bj = 0; bj + 1 < cs.size(); ++bj)
+            for (int j = cs[bj]; j < cs[bj + 1]; ++j)
+                for (int i = rs[bi]; i < rs[bi + 1]; ++i) {
+                    const uint64_t d = at[bi * (cs.size() - 1) + bj] + uint64_t(j - cs[bj]) * uint64_t(rs[bi + 1] - rs[bi]) + uint64_t(i - rs[bi]);
+                    const uint64_t sidx = op == 'N' ? uint64_t(j) * uint64_t(lda) + uint64_t(i) : uint64_t(i) * uint64_t(lda) + uint64_t(j);
+                    want.push_back({C0 + d * E, A0 + sidx * E});
+                }
+    return check_extent_pairs(std::string("groups fp32 ragged C, stretched A ") + op, *p, E, std::move(want), true, false);
+}
+
+// the medium class: 65 x 64 separate 48 x 48 fp32 blocks of A (no two continue each other) transposed
+// into a block-cyclic C of pitch 1400000: 4160 aligned transposing ops below the large class
+static bool check_extent_medium() {
+    const int nbr = 64, nbc = 65, b = 48;  // A is 3072 x 3120, C 3120 x 3072
+    const int64_t ldc = 1400000, E = 4;
+    const uint64_t A0 = uint64_t(1) << 40, C0 = uint64_t(1) << 44;
+    std::vector<int> rs, cs;
+    for (int i = 0; i <= nbr; ++i) rs.push_back(b * i);
+    for (int j = 0; j <= nbc; ++j) cs.push_back(b * j);
+    auto A = layout<float>(rs, cs, A0, 64);
+    const int m = b * nbc, n = b * nbr;
+    auto C = block_cyclic_layout<float>(m, n, b, b, 1, 1, m, n, 1, 1, 'R', 0, 0, reinterpret_cast<float*>(C0), int(ldc), 'C', 0);
+    elayout ea = erase(A), ec = erase(C);
+    auto p = float_plan(ea, ec, 'T');
+    const std::vector<uint64_t> at = layout_offsets(rs, cs, 64);
+    std::vector<addr_pair> want;
+    want.reserve(size_t(m) * size_t(n));
+    for (int j = 0; j < n; ++j)      // C(i, j) = A(j, i)
+        for (int i = 0; i < m; ++i) {
+            const uint64_t s = at[size_t(j / b) * size_t(nbc) + size_t(i / b)] + uint64_t(i % b) * b + uint64_t(j % b);
+            want.push_back({C0 + (uint64_t(j) * uint64_t(ldc) + uint64_t(i)) * E, A0 + s * E});
+        }
+    return check_extent_pairs("medium fp32 48^2 blocks 'T', ldc 1400000", *p, E, std::move(want), false, true);
+}
+
+static bool check_extents() {
+    const std::string name = "extents";
+    using z = std::complex<double>;
+    // byte rule (fp64, c128) and element rule (fp32), aligned and odd pitches, 'N' and 'T'
+    for (char op : {'N', 'T'}) {
+        const std::string o(1, op);
+        if (!check_extent_case<double>("fp64 24^2 aligned " + o, 300, 400, 24, 1792256, 1792000 + 256 * 3, op)) return false;
+        if (!check_extent_case<double>("fp64 128^2 odd " + o, 300, 400, 128, 1792257, 1792003, op)) return false;
+        if (!check_extent_case<float>("fp32 24^2 odd, 2^31 elements " + o, 300, 400, 24, 7158279, 7158281, op)) return false;
+        if (!check_extent_case<z>("c128 24^2 " + o, 300, 400, 24, 895232, 895233, op)) return false;
+        // a compact block-cyclic target (one merged op: the large shape and pieces, no group)
+        if (!check_extent_case<float>("fp32 24^2 compact C " + o, 300, 400, 24, 7158279, 300, op)) return false;
+        if (!check_extent_groups(op)) return false;
+    }
+    if (!check_extent_medium()) return false;
+    // granule_split gives up once max(lds, ldd) * 64 > INT32_MAX (its parts' pitch p * ld must fit an
+    // int): just below, a copy into an odd pitch is cut at the granules (records of pitch p * ld);
+    // above, every record keeps the op's own pitch
+    for (int64_t ld : {int64_t(33554431), int64_t(33554433)}) {
+        extent_lists l;
+        if (!check_extent_case<float>("granule " + std::to_string(ld), 300, 64, 300, ld, ld, 'N', &l)) return false;
+        bool cut = false;
+        for (const auto& o : l.ord) cut = cut || o.ldd > ld;
+        CHECK(cut == (ld * 64 <= INT32_MAX), "granule bail-out: pitch %lld %s", (long long)ld, cut ? "cut" : "not cut");
+        std::printf("granule bail-out: pitch %lld %s\n", (long long)ld, cut ? "cut at the granules" : "left whole");
+    }
+    // the destination-panel sort key has 16 bits for the panel index: ldd / panel < 2^16.  fp64 'T',
+    // panels of 16384 rows: at ldd = 2^30 - 16384 the key fits (the items walk panel by panel), at
+    // ldd = 2^30 it does not and the items stay in plain destination-address order
+    for (int64_t ld : {(int64_t(1) << 30) - 16384, int64_t(1) << 30}) {
+        extent_lists l;
+        if (!check_extent_case<double>("panel " + std::to_string(ld), 40000, 128, 40000, 128, ld, 'T', &l)) return false;
+        shape_dims sh;
+        tile_shapes(COSTA_DOUBLE, true, &sh);
+        const int bf = l.w.sq ? sh.bf_q : sh.bf, bs = l.w.sq ? sh.bs_q : sh.bs;
+        int64_t back = 0;
+        uint64_t last = 0;
+        for (int64_t x = 0; x < l.w.n_large; ++x) {
+            const costa_tile_op_t& o = l.ord[size_t(l.work[size_t(x)] >> 32)];
+            const int64_t q = int64_t(l.work[size_t(x)] & 0xFFFFFFFFull), nbf = (o.nf + bf - 1) / bf;
+            const uint64_t at = o.dst + uint64_t(((q % nbf) * bf * int64_t(o.ldd) + (q / nbf) * bs) * 8);
+            back += at < last;
+            last = at;
+        }
+        const bool fits = ld / 16384 < 65536;
+        CHECK(l.w.n_large > 1 && (back > 0) == fits, "panel key fallback: ldd %lld, %lld steps back in address order",
+              (long long)ld, (long long)back);
+        std::printf("panel key fallback: ldd %lld %s\n", (long long)ld, fits ? "panel order" : "plain address order");
+    }
+    // strip lists (converting, scaled, edge-tile) of one 300 x 260 op with stretched pitches: every
+    // sub-tile once, VEC flags by the table, dst_order by 64-bit destination addresses
+    auto every = [](const auto&, int, int) { return 1; };
+    for (int tr = 0; tr < 2; ++tr) {
+        std::vector<uint64_t> work;
+        int bf, bs;
+        auto one_op = [&](auto t, int64_t lds, int64_t ldd) {
+            costa_tile_op_t& op = tile_of(t);
+            op.nf = 300, op.ns = 260, op.lds = int32_t(lds), op.ldd = int32_t(ldd);
+            op.src = 4096, op.dst = uint64_t(1) << 24;
+            op.flags = tr ? COSTA_TILE_TRANSPOSE : 0u;
+            return std::vector<decltype(t)>{t, t};
+        };
+        {
+            convert_subtile(COSTA_DOUBLE, COSTA_FLOAT, &bf, &bs);
+            auto ops = one_op(costa_tile_op_t{}, 2753324, 5506604);
+            ops[1].dst += 64;
+            std::vector<costa_tile_op_t> ord;
+            const strip_list l = build_convert_work(COSTA_DOUBLE, COSTA_FLOAT, ops, 0, 0, ord, work);
+            if (!check_strip("extents pair", ops, ord, work, l, bf, bs, 8, 4, 16, 8, 0, 0, 0, every, false)) return false;
+        }
+        for (int by_dst = 0; by_dst < 2; ++by_dst) {
+            scaled_subtile(COSTA_FP8_E4M3, COSTA_FP8_E4M3, &bf, &bs);
+            auto ops = one_op(costa_scaled_op_t{}, 22026412, 22026416);
+            ops[1].op.dst -= 1 << 20;
+            std::vector<costa_scaled_op_t> ord;
+            const strip_list l = build_scaled_work(COSTA_FP8_E4M3, COSTA_FP8_E4M3, ops, 0, 0, ord, work, by_dst);
+            if (!check_strip("extents scaled", ops, ord, work, l, bf, bs, 1, 1, 4, 4, 0, 0, 0, every, by_dst)) return false;
+        }
+        {
+            tri_subtile(COSTA_DOUBLE, &bf, &bs);
+            auto ops = one_op(costa_tri_op_t{}, 2753324, 2753326);
+            for (auto& t : ops) t.diag = -(1 << 30);
+            std::vector<costa_tri_op_t> ord;
+            const strip_list l = build_tri_work(COSTA_DOUBLE, ops, 0, 0, ord, work);
+            auto whole = [](const auto&, int, int) { return 2; };
+            if (!check_strip("extents tri", ops, ord, work, l, bf, bs, 8, 8, 16, 16, 0, 0, 1, whole, false)) return false;
+        }
+    }
+    // the limits are refusals: an op of more sub-tiles than a work item names
+    {
+        costa_tile_op_t t{};
+        t.nf = t.ns = t.lds = t.ldd = INT32_MAX;
+        int refused = 0;
+        std::vector<uint64_t> work;
+        try {
+            std::vector<costa_tile_op_t> ord;
+            build_convert_work(COSTA_DOUBLE, COSTA_FLOAT, {t}, 0, 0, ord, work);
+        } catch (const error& e) { refused += e.code == COSTA_ERR_ARG && std::string(e.what()).find("list too long") != std::string::npos; }
+        try {
+            std::vector<costa_scaled_op_t> ord;
+            costa_scaled_op_t st{};
+            st.op = t;
+            build_scaled_work(COSTA_FLOAT, COSTA_FLOAT, {st}, 0, 0, ord, work, false);
+        } catch (const error& e) { refused += e.code == COSTA_ERR_ARG && std::string(e.what()).find("list too long") != std::string::npos; }
+        for (uint32_t fl : {0u, uint32_t(COSTA_TILE_TRANSPOSE), uint32_t(COSTA_TILE_VEC_SRC | COSTA_TILE_VEC_DST)}) {
+            try {
+                std::vector<costa_tile_op_t> ord;
+                t.flags = fl | (COSTA_SCALE_ALPHA << COSTA_SCALE_SHIFT);
+                build_work(COSTA_DOUBLE, {t}, ord, work, list_local);
+            } catch (const error& e) { refused += e.code == COSTA_ERR_ARG && std::string(e.what()).find("tile too large") != std::string::npos; }
+        }
+        // ... and one that passes 2^32 sub-tiles far from INT32_MAX
+        t.nf = t.ns = t.lds = t.ldd = 1 << 28;
+        for (uint32_t fl : {0u, uint32_t(COSTA_TILE_TRANSPOSE | COSTA_TILE_VEC_SRC | COSTA_TILE_VEC_DST)}) {
+            try {
+                std::vector<costa_tile_op_t> ord;
+                t.flags = fl | (COSTA_SCALE_ALPHA << COSTA_SCALE_SHIFT);
+                build_work(COSTA_DOUBLE, {t}, ord, work, list_local);
+            } catch (const error& e) { refused += e.code == COSTA_ERR_ARG && std::string(e.what()).find("tile too large") != std::string::npos; }
+        }
+        CHECK(refused == 7, "strip / plain limits: %d of 7 lists refused with COSTA_ERR_ARG", refused);
+        std::printf("strip and plain limits: 7 of 7 refused\n");
+    }
+    return true;
+}
+
 int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "extents") {
+        if (!check_extents()) return 1;
+        std::printf("ok\n");
+        return 0;
+    }
     if (argc > 1 && std::string(argv[1]) == "digest") return digest();
     if (argc > 1 && std::string(argv[1]) == "rounds") {
         if (!check_rounds()) return 1;
