@@ -38,7 +38,7 @@ __all__ = [
     "plan_export_scaled", "scaled_subtile", "scaled_items", "mx_subtile", "block_subtile",
     "transform_amax", "layout_amax", "execute_tiles_amax", "amax_items",
     "MxScales", "MX_ROWS", "MX_COLS", "MX_FLOOR", "MX_CEIL", "mx_scales", "transform_mx",
-    "execute_tiles_mx", "mx_items", "mx_check_ops", "mx_check_scales",
+    "execute_tiles_mx", "mx_items", "sr_bits", "mx_check_ops", "mx_check_scales",
     "BlockScales", "BLOCK_EXACT", "BLOCK_POW2", "block_scales", "transform_block_scaled",
     "execute_tiles_block_scaled", "block_items", "block_check_ops", "block_check_scales",
 ]
@@ -331,6 +331,14 @@ def lib():
         "costa_hip_execute_tiles_mx": (i, [i, i, C.POINTER(ScaledOp), i64, vp, vp, vp, i, C.POINTER(MxScales),
                                            C.POINTER(MxScales), i, i64, i64, i, i]),
         "costa_hip_mx_items": (i, [C.POINTER(i64), i]),
+        "costa_hip_transform_mx_sr": (i, [vp, vp, c, vp, vp, C.POINTER(MxScales), C.POINTER(MxScales), i,
+                                          C.c_uint64, vp]),
+        "costa_hip_transform_mx_sr_async": (i, [vp, vp, c, vp, vp, C.POINTER(MxScales), C.POINTER(MxScales), i,
+                                                C.c_uint64, vp, vp]),
+        "costa_hip_execute_tiles_mx_sr": (i, [i, i, C.POINTER(ScaledOp), i64, vp, vp, vp, i,
+                                              C.POINTER(MxScales), C.POINTER(MxScales), i, i64, i64, i,
+                                              C.c_uint64, i]),
+        "costa_hip_sr_bits": (i, [C.c_uint64, i64, i64, C.POINTER(C.c_uint32)]),
         "costa_hip_transform_block_scaled": (i, [vp, vp, c, vp, vp, C.POINTER(BlockScales),
                                                  C.POINTER(BlockScales), i, vp]),
         "costa_hip_transform_block_scaled_async": (i, [vp, vp, c, vp, vp, C.POINTER(BlockScales),
@@ -1094,8 +1102,28 @@ def _mx_arg(d, what, shape=None):
     return C.byref(d)
 
 
+def _sr_seed(seed):
+    """a stochastic_seed argument: None, or an int in [0, 2^64)"""
+    if seed is None:
+        return None
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 1 << 64:
+        raise ValueError(f"stochastic_seed: None or an int in [0, 2^64), not {seed!r}")
+    return C.c_uint64(int(seed))
+
+
+def sr_bits(seed: int, i: int, j: int) -> int:
+    """The 24 random bits U(seed, i, j) of target element (i, j) under stochastic rounding
+    (costa_hip_sr_bits; costa_hip.h, "Stochastic rounding in the MX transforms"); host only."""
+    s = _sr_seed(seed)
+    if s is None:
+        raise ValueError("sr_bits: seed must be an int in [0, 2^64)")
+    v = C.c_uint32(0)
+    _check(lib().costa_hip_sr_bits(s, int(i), int(j), C.byref(v)))
+    return v.value
+
+
 def transform_mx(A: Layout, Cl: Layout, comm: Comm, trans: str = "N", alpha=1.0, beta=0.0,
-                 a_scales=None, c_scales=None, rounding="floor", stream=None):
+                 a_scales=None, c_scales=None, rounding="floor", stream=None, stochastic_seed=None):
     """MX block-scaled transform (costa_hip_transform_mx; costa_hip.h, "MX block-scaled
     transforms"): quantise (FLOAT -> FP8, ``c_scales``), dequantise (FP8 -> FLOAT, ``a_scales``) or
     requantise (FP8 -> the same FP8, both) while redistributing, one E8M0 scale byte per 32 elements
@@ -1110,39 +1138,52 @@ def transform_mx(A: Layout, Cl: Layout, comm: Comm, trans: str = "N", alpha=1.0,
     With ``stream`` the call is stream-ordered and the
     tensors must stay valid until the stream has passed it.  With several ranks each rank writes the
     ``c_scales`` bytes of its own blocks only (merge zero-initialised tensors with a MAX all-reduce)
-    and needs the ``a_scales`` bytes of every block it reads."""
+    and needs the ``a_scales`` bytes of every block it reads.
+    With ``stochastic_seed`` (an int in [0, 2^64); quantise and requantise only) the conversion rounds
+    stochastically (costa_hip_transform_mx_sr; costa_hip.h, "Stochastic rounding in the MX
+    transforms"): an element's decision depends on the seed, its row and column in C's matrix and its
+    value alone, and the scale bytes are those of the call without a seed."""
+    seed = _sr_seed(stochastic_seed)
     if not isinstance(A, Layout) or not isinstance(Cl, Layout):
         raise CostaError(1, "costa: batches of MX layout pairs are not supported")
     code = _scalar_code(A.dtype, Cl.dtype)
     ab, bb = _scalar_bytes(code, alpha), _scalar_bytes(code, beta)
     args = (A.handle, Cl.handle, _chr(trans), ab, bb, _mx_arg(a_scales, "a_scales", A.shape()),
-            _mx_arg(c_scales, "c_scales", Cl.shape()), _mx_rounding(rounding), comm.handle)
+            _mx_arg(c_scales, "c_scales", Cl.shape()), _mx_rounding(rounding))
+    sr = "" if seed is None else "_sr"
+    if seed is not None:
+        args += (seed,)
+    args += (comm.handle,)
     if stream is None:
-        _check(lib().costa_hip_transform_mx(*args))
+        _check(getattr(lib(), "costa_hip_transform_mx" + sr)(*args))
     else:
         s = getattr(stream, "cuda_stream", stream) or 0
-        _check(lib().costa_hip_transform_mx_async(*args, C.c_void_p(s)))
+        _check(getattr(lib(), "costa_hip_transform_mx" + sr + "_async")(*args, C.c_void_p(s)))
 
 
 def execute_tiles_mx(src_dtype, dst_dtype, ops: np.ndarray, scalars: np.ndarray, m: int, n: int,
                      src_base=0, dst_base=0, a_scales=None, c_scales=None, rounding="floor",
-                     a_transposed: bool = False, device: int = 0):
+                     a_transposed: bool = False, device: int = 0, stochastic_seed=None):
     """Run a list of scaled ops (SCALED_OP_DTYPE) in one launch of the MX kernel; ``m`` x ``n`` is C's
     matrix, fp32 ``scalars``; with ``a_transposed`` A's matrix is n x m and ``a_scales`` is indexed by
     it (costa_hip_execute_tiles_mx).  With FP4_E2M1 (quantise, dequantise, requantise as for
     transform_mx) every count of an op is in elements, ``src`` / ``dst`` are byte offsets, and on each
     FP4 side the leading dimension and the extent along the stored-contiguous dimension are even.
     With FP6_E2M3 / FP6_E3M2 the same holds with multiples of 4 on each FP6 side ("FP6 quad"); a byte
-    offset may have any parity."""
+    offset may have any parity.  ``stochastic_seed`` as for transform_mx
+    (costa_hip_execute_tiles_mx_sr)."""
+    seed = _sr_seed(stochastic_seed)
     sc_, dc_ = element_code(src_dtype), element_code(dst_dtype)
     ops = np.ascontiguousarray(ops, dtype=SCALED_OP_DTYPE)
     sc = np.ascontiguousarray(scalars, dtype=np.float32).reshape(-1)
     assert sc.size % 2 == 0
-    _check(lib().costa_hip_execute_tiles_mx(sc_, dc_, ops.ctypes.data_as(C.POINTER(ScaledOp)), ops.size,
-                                            C.c_void_p(_ptr(src_base)), C.c_void_p(_ptr(dst_base)),
-                                            sc.ctypes.data, sc.size // 2, _mx_arg(a_scales, "a_scales"),
-                                            _mx_arg(c_scales, "c_scales"), _mx_rounding(rounding), m, n,
-                                            int(a_transposed), device))
+    args = (sc_, dc_, ops.ctypes.data_as(C.POINTER(ScaledOp)), ops.size, C.c_void_p(_ptr(src_base)),
+            C.c_void_p(_ptr(dst_base)), sc.ctypes.data, sc.size // 2, _mx_arg(a_scales, "a_scales"),
+            _mx_arg(c_scales, "c_scales"), _mx_rounding(rounding), m, n, int(a_transposed))
+    if seed is None:
+        _check(lib().costa_hip_execute_tiles_mx(*args, device))
+    else:
+        _check(lib().costa_hip_execute_tiles_mx_sr(*args, seed, device))
 
 
 def mx_items(reset: bool = False) -> int:

@@ -728,6 +728,53 @@ int costa_hip_execute_tiles_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
     });
 }
 
+int costa_hip_transform_mx_sr(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                              const void* beta, const costa_mx_scales_t* a_scales,
+                              const costa_mx_scales_t* c_scales, int rounding, uint64_t seed,
+                              costa_comm_t comm) {
+    return gpu_guarded([&] {
+        if (!comm || !alpha || !beta) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        auto jobs = make_mx_job(A, C, trans, alpha, beta, a_scales, c_scales, rounding);
+        jobs[0].mx_sr = true;
+        jobs[0].mx_seed = seed;
+        costa::engine::transform(jobs, comm->c);
+    });
+}
+
+int costa_hip_transform_mx_sr_async(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                                    const void* beta, const costa_mx_scales_t* a_scales,
+                                    const costa_mx_scales_t* c_scales, int rounding, uint64_t seed,
+                                    costa_comm_t comm, void* stream) {
+    return gpu_guarded([&] {
+        if (!comm || !alpha || !beta) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        auto jobs = make_mx_job(A, C, trans, alpha, beta, a_scales, c_scales, rounding);
+        jobs[0].mx_sr = true;
+        jobs[0].mx_seed = seed;
+        costa::engine::transform(jobs, comm->c, stream, true);
+    });
+}
+
+int costa_hip_execute_tiles_mx_sr(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
+                                  const costa_scaled_op_t* ops, int64_t n_ops, const void* src_base,
+                                  void* dst_base, const void* scalars, int n_slots,
+                                  const costa_mx_scales_t* a_scales, const costa_mx_scales_t* c_scales,
+                                  int rounding, int64_t m, int64_t n, int a_transposed, uint64_t seed,
+                                  int device) {
+    return gpu_guarded([&] {
+        if (n_ops < 0 || (n_ops > 0 && (!ops || !scalars)))
+            throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::execute_tiles_mx(src_dtype, dst_dtype, ops, n_ops, src_base, dst_base, scalars, n_slots,
+                                        a_scales, c_scales, rounding, m, n, a_transposed, device, &seed);
+    });
+}
+
+int costa_hip_sr_bits(uint64_t seed, int64_t i, int64_t j, uint32_t* u24) {
+    return guarded([&] {
+        if (!u24) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        *u24 = costa::engine::mx_sr_bits(seed, i, j);
+    });
+}
+
 int costa_hip_mx_items(int64_t* items, int reset) {
     return guarded([&] {
         if (!items) throw costa::engine::error(COSTA_ERR_ARG, "null argument");

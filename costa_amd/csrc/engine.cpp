@@ -2595,6 +2595,8 @@ struct scaled_args {
     struct {  // mx (costa_hip_transform_mx): mx_kernel, its tensors in target coordinates
         mx_side a_scales, c_scales;
         bool ceil = false;
+        bool sr = false;  // costa_hip_transform_mx_sr: the SR instances, with the keys of the call's seed
+        mx_sr keys;
     } mx;
     struct {  // block (costa_hip_transform_block_scaled): block_kernel
         block_side a_scales, c_scales;
@@ -2659,6 +2661,9 @@ void check_mx_job(const job& j) {
                     dtype_is_fp8(c) || dtype_is_packed(c), j.a_scales, j.c_scales,
                     j.mx_rounding == COSTA_MX_FLOOR || j.mx_rounding == COSTA_MX_CEIL,
                     "COSTA_MX_FLOOR or COSTA_MX_CEIL", check_mx_scales);
+    if (j.mx_sr && c == COSTA_FLOAT)
+        throw error(COSTA_ERR_ARG, std::string("costa_hip_transform_mx_sr: stochastic rounding needs a quantising "
+                                               "pair (c_scales), not ") + dtype_name(a) + " -> " + dtype_name(c));
 }
 
 // ... and of costa_hip_transform_block_scaled
@@ -2729,6 +2734,8 @@ scaled_args mx_args(const job& j, cached_plan& cp) {
     sv.mx.a_scales = mx_side_of(j.a_scales, std::toupper(static_cast<unsigned char>(j.trans)) != 'N');
     sv.mx.c_scales = mx_side_of(j.c_scales, false);
     sv.mx.ceil = j.mx_rounding == COSTA_MX_CEIL;
+    sv.mx.sr = j.mx_sr;
+    if (j.mx_sr) sv.mx.keys = mx_sr_keys(j.mx_seed);
     return sv;
 }
 
@@ -2793,7 +2800,7 @@ void launch_phase(const cached_plan& cp, const phase_lists& ph, list_kind kind, 
                 break;
             case scale_scheme::mx:
                 launch_mx(t.src, t.dst, ops, ph.scaled.items(), ph.scaled_items, src_base, dst_base, scal,
-                          sv.mx.a_scales, sv.mx.c_scales, sv.mx.ceil, s);
+                          sv.mx.a_scales, sv.mx.c_scales, sv.mx.ceil, s, sv.mx.sr ? &sv.mx.keys : nullptr);
                 break;
             default:
                 launch_scaled(t.src, t.dst, ops, ph.scaled.items(), ph.scaled_items, src_base, dst_base, scal,
@@ -3397,7 +3404,7 @@ void check_no_axpby(const std::string& who, const std::vector<costa_scaled_op_t>
 void execute_tiles_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* ops,
                       int64_t n_ops, const void* src_base, void* dst_base, const void* scalars, int n_slots,
                       const costa_mx_scales_t* a_scales, const costa_mx_scales_t* c_scales, int rounding,
-                      int64_t m, int64_t n, int a_transposed, int device) {
+                      int64_t m, int64_t n, int a_transposed, int device, const uint64_t* seed) {
     std::lock_guard<std::recursive_mutex> lk(g_mutex);
     const std::string who = "costa_hip_execute_tiles_mx";
     if (!mx_pair(src_dtype, dst_dtype))
@@ -3422,6 +3429,10 @@ void execute_tiles_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const co
         check_mx_ops(v, sc.axis, m, n);
     }
     if (p4 || p6) check_packed_ops(src_dtype, dst_dtype, v);
+    if (seed && dst_dtype == COSTA_FLOAT)
+        throw error(COSTA_ERR_ARG, who + "_sr: stochastic rounding needs a quantising pair (c_scales), not " +
+                                       dtype_name(src_dtype) + " -> " + dtype_name(dst_dtype));
+    const mx_sr keys = seed ? mx_sr_keys(*seed) : mx_sr{};
     ctx(device);  // (is_device_ptr needs the device's context)
     scale_tensors_on_device(who, sa.data, sc.data);
     const mx_side da = mx_side_of(sa, a_transposed != 0), dc_ = mx_side_of(sc, false);
@@ -3431,7 +3442,8 @@ void execute_tiles_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const co
         [&](const auto& l, auto& ord, auto& w) { return build_scaled_work(src_dtype, dst_dtype, l, sb, db, ord, w, false); },
         [&](const costa_scaled_op_t* d_ops, const uint64_t* d_work, const strip_list& l, const void* d_scal, void* s) {
             launch_mx(src_dtype, dst_dtype, d_ops, d_work, l, static_cast<const char*>(src_base),
-                      static_cast<char*>(dst_base), d_scal, da, dc_, rounding == COSTA_MX_CEIL, s);
+                      static_cast<char*>(dst_base), d_scal, da, dc_, rounding == COSTA_MX_CEIL, s,
+                      seed ? &keys : nullptr);
         });
 }
 

@@ -122,6 +122,10 @@ struct job {
     costa_mx_scales_t a_scales{};
     costa_mx_scales_t c_scales{};
     int mx_rounding = 0;
+    // ... and, for costa_hip_transform_mx_sr, the seed of the call's stochastic rounding (of the call,
+    // not of the plan: the cache key does not see it)
+    bool mx_sr = false;
+    uint64_t mx_seed = 0;
     // block-scaled FP8 transforms (costa_hip_transform_block_scaled): likewise a scaled job, its lists
     // on block_kernel
     bool blk = false;
@@ -394,7 +398,7 @@ void layout_amax(const elayout& L, void* row_amax, void* col_amax, struct comm* 
 // sub-tiles run by the AMAX instantiations of scaled_kernel and by amax_kernel since the last reset
 int64_t amax_items(bool reset);
 // ---- MX block-scaled transforms (mx_kernels.hip; costa_hip.h, "MX block-scaled transforms") ----
-// One kernel family, mx_kernel<Es, Ed, QUANT>, on the scaled ops and work items of a scaled plan
+// One kernel family, mx_kernel<Es, Ed, QUANT, SR>, on the scaled ops and work items of a scaled plan
 // (build_scaled_work: the same 64 x 64 sub-tile and alignment rule).  A scale tensor as the kernel
 // sees it, in TARGET coordinates (C's; A's descriptor has its axis turned round when the job
 // transposes): byte of (block b, line l) at data[b * block_stride + l * line_stride], `rows` = a
@@ -411,11 +415,20 @@ bool mx_pair(costa_dtype_t src, costa_dtype_t dst);
 // ops: on each packed side the leading dimension and the extent along the side's stored-contiguous
 // dimension are multiples of the packing group
 void check_packed_ops(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const std::vector<costa_scaled_op_t>& ops);
-// a scale tensor on exactly the FP8 sides of the pair; `ceil`: COSTA_MX_CEIL
+// Stochastic rounding (costa_hip.h, "Stochastic rounding in the MX transforms"): the two 32-bit keys
+// of a call's seed, which the SR instances mx_kernel<.., QUANT, SR> take as kernel arguments, and the
+// 24 random bits of target element (i, j) (host only; the kernels compute the same)
+struct mx_sr {
+    uint32_t k0 = 0, k1 = 0;
+};
+mx_sr mx_sr_keys(uint64_t seed);
+uint32_t mx_sr_bits(uint64_t seed, int64_t i, int64_t j);
+// a scale tensor on exactly the FP8 sides of the pair; `ceil`: COSTA_MX_CEIL; `sr` (quantising pairs
+// only): the SR instance with these keys, nullptr: round to nearest even
 void launch_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* d_ops,
                const uint64_t* d_work, const strip_list& l, const char* src_base, char* dst_base,
                const void* d_scalars, const mx_side& a_scales, const mx_side& c_scales, bool ceil,
-               void* stream /* hipStream_t */);
+               void* stream /* hipStream_t */, const mx_sr* sr = nullptr);
 // a descriptor's strides are positive and no two (block, line) of a rows x cols matrix share a byte
 // (throws COSTA_ERR_ARG naming `what`); host only
 void check_mx_scales(const costa_mx_scales_t& s, int64_t rows, int64_t cols, const std::string& what);
@@ -424,10 +437,11 @@ void check_mx_scales(const costa_mx_scales_t& s, int64_t rows, int64_t cols, con
 void check_mx_ops(const std::vector<costa_scaled_op_t>& ops, int axis, int64_t m, int64_t n);
 // costa_hip_execute_tiles_mx: m x n is C's matrix; a_transposed: A's matrix is n x m (target (i, j)
 // is A's (j, i))
+// `seed` (costa_hip_execute_tiles_mx_sr): stochastic rounding with this seed, a quantising pair only
 void execute_tiles_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* ops,
                       int64_t n_ops, const void* src_base, void* dst_base, const void* scalars, int n_slots,
                       const costa_mx_scales_t* a_scales, const costa_mx_scales_t* c_scales, int rounding,
-                      int64_t m, int64_t n, int a_transposed, int device);
+                      int64_t m, int64_t n, int a_transposed, int device, const uint64_t* seed = nullptr);
 // sub-tiles run by mx_kernel since the last reset
 int64_t mx_items(bool reset);
 // ---- block-scaled FP8 transforms (block_kernels.hip; costa_hip.h, "Block-scaled FP8 transforms") ----

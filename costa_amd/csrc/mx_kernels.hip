@@ -13,7 +13,7 @@
 //     E = 255 and NaN everywhere when e == 255, else E = max(e - emax, 0) (CEIL: one more when
 //     amax * pow2(254 - E) > fmax), q = cvt(clamp(v * pow2(254 - E), -fmax, fmax)), SC[block] = E.
 //
-// One family, mx_kernel<Es, Ed, QUANT>, on the strip frame (strip_device.hpp, strip_work.hpp,
+// One family, mx_kernel<Es, Ed, QUANT, SR>, on the strip frame (strip_device.hpp, strip_work.hpp,
 // strip_launch.hpp): 256 threads per 64 x 64 sub-tile, (op << 32) | sub-tile work items.  The planner
 // and costa_hip_execute_tiles_mx guarantee that an op starts on a multiple of 32 of C's block axis,
 // and 64 is a multiple of 32, so a sub-tile holds 2 x 64 whole blocks (the last may be partial at the
@@ -100,6 +100,16 @@
 // kept and NaN -> 0x00, w6 a shift and a select (subnormal codes: an exact int -> fp32 conversion
 // times the step); the gfx950 packed FP6 conversion instructions are not used.  LDS: as for FP4, the
 // staged tile holds fp32 v and `red` fp32 bit patterns, so the bank argument above stands unchanged.
+//
+// Stochastic rounding (costa_hip.h, "Stochastic rounding in the MX transforms"): the template flag SR,
+// valid with QUANT, gives ten more instantiations (f32_e -> Q, Q -> Q for the five codecs) that differ
+// from the plain ones at the two store sites alone: Ed::narrow_sr(v, U) in place of Ed::narrow(v), U
+// the 24 hashed bits of the element's row and column in C's matrix under the call's two 32-bit keys
+// (kernel arguments of the SR instantiations only).  The target coordinates are in registers at both
+// sites -- copy mode (F0 + lf + e, S0 + s), transpose mode after the lane exchange (F0 + f,
+// S0 + sb + e), (i, j) through F_ROWS -- and a lane's 16 elements lie in 4 rows of C either way, so
+// the row's inner fmix32 runs 4 times per lane and the outer one once per element.  Integer VALU code;
+// no LDS access, no barrier and no memory access is added or moved.  No scratch.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -220,11 +230,23 @@ __device__ __forceinline__ uint32_t half_row_max(uint32_t v) {
     return umax(v, dpp_self<0x141>(v));  // row_half_mirror: the other quad
 }
 
-template <typename Es, typename Ed, bool QUANT, bool FULL>
+// ---- stochastic rounding (costa_hip.h, "Stochastic rounding in the MX transforms") ----
+__host__ __device__ __forceinline__ uint32_t fmix32(uint32_t h) {
+    h ^= h >> 16;
+    h *= 0x85EBCA6Bu;
+    h ^= h >> 13;
+    h *= 0xC2B2AE35u;
+    return h ^ (h >> 16);
+}
+// U(seed, i, j) from the row's inner hash r = fmix32(uint32(i) ^ k0)
+__device__ __forceinline__ uint32_t sr_bits(uint32_t r, uint32_t j, uint32_t k1) { return fmix32((r + j) ^ k1) >> 8; }
+
+template <typename Es, typename Ed, bool QUANT, bool SR, bool FULL>
 __device__ __forceinline__ void run_mx(const costa_scaled_op_t& sop, int f0, int s0, int tf_, int ts_,
                                        const char* src_base, char* dst_base, float alpha, float beta,
                                        const mx_side& sa, const mx_side& sc, bool ceil, float* tile,
-                                       uint32_t* red) {
+                                       uint32_t* red, uint32_t k0, uint32_t k1) {
+    static_assert(QUANT || !SR, "stochastic rounding belongs to the quantising instances");
     using Ss = typename Es::st;
     using Sd = typename Ed::st;
     using Q = typename q_of<Ed>::type;
@@ -385,6 +407,15 @@ __device__ __forceinline__ void run_mx(const costa_scaled_op_t& sop, int f0, int
                     for (int e = 0; e < SV; ++e) Eb[b][e] = block_E<Q>(line_max(b, lf + e), ceil);
             }
         }
+        // SR: element (F0 + lf + e, S0 + s) of pass k; its row is F (one inner hash per e, shared by the
+        // passes) or S (one per pass, shared by the strip)
+        [[maybe_unused]] uint32_t rh[SV];
+        if constexpr (SR) {
+            static_assert(SPL == SV, "one inner hash per element or per pass");
+#pragma unroll
+            for (int e = 0; e < SV; ++e)
+                rh[e] = fmix32((frow ? uint32_t(F0) + uint32_t(lf + e) : uint32_t(S0) + uint32_t(c0 + e * SCPP)) ^ k0);
+        }
 #pragma unroll
         for (int k = 0; k < SPL; ++k) {
             const int s = c0 + k * SCPP;
@@ -398,7 +429,11 @@ __device__ __forceinline__ void run_mx(const costa_scaled_op_t& sop, int f0, int
                 } else {
                     v = scale<float>(v, Ed::widen(old[k].e[e]), kind, false, alpha, beta);
                 }
-                o.e[e] = Ed::narrow(v);
+                if constexpr (SR)
+                    o.e[e] = Ed::narrow_sr(v, frow ? sr_bits(rh[e], uint32_t(S0) + uint32_t(s), k1)
+                                                   : sr_bits(rh[k], uint32_t(F0) + uint32_t(lf + e), k1));
+                else
+                    o.e[e] = Ed::narrow(v);
             }
             store_at<Ed>(dst, s * ldd + lf, o, nf_lane, vd);
         }
@@ -417,6 +452,16 @@ __device__ __forceinline__ void run_mx(const costa_scaled_op_t& sop, int f0, int
     }
     __syncthreads();
     store_bytes();
+    // SR: element (F0 + f, S0 + sb + e) of unit k, sb = lane - j for every unit; its row is F (one inner
+    // hash per unit, shared by the strip) or S (one per e, shared by the units)
+    [[maybe_unused]] uint32_t rh[SV];
+    if constexpr (SR) {
+        static_assert(SPS == SV, "one inner hash per unit or per element");
+#pragma unroll
+        for (int e = 0; e < SV; ++e)
+            rh[e] = fmix32((frow ? uint32_t(F0) + uint32_t((wave + SNW * e) * SV + j)
+                                 : uint32_t(S0) + uint32_t(lane - j + e)) ^ k0);
+    }
     float y[SPS][SV];
 #pragma unroll
     for (int k = 0; k < SPS; ++k) {
@@ -443,17 +488,29 @@ __device__ __forceinline__ void run_mx(const costa_scaled_op_t& sop, int f0, int
             } else {
                 v = scale<float>(v, Ed::widen(old[k].e[e]), kind, false, alpha, beta);
             }
-            o.e[e] = Ed::narrow(v);
+            if constexpr (SR)
+                o.e[e] = Ed::narrow_sr(v, frow ? sr_bits(rh[k], uint32_t(S0) + uint32_t(sb + e), k1)
+                                               : sr_bits(rh[e], uint32_t(F0) + uint32_t(f), k1));
+            else
+                o.e[e] = Ed::narrow(v);
         }
         store_at<Ed>(dst, f * ldd + sb, o, n_s, vd);
     }
 }
 
-template <typename Es, typename Ed, bool QUANT>
+// SR instances take the two 32-bit keys of the call's seed behind `ceil`; the others no argument more
+template <typename Es, typename Ed, bool QUANT, bool SR, typename... Keys>
 __global__ __launch_bounds__(SNT) void mx_kernel(const costa_scaled_op_t* __restrict__ ops,
                                                  const uint64_t* __restrict__ work, const char* src_base,
                                                  char* dst_base, const float* __restrict__ scalars, mx_side sa,
-                                                 mx_side sc, int ceil) {
+                                                 mx_side sc, int ceil, Keys... keys) {
+    static_assert(sizeof...(Keys) == (SR ? 2 : 0), "k0, k1 with SR only");
+    uint32_t k0 = 0, k1 = 0;
+    if constexpr (SR) {
+        const uint32_t kk[2] = {keys...};
+        k0 = kk[0];
+        k1 = kk[1];
+    }
     uint32_t* red = nullptr;
     if constexpr (QUANT) {
         __shared__ uint32_t mx_red[MX_RED];
@@ -476,33 +533,53 @@ __global__ __launch_bounds__(SNT) void mx_kernel(const costa_scaled_op_t* __rest
     const float beta = scalars[2 * slot + 1];
     const uint32_t vec_both = COSTA_TILE_VEC_SRC | COSTA_TILE_VEC_DST;
     if (tf == SBF && ts == SBS && (op.flags & vec_both) == vec_both)
-        run_mx<Es, Ed, QUANT, true>(sop, f0, s0, tf, ts, src_base, dst_base, alpha, beta, sa, sc, ceil != 0, tile, red);
+        run_mx<Es, Ed, QUANT, SR, true>(sop, f0, s0, tf, ts, src_base, dst_base, alpha, beta, sa, sc, ceil != 0, tile,
+                                        red, k0, k1);
     else
-        run_mx<Es, Ed, QUANT, false>(sop, f0, s0, tf, ts, src_base, dst_base, alpha, beta, sa, sc, ceil != 0, tile, red);
+        run_mx<Es, Ed, QUANT, SR, false>(sop, f0, s0, tf, ts, src_base, dst_base, alpha, beta, sa, sc, ceil != 0, tile,
+                                         red, k0, k1);
 }
 
 template <typename Es, typename Ed, bool QUANT>
 void launch_inst(const costa_scaled_op_t* d_ops, const uint64_t* d_work, const strip_list& l, const char* src_base,
                  char* dst_base, const void* d_scalars, const mx_side& sa, const mx_side& sc, bool ceil,
-                 hipStream_t stream) {
-    launch_strip<&mx_kernel<Es, Ed, QUANT>, sshape<float>::lds_bytes>("MX", SNT, l, stream, d_ops, d_work, src_base,
-                                                                     dst_base, static_cast<const float*>(d_scalars),
-                                                                     sa, sc, int(ceil));
+                 const mx_sr* sr, hipStream_t stream) {
+    if constexpr (QUANT) {
+        if (sr) {
+            launch_strip<&mx_kernel<Es, Ed, true, true, uint32_t, uint32_t>, sshape<float>::lds_bytes>(
+                "MX", SNT, l, stream, d_ops, d_work, src_base, dst_base, static_cast<const float*>(d_scalars), sa, sc,
+                int(ceil), sr->k0, sr->k1);
+            return;
+        }
+    }
+    launch_strip<&mx_kernel<Es, Ed, QUANT, false>, sshape<float>::lds_bytes>("MX", SNT, l, stream, d_ops, d_work,
+                                                                            src_base, dst_base,
+                                                                            static_cast<const float*>(d_scalars), sa,
+                                                                            sc, int(ceil));
 }
 
 template <typename EQ>  // the codec of the pair's narrow type: q_e<Q>, q4_e or q6_e<T>
 void launch_q(bool src_f, bool dst_f, const costa_scaled_op_t* d_ops, const uint64_t* d_work, const strip_list& l,
               const char* src_base, char* dst_base, const void* d_scalars, const mx_side& sa, const mx_side& sc,
-              bool ceil, hipStream_t s) {
+              bool ceil, const mx_sr* sr, hipStream_t s) {
     if (src_f)
-        launch_inst<f32_e, EQ, true>(d_ops, d_work, l, src_base, dst_base, d_scalars, sa, sc, ceil, s);
+        launch_inst<f32_e, EQ, true>(d_ops, d_work, l, src_base, dst_base, d_scalars, sa, sc, ceil, sr, s);
     else if (dst_f)
-        launch_inst<EQ, f32_e, false>(d_ops, d_work, l, src_base, dst_base, d_scalars, sa, sc, ceil, s);
+        launch_inst<EQ, f32_e, false>(d_ops, d_work, l, src_base, dst_base, d_scalars, sa, sc, ceil, sr, s);
     else
-        launch_inst<EQ, EQ, true>(d_ops, d_work, l, src_base, dst_base, d_scalars, sa, sc, ceil, s);
+        launch_inst<EQ, EQ, true>(d_ops, d_work, l, src_base, dst_base, d_scalars, sa, sc, ceil, sr, s);
 }
 
 }  // namespace
+
+mx_sr mx_sr_keys(uint64_t seed) {
+    return {fmix32(uint32_t(seed) ^ 0x9E3779B9u), fmix32(uint32_t(seed >> 32) ^ 0x85EBCA6Bu)};
+}
+
+uint32_t mx_sr_bits(uint64_t seed, int64_t i, int64_t j) {
+    const mx_sr k = mx_sr_keys(seed);
+    return fmix32((fmix32(uint32_t(i) ^ k.k0) + uint32_t(j)) ^ k.k1) >> 8;
+}
 
 bool mx_pair(costa_dtype_t src, costa_dtype_t dst) {
     return fp8_pair(src, dst) || packed_pair(src, dst);  // FLOAT -> Q, Q -> FLOAT, Q -> Q of one Q
@@ -510,7 +587,8 @@ bool mx_pair(costa_dtype_t src, costa_dtype_t dst) {
 
 void launch_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_scaled_op_t* d_ops,
                const uint64_t* d_work, const strip_list& l, const char* src_base, char* dst_base,
-               const void* d_scalars, const mx_side& a_scales, const mx_side& c_scales, bool ceil, void* stream) {
+               const void* d_scalars, const mx_side& a_scales, const mx_side& c_scales, bool ceil, void* stream,
+               const mx_sr* sr) {
     if (l.n_items <= 0) return;
     if (!mx_pair(src_dtype, dst_dtype))
         throw error(COSTA_ERR_ARG, std::string("costa: no MX kernel for ") + dtype_name(src_dtype) + " -> " +
@@ -518,18 +596,19 @@ void launch_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const costa_sca
     const bool src_f = src_dtype == COSTA_FLOAT, dst_f = dst_dtype == COSTA_FLOAT;
     if ((a_scales.data != nullptr) == src_f || (c_scales.data != nullptr) == dst_f)
         throw error(COSTA_ERR_ARG, "costa: an MX launch needs a scale tensor exactly on its FP8 sides");
+    if (sr && dst_f) throw error(COSTA_ERR_ARG, "costa: stochastic rounding needs a quantising MX launch (c_scales)");
     hipStream_t s = static_cast<hipStream_t>(stream);
     const costa_dtype_t nt = src_f ? dst_dtype : src_dtype;
     if (nt == COSTA_FP8_E4M3)
-        launch_q<q_e<e4m3_t>>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, a_scales, c_scales, ceil, s);
+        launch_q<q_e<e4m3_t>>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, a_scales, c_scales, ceil, sr, s);
     else if (nt == COSTA_FP8_E5M2)
-        launch_q<q_e<e5m2_t>>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, a_scales, c_scales, ceil, s);
+        launch_q<q_e<e5m2_t>>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, a_scales, c_scales, ceil, sr, s);
     else if (nt == COSTA_FP4_E2M1)
-        launch_q<q4_e>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, a_scales, c_scales, ceil, s);
+        launch_q<q4_e>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, a_scales, c_scales, ceil, sr, s);
     else if (nt == COSTA_FP6_E2M3)
-        launch_q<q6_e<e2m3_t>>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, a_scales, c_scales, ceil, s);
+        launch_q<q6_e<e2m3_t>>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, a_scales, c_scales, ceil, sr, s);
     else
-        launch_q<q6_e<e3m2_t>>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, a_scales, c_scales, ceil, s);
+        launch_q<q6_e<e3m2_t>>(src_f, dst_f, d_ops, d_work, l, src_base, dst_base, d_scalars, a_scales, c_scales, ceil, sr, s);
 }
 
 }  // namespace engine

@@ -58,6 +58,7 @@ struct q_e {
     using ct = float;
     static __device__ __forceinline__ float widen(uint8_t b) { return Q::widen(b); }
     static __device__ __forceinline__ uint8_t narrow(float x) { return uint8_t(Q::narrow(x)); }
+    static __device__ __forceinline__ uint8_t narrow_sr(float x, uint32_t U) { return uint8_t(Q::narrow_sr(x, U)); }
 };
 // packed e2m1 (COSTA_FP4_E2M1): a strip<uint8_t> holds 4 unpacked codes, one per byte; two codes
 // share a stored byte (load_strip4 / store_strip4 below)
@@ -66,6 +67,7 @@ struct q4_e {
     using ct = float;
     static __device__ __forceinline__ float widen(uint8_t c) { return e2m1_t::widen(c); }
     static __device__ __forceinline__ uint8_t narrow(float x) { return uint8_t(e2m1_t::narrow(x)); }
+    static __device__ __forceinline__ uint8_t narrow_sr(float x, uint32_t U) { return uint8_t(e2m1_t::narrow_sr(x, U)); }
 };
 // packed FP6 (COSTA_FP6_E2M3 / COSTA_FP6_E3M2; T = e2m3_t / e3m2_t): a strip<uint8_t> holds 4 unpacked
 // codes, one per byte; four codes share three stored bytes (load_strip6 / store_strip6 below)
@@ -75,6 +77,7 @@ struct q6_e {
     using ct = float;
     static __device__ __forceinline__ float widen(uint8_t c) { return T::widen(c); }
     static __device__ __forceinline__ uint8_t narrow(float x) { return uint8_t(T::narrow(x)); }
+    static __device__ __forceinline__ uint8_t narrow_sr(float x, uint32_t U) { return uint8_t(T::narrow_sr(x, U)); }
 };
 template <typename H>  // the FLOAT source of a FLOAT -> H pair: rounded to H first
 struct f32_via {

@@ -355,6 +355,20 @@ __device__ __forceinline__ uint32_t round_finite(uint32_t a) {  // |x| as fp32 b
     a += (uint32_t(BIAS - 127) << 23) + ((1u << (DROP - 1)) - 1u) + ((a >> DROP) & 1u);
     return a >> DROP;
 }
+// Stochastic rounding of the same |x| (costa_hip.h, "Stochastic rounding in the MX transforms"): U is
+// the element's 24 random bits.  In the normal range the top DROP bits of U are added below the kept
+// mantissa and the sum is truncated (a carry moves to the exponent); below the smallest normal |x| is
+// brought to units of the subnormal step with 24 fraction bits -- an exact product with a power of
+// two, below 2^(MB + 24), truncated by the conversion -- and U is added there.  A representable |x|
+// has no dropped bits and keeps its code for every U.
+template <int MB, int BIAS>
+__device__ __forceinline__ uint32_t sr_finite(uint32_t a, uint32_t U) {
+    constexpr int DROP = 23 - MB;
+    constexpr uint32_t MIN_NORMAL = uint32_t(127 - BIAS + 1) << 23;
+    constexpr uint32_t TO_FIXED = uint32_t(127 + 24 + BIAS - 1 + MB) << 23;  // 2^24 / the subnormal step
+    if (a < MIN_NORMAL) return (uint32_t(u2f(a) * u2f(TO_FIXED)) + U) >> 24;
+    return (a + (uint32_t(BIAS - 127) << 23) + (U >> (24 - DROP))) >> DROP;
+}
 struct e4m3_t {  // OCP e4m3fn: bias 7, no infinities, NaN = 0x7F / 0xFF, largest finite 448
     static __device__ __forceinline__ float widen(uint32_t b) {
         // the 7 magnitude bits read as binary16 (4-bit exponent in the low exponent bits) are the
@@ -371,6 +385,12 @@ struct e4m3_t {  // OCP e4m3fn: bias 7, no infinities, NaN = 0x7F / 0xFF, larges
         if (a >= 0x43F00000u) return sign | 0x7Fu;
         return sign | round_finite<3, 7>(a);
     }
+    // (the MX kernels clamp to 448 first: only a NaN reaches the first branch, and 448 + U never carries)
+    static __device__ __forceinline__ uint32_t narrow_sr(float x, uint32_t U) {
+        const uint32_t u = f2u(x), a = u & 0x7FFFFFFFu, sign = (u >> 24) & 0x80u;
+        if (a >= 0x43F00000u) return sign | 0x7Fu;
+        return sign | sr_finite<3, 7>(a, U);
+    }
 };
 struct e5m2_t {  // OCP e5m2: bias 15, the high byte of IEEE binary16
     static __device__ __forceinline__ float widen(uint32_t b) {
@@ -384,6 +404,11 @@ struct e5m2_t {  // OCP e5m2: bias 15, the high byte of IEEE binary16
         // NaN; 61440 = 1.875 * 2^15 and above -> +-inf ((57344, 61440) rounds by itself, the tie to inf)
         if (a >= 0x47700000u) return sign | (a > 0x7F800000u ? 0x7Fu : 0x7Cu);
         return sign | round_finite<2, 15>(a);
+    }
+    static __device__ __forceinline__ uint32_t narrow_sr(float x, uint32_t U) {
+        const uint32_t u = f2u(x), a = u & 0x7FFFFFFFu, sign = (u >> 24) & 0x80u;
+        if (a >= 0x47700000u) return sign | (a > 0x7F800000u ? 0x7Fu : 0x7Cu);
+        return sign | sr_finite<2, 15>(a, U);
     }
 };
 
@@ -406,6 +431,11 @@ struct e2m1_t {
         const uint32_t u = f2u(x), a = u & 0x7FFFFFFFu;
         if (a > 0x7F800000u) return 0u;
         return (u >> 28 & 8u) | round_finite<1, 1>(a);
+    }
+    static __device__ __forceinline__ uint32_t narrow_sr(float x, uint32_t U) {
+        const uint32_t u = f2u(x), a = u & 0x7FFFFFFFu;
+        if (a > 0x7F800000u) return 0u;
+        return (u >> 28 & 8u) | sr_finite<1, 1>(a, U);
     }
 };
 
@@ -430,6 +460,11 @@ struct fp6_t {
         const uint32_t u = f2u(x), a = u & 0x7FFFFFFFu;
         if (a > 0x7F800000u) return 0u;
         return (u >> 26 & 32u) | round_finite<MB, BIAS>(a);
+    }
+    static __device__ __forceinline__ uint32_t narrow_sr(float x, uint32_t U) {
+        const uint32_t u = f2u(x), a = u & 0x7FFFFFFFu;
+        if (a > 0x7F800000u) return 0u;
+        return (u >> 26 & 32u) | sr_finite<MB, BIAS>(a, U);
     }
 };
 using e2m3_t = fp6_t<3, 1>;

@@ -639,6 +639,68 @@ int costa_hip_mx_check_scales(const costa_mx_scales_t* s, int64_t rows, int64_t 
  * Not covered: NVFP4, bf16 / fp16 sides, host-resident packed layouts, batches, masks, in-place
  * calls, extents off the grid of 4 (2 for FP4), swizzled scales, FP6 <-> FP4 / FP8 requantise. */
 
+/* ---- Stochastic rounding in the MX transforms (MI355X-native): seeded, position-keyed ----
+ * The quantise (COSTA_FLOAT -> Q) and requantise (Q -> the same Q) legs of the MX transforms with
+ * stochastic rounding (SR) in place of round-to-nearest-even, for the five Q types: FP8 e4m3 / e5m2,
+ * FP4 e2m1, FP6 e2m3 / e3m2.  The rounding decision of an element depends on three things only: the
+ * call's 64-bit seed, the element's row i and column j in C's matrix (zero-based, the coordinates
+ * c_scales is indexed by) and its value.  The same call therefore gives the same bytes whatever the
+ * layouts, tile cuts, rank count and kernel mode, and on every run.
+ *
+ * Arithmetic.  Steps 1 - 4 of "MX block-scaled transforms" (and of MXFP4 / MXFP6) stay as they are up
+ * to and including the block's E (floor or ceil rule) and t = clamp(v * pow2(254 - E), -fmax, +fmax):
+ * the scale bytes are those of the round-to-nearest call, and a block with E = 255 is stored as there
+ * (NaN codes for FP8, code 0 for FP4 / FP6).  Only cvt changes.
+ *
+ * Random bits (uint32 arithmetic, wrapping):
+ *   fmix32(h): h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16
+ *   k0 = fmix32(uint32(seed)       ^ 0x9E3779B9)
+ *   k1 = fmix32(uint32(seed >> 32) ^ 0x85EBCA6B)
+ *   U(seed, i, j) = fmix32((fmix32(uint32(i) ^ k0) + uint32(j)) ^ k1) >> 8          24 bits
+ * Known answers: fmix32(1) = 0x514E28B7; the keys of seed 0 are (0x92CA2F0E, 0xCB72770F), those of
+ * seed 0x0123456789ABCDEF (0x089887A8, 0x66EA390A); U at (0,0), (1,2), (202,157), (70000,3) is
+ * 0x40042D, 0x0C4B6B, 0x09E145, 0x0982E5 for seed 0x0123456789ABCDEF and 0x2D3D8A, 0xECE447, 0x5F71F2,
+ * 0x40208F for seed 0.
+ *
+ * Conversion.  Let a = |t| and m_0 = 0 < m_1 < .. < m_K = fmax the finite magnitudes of Q in code
+ * order; lo = m_k is the largest magnitude <= a.  If a == lo the magnitude code is k for every U.
+ * Otherwise hi = m_(k+1), T = floor((a - lo) / (hi - lo) * 2^24), and the code is k + 1 when
+ * T + U >= 2^24, else k.  The sign bit of t is always kept (-0 and negatives that round to zero
+ * included).  So P(up) = T / 2^24 exactly.  For a result in Q's normal range T is the dropped mantissa
+ * bits of a shifted to 24 bits: the top 23 - MB bits of U are added below the kept mantissa of a's
+ * fp32 pattern and the sum is truncated (a carry moves into the exponent).  Below Q's smallest normal
+ * it is the same rule on a in units of the subnormal step with 24 fraction bits, truncated.  After
+ * the clamp a <= fmax, so k + 1 never passes fmax (e4m3 never produces 0x7F in a finite block).
+ *
+ * Calls.  The _sr forms take every argument and every check of their plain forms, with the same
+ * messages, and `seed`; `rounding` stays the floor / ceil rule of the scales.  One more check: a
+ * dequantise (C is COSTA_FLOAT, no c_scales) is COSTA_ERR_ARG with "stochastic rounding" in the
+ * message, C and the tensors untouched.  The seed is an argument of the call, not of the plan: the
+ * pair's cached scaled plan serves SR and plain calls of every seed.  Several ranks: unchanged
+ * (COSTA_FLOAT -> Q quantises in UNPACK, Q -> .. sends Q bytes); since U is keyed on C's global
+ * coordinates every rank computes the bytes a single rank would.  costa_hip_mx_items counts the
+ * sub-tiles of SR launches like the others.  Use a fresh seed per call and per tensor.
+ *
+ * Not covered: SR in costa_hip_transform_block_scaled, in the plain and scaled COSTA_FLOAT -> FP8 /
+ * half transforms, the gfx950 stochastic-rounding conversion instructions (their bit selection is
+ * not this definition), bf16 sides. */
+int costa_hip_transform_mx_sr(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                              const void* beta, const costa_mx_scales_t* a_scales,
+                              const costa_mx_scales_t* c_scales, int rounding, uint64_t seed,
+                              costa_comm_t comm);
+int costa_hip_transform_mx_sr_async(costa_layout_t A, costa_layout_t C, char trans, const void* alpha,
+                                    const void* beta, const costa_mx_scales_t* a_scales,
+                                    const costa_mx_scales_t* c_scales, int rounding, uint64_t seed,
+                                    costa_comm_t comm, void* stream);
+int costa_hip_execute_tiles_mx_sr(costa_dtype_t src_dtype, costa_dtype_t dst_dtype,
+                                  const costa_scaled_op_t* ops, int64_t n_ops, const void* src_base,
+                                  void* dst_base, const void* scalars, int n_slots,
+                                  const costa_mx_scales_t* a_scales, const costa_mx_scales_t* c_scales,
+                                  int rounding, int64_t m, int64_t n, int a_transposed, uint64_t seed,
+                                  int device);
+/* U(seed, i, j) above (host only, no GPU) */
+int costa_hip_sr_bits(uint64_t seed, int64_t i, int64_t j, uint32_t* u24);
+
 /* ---- Block-scaled FP8 transforms (fp32 scales) (MI355X-native): 1 x 128 / 128 x 128 blocks, fused ----
  * FP8 data with one fp32 scale per 1 x 128 group of a row, 128 x 1 group of a column or 128 x 128
  * tile ("blockwise" / DeepSeek-style scaling), produced or consumed in the pass that redistributes
