@@ -94,6 +94,10 @@ TRI_OP_DTYPE = np.dtype(TILE_OP_DTYPE.descr + [("diag", "<i4"), ("pad", "<i4")])
 SCALED_F_ROWS = 0x80
 SCALED_OP_DTYPE = np.dtype([("op", TILE_OP_DTYPE), ("row0", "<i4"), ("col0", "<i4")])
 
+# numpy view of costa_dual_op_t (64 bytes): the scaled op of output 1, then output 2's address, leading
+# dimension and store mode (TILE_TRANSPOSE: dst2(f*ldd2 + s), else dst2(s*ldd2 + f))
+DUAL_OP_DTYPE = np.dtype([("s", SCALED_OP_DTYPE), ("dst2", "<u8"), ("ldd2", "<i4"), ("flags2", "<u4")])
+
 
 class CostaError(RuntimeError):
     """Raised when the native library reports an error (status != COSTA_OK)."""
@@ -169,6 +173,12 @@ class ScaledOp(C.Structure):
     """costa_scaled_op_t: source element (f, s) of the op is target element (row0 + f, col0 + s)
     with flag SCALED_F_ROWS, (row0 + s, col0 + f) without."""
     _fields_ = [("op", TileOp), ("row0", C.c_int32), ("col0", C.c_int32)]
+
+
+class DualOp(C.Structure):
+    """costa_dual_op_t: the scaled op of output 1 and where source element (f, s) goes in output 2,
+    whose element has target coordinates (j, i)."""
+    _fields_ = [("s", ScaledOp), ("dst2", C.c_uint64), ("ldd2", C.c_int32), ("flags2", C.c_uint32)]
 
 
 # MX block-scaled transforms (costa_hip.h): the axis a block of 32 runs along, the rounding of E
@@ -339,6 +349,15 @@ def lib():
                                               C.POINTER(MxScales), C.POINTER(MxScales), i, i64, i64, i,
                                               C.c_uint64, i]),
         "costa_hip_sr_bits": (i, [C.c_uint64, i64, i64, C.POINTER(C.c_uint32)]),
+        "costa_hip_transform_mx_dual": (i, [vp, vp, vp, c, vp, C.POINTER(MxScales), C.POINTER(MxScales), i,
+                                            C.POINTER(C.c_uint64), vp]),
+        "costa_hip_transform_mx_dual_async": (i, [vp, vp, vp, c, vp, C.POINTER(MxScales), C.POINTER(MxScales),
+                                                  i, C.POINTER(C.c_uint64), vp, vp]),
+        "costa_hip_execute_tiles_mx_dual": (i, [i, C.POINTER(DualOp), i64, vp, vp, vp, vp, i,
+                                                C.POINTER(MxScales), C.POINTER(MxScales), i, i64, i64,
+                                                C.POINTER(C.c_uint64), i]),
+        "costa_hip_mx_dual_items": (i, [C.POINTER(i64), i]),
+        "costa_hip_plan_export_dual": (i, [vp, vp, vp, c, vp, i, i, i, i, C.POINTER(ScaledPlanInfo), vp, vp]),
         "costa_hip_transform_block_scaled": (i, [vp, vp, c, vp, vp, C.POINTER(BlockScales),
                                                  C.POINTER(BlockScales), i, vp]),
         "costa_hip_transform_block_scaled_async": (i, [vp, vp, c, vp, vp, C.POINTER(BlockScales),
@@ -1205,6 +1224,87 @@ def mx_check_scales(d: MxScales, rows: int, cols: int):
     """The stride rule of a descriptor for a rows x cols matrix (host only): positive strides, no two
     (block, line) entries on one byte."""
     _check(lib().costa_hip_mx_check_scales(C.byref(d), rows, cols))
+
+
+# ------------------------------------------------------------------ dual-output MX quantise
+def _seed_ref(seed):
+    return None if seed is None else C.byref(seed)
+
+
+def transform_mx_dual(A: Layout, Cl: Layout, Ct: Layout, comm: Comm, trans: str = "N", alpha=1.0,
+                      c_scales=None, ct_scales=None, rounding="floor", stochastic_seed=None, stream=None):
+    """Dual-output MX quantise (costa_hip_transform_mx_dual; costa_hip.h, "Dual-output MX quantise"):
+    ``Cl`` = quantised op(A) and ``Ct`` = quantised op(A)^T, its 32-element blocks cut anew, from ONE read
+    of the fp32 ``A``.  The bytes of ``Cl`` / ``c_scales`` are those of ``transform_mx(A, Cl, trans)`` and
+    the bytes of ``Ct`` / ``ct_scales`` those of ``transform_mx(A, Ct)`` with the opposite ``trans``;
+    ``c_scales`` is indexed by Cl's matrix, ``ct_scales`` by Ct's, each with its own axis.  Every tile of
+    the (A, Cl) plan must fall, transposed, inside one block of ``Ct`` that this rank owns (CostaError
+    with "dual layouts").  ``stochastic_seed`` rounds both outputs stochastically, each element keyed on
+    its position in its own output.  ``stream``: stream-ordered, as for transform_mx."""
+    seed = _sr_seed(stochastic_seed)
+    if not all(isinstance(x, Layout) for x in (A, Cl, Ct)):
+        raise CostaError(1, "costa: batches of dual MX layouts are not supported")
+    ab = _scalar_bytes(FLOAT, alpha)
+    args = (A.handle, Cl.handle, Ct.handle, _chr(trans), ab, _mx_arg(c_scales, "c_scales", Cl.shape()),
+            _mx_arg(ct_scales, "ct_scales", Ct.shape()), _mx_rounding(rounding), _seed_ref(seed), comm.handle)
+    if stream is None:
+        _check(lib().costa_hip_transform_mx_dual(*args))
+    else:
+        s = getattr(stream, "cuda_stream", stream) or 0
+        _check(lib().costa_hip_transform_mx_dual_async(*args, C.c_void_p(s)))
+
+
+def execute_tiles_mx_dual(dst_dtype, ops: np.ndarray, scalars: np.ndarray, m: int, n: int, src_base=0,
+                          dst_base=0, dst2_base=0, c_scales=None, ct_scales=None, rounding="floor",
+                          device: int = 0, stochastic_seed=None):
+    """Run a list of dual ops (DUAL_OP_DTYPE) in one launch of the dual MX kernel: FLOAT -> ``dst_dtype``
+    into output 1 (``m`` x ``n``, ``c_scales``) and output 2 (``n`` x ``m``, ``ct_scales``); fp32
+    ``scalars`` (costa_hip_execute_tiles_mx_dual)."""
+    seed = _sr_seed(stochastic_seed)
+    ops = np.ascontiguousarray(ops, dtype=DUAL_OP_DTYPE)
+    sc = np.ascontiguousarray(scalars, dtype=np.float32).reshape(-1)
+    assert sc.size % 2 == 0
+    _check(lib().costa_hip_execute_tiles_mx_dual(
+        element_code(dst_dtype), ops.ctypes.data_as(C.POINTER(DualOp)), ops.size, C.c_void_p(_ptr(src_base)),
+        C.c_void_p(_ptr(dst_base)), C.c_void_p(_ptr(dst2_base)), sc.ctypes.data, sc.size // 2,
+        _mx_arg(c_scales, "c_scales"), _mx_arg(ct_scales, "ct_scales"), _mx_rounding(rounding), m, n,
+        _seed_ref(seed), device))
+
+
+def mx_dual_items(reset: bool = False) -> int:
+    """Sub-tiles run by the dual MX kernel since the last reset (mx_items does not count them)."""
+    v = C.c_int64(0)
+    _check(lib().costa_hip_mx_dual_items(C.byref(v), int(reset)))
+    return v.value
+
+
+@dataclass
+class DualPlan:
+    local_dual: np.ndarray   # DUAL_OP_DTYPE: every tile that stays on the rank, with its twin in Ct
+    unpack_dual: np.ndarray  # DUAL_OP_DTYPE: every tile read from the receive package, likewise
+    send_elems: int = 0
+    recv_elems: int = 0
+    local_elems: int = 0
+
+
+def plan_export_dual(A: Layout, Cl: Layout, Ct: Layout, rank: int, nranks: int, trans: str = "N", alpha=1.0,
+                     c_axis=None, ct_axis=None) -> DualPlan:
+    """The LOCAL and UNPACK dual ops of `rank` for transform_mx_dual (host planner, never touches a GPU),
+    in the order of plan_export_scaled(A, Cl); CostaError with "dual layouts" where a tile has no twin
+    in ``Ct``.  With ``c_axis`` / ``ct_axis`` the "MX block" rule of that output is checked too."""
+    if not all(isinstance(x, Layout) for x in (A, Cl, Ct)):
+        raise CostaError(1, "costa: batches of dual MX layouts are not supported")
+    ab = _scalar_bytes(FLOAT, alpha)
+    info = ScaledPlanInfo()
+    ax = [-1 if a is None else _mx_axis(a) for a in (c_axis, ct_axis)]
+    args = (A.handle, Cl.handle, Ct.handle, _chr(trans), ab, ax[0], ax[1], rank, nranks, C.byref(info))
+    L = lib()
+    _check(L.costa_hip_plan_export_dual(*args, None, None))
+    ld = np.zeros(info.n_local_scaled, DUAL_OP_DTYPE)
+    ud = np.zeros(info.n_unpack_scaled, DUAL_OP_DTYPE)
+    _check(L.costa_hip_plan_export_dual(*args, ld.ctypes.data, ud.ctypes.data))
+    b = info.base
+    return DualPlan(ld, ud, b.send_elems, b.recv_elems, b.local_elems)
 
 
 # ------------------------------------------------------------------ block-scaled FP8 transforms

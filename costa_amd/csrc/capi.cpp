@@ -782,6 +782,129 @@ int costa_hip_mx_items(int64_t* items, int reset) {
     });
 }
 
+namespace {
+// the one job of costa_hip_transform_mx_dual: the MX job of (A, C, trans) with beta = 0, plus the second
+// target and its descriptor
+std::vector<job> make_dual_job(costa_layout_t A, costa_layout_t C, costa_layout_t Ct, char trans, const void* alpha,
+                               const costa_mx_scales_t* c_scales, const costa_mx_scales_t* ct_scales, int rounding,
+                               const uint64_t* sr_seed) {
+    static_assert(sizeof(costa_dual_op_t) == 64, "dual op size");
+    if (!Ct) throw costa::engine::error(COSTA_ERR_ARG, "costa: null layout");
+    check_handles(1, &A, &C);
+    const float beta = 0.0f;
+    // (A's type is checked by the call itself: a non-FLOAT A must not reach the scaled job's pair table)
+    if (A->e.dtype != COSTA_FLOAT)
+        throw costa::engine::error(COSTA_ERR_ARG,
+                                   std::string("costa_hip_transform_mx_dual: A must be COSTA_FLOAT, not ") +
+                                       costa::engine::dtype_name(A->e.dtype) +
+                                       " (no dual MX transform from a quantised or half source)");
+    if (C->e.dtype != Ct->e.dtype || C->e.dtype == COSTA_FLOAT || !costa::engine::mx_pair(COSTA_FLOAT, C->e.dtype))
+        throw costa::engine::error(COSTA_ERR_ARG,
+                                   std::string("costa_hip_transform_mx_dual: no dual MX transform for FLOAT -> ") +
+                                       costa::engine::dtype_name(C->e.dtype) + " / " +
+                                       costa::engine::dtype_name(Ct->e.dtype) +
+                                       " (C and Ct of one type: FP8_E4M3, FP8_E5M2, FP4_E2M1, FP6_E2M3 or FP6_E3M2)");
+    auto jobs = make_mx_job(A, C, trans, alpha, &beta, nullptr, c_scales, rounding);
+    jobs[0].Ct = &Ct->e;
+    if (ct_scales && ct_scales->data) jobs[0].ct_scales = *ct_scales;
+    if (sr_seed) {
+        jobs[0].mx_sr = true;
+        jobs[0].mx_seed = *sr_seed;
+    }
+    return jobs;
+}
+}  // namespace
+
+int costa_hip_transform_mx_dual(costa_layout_t A, costa_layout_t C, costa_layout_t Ct, char trans,
+                                const void* alpha, const costa_mx_scales_t* c_scales,
+                                const costa_mx_scales_t* ct_scales, int rounding, const uint64_t* sr_seed,
+                                costa_comm_t comm) {
+    return gpu_guarded([&] {
+        if (!comm || !alpha) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::transform(make_dual_job(A, C, Ct, trans, alpha, c_scales, ct_scales, rounding, sr_seed), comm->c);
+    });
+}
+
+int costa_hip_transform_mx_dual_async(costa_layout_t A, costa_layout_t C, costa_layout_t Ct, char trans,
+                                      const void* alpha, const costa_mx_scales_t* c_scales,
+                                      const costa_mx_scales_t* ct_scales, int rounding,
+                                      const uint64_t* sr_seed, costa_comm_t comm, void* stream) {
+    return gpu_guarded([&] {
+        if (!comm || !alpha) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::transform(make_dual_job(A, C, Ct, trans, alpha, c_scales, ct_scales, rounding, sr_seed), comm->c,
+                                 stream, true);
+    });
+}
+
+int costa_hip_execute_tiles_mx_dual(costa_dtype_t dst_dtype, const costa_dual_op_t* ops, int64_t n_ops,
+                                    const void* src_base, void* dst_base, void* dst2_base,
+                                    const void* scalars, int n_slots, const costa_mx_scales_t* c_scales,
+                                    const costa_mx_scales_t* ct_scales, int rounding, int64_t m, int64_t n,
+                                    const uint64_t* sr_seed, int device) {
+    return gpu_guarded([&] {
+        if (n_ops < 0 || (n_ops > 0 && (!ops || !scalars)))
+            throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        costa::engine::execute_tiles_mx_dual(dst_dtype, ops, n_ops, src_base, dst_base, dst2_base, scalars, n_slots,
+                                             c_scales, ct_scales, rounding, m, n, sr_seed, device);
+    });
+}
+
+int costa_hip_mx_dual_items(int64_t* items, int reset) {
+    return guarded([&] {
+        if (!items) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        *items = costa::engine::mx_dual_items(reset != 0);
+    });
+}
+
+int costa_hip_plan_export_dual(costa_layout_t A, costa_layout_t C, costa_layout_t Ct, char trans,
+                               const void* alpha, int c_axis, int ct_axis, int rank, int nranks,
+                               costa_scaled_plan_info_t* info, costa_dual_op_t* local_dual,
+                               costa_dual_op_t* unpack_dual) {
+    return guarded([&] {
+        if (!info || !alpha) throw costa::engine::error(COSTA_ERR_ARG, "null argument");
+        if (nranks < 1 || rank < 0 || rank >= nranks)
+            throw costa::engine::error(COSTA_ERR_ARG, "bad rank/size");
+        for (int ax : {c_axis, ct_axis})
+            if (ax != -1 && ax != COSTA_MX_ROWS && ax != COSTA_MX_COLS)
+                throw costa::engine::error(COSTA_ERR_ARG, "costa_hip_plan_export_dual: an axis must be COSTA_MX_ROWS, "
+                                                          "COSTA_MX_COLS or -1");
+        auto jobs = make_dual_job(A, C, Ct, trans, alpha, nullptr, nullptr, COSTA_MX_FLOOR, nullptr);
+        int64_t m = 0, n = 0, r = 0, k = 0;
+        if (!C->e.rows_split.empty() && !C->e.cols_split.empty()) {
+            m = int64_t(C->e.rows_split.back()) - C->e.rows_split.front();
+            n = int64_t(C->e.cols_split.back()) - C->e.cols_split.front();
+        }
+        if (!Ct->e.rows_split.empty() && !Ct->e.cols_split.empty()) {
+            r = int64_t(Ct->e.rows_split.back()) - Ct->e.rows_split.front();
+            k = int64_t(Ct->e.cols_split.back()) - Ct->e.cols_split.front();
+        }
+        if (Ct == A || Ct == C)
+            throw costa::engine::error(COSTA_ERR_ARG, "costa_hip_plan_export_dual: Ct must be a layout of its own");
+        if (r != n || k != m)
+            throw costa::engine::error(COSTA_ERR_ARG,
+                                       "costa_hip_plan_export_dual: dual layouts: Ct describes a " + std::to_string(r) +
+                                           " x " + std::to_string(k) + " matrix, the transpose of C's " +
+                                           std::to_string(m) + " x " + std::to_string(n) + " is " + std::to_string(n) +
+                                           " x " + std::to_string(m));
+        auto p = costa::engine::make_plan(jobs, rank, nranks);
+        const auto ld = costa::engine::dual_twins(p->local_scaled, Ct->e, rank);
+        const auto ud = costa::engine::dual_twins(p->unpack_scaled, Ct->e, rank);
+        costa::engine::check_dual_ops(C->e.dtype, ld, c_axis, ct_axis, m, n);
+        costa::engine::check_dual_ops(C->e.dtype, ud, c_axis, ct_axis, m, n);
+        *info = costa_scaled_plan_info_t{};
+        info->base.n_pack = int64_t(p->pack_ops.size());
+        info->base.send_elems = p->send_elems;
+        info->base.recv_elems = p->recv_elems;
+        info->base.local_elems = p->local_elems;
+        info->base.n_ranks = nranks;
+        info->base.n_slots = int32_t(p->slots.size());
+        info->n_local_scaled = int64_t(ld.size());
+        info->n_unpack_scaled = int64_t(ud.size());
+        if (local_dual && !ld.empty()) std::memcpy(local_dual, ld.data(), ld.size() * sizeof(ld[0]));
+        if (unpack_dual && !ud.empty()) std::memcpy(unpack_dual, ud.data(), ud.size() * sizeof(ud[0]));
+    });
+}
+
 int costa_hip_mx_check_ops(const costa_scaled_op_t* ops, int64_t n_ops, int axis, int64_t m, int64_t n) {
     return guarded([&] {
         if (n_ops < 0 || (n_ops > 0 && !ops)) throw costa::engine::error(COSTA_ERR_ARG, "null argument");

@@ -1848,8 +1848,13 @@ struct phase_lists {
     // the 128 x 128 regions of block_kernel's quantising form over scaled.ops (plans whose C holds FP8)
     dbuf block_work;
     strip_list block_items;
+    // the dual ops of a dual-output MX plan (mx_dual_kernels.hip): the scaled ops with their twins in Ct,
+    // in place of `scaled`
+    dev_list dual;
+    strip_list dual_items;
     bool empty() const {
-        return !split.n_items() && !convert.n_items && !tri_items.n_items && !scaled_items.n_items;
+        return !split.n_items() && !convert.n_items && !tri_items.n_items && !scaled_items.n_items &&
+               !dual_items.n_items;
     }
 };
 
@@ -1866,6 +1871,10 @@ struct cached_plan {
     int mx_rule[2] = {0, 0};
     // ... and of block-scaled FP8 calls per block shape of c_scales ((1,128), (128,1), (128,128))
     int blk_rule[3] = {0, 0, 0};
+    // a dual-output MX plan (job::Ct): every LOCAL / UNPACK op with its twin, in the plan's order (the twin
+    // rule held when they were built), and the block rule of both outputs per (c_scales, ct_scales) axis
+    std::vector<costa_dual_op_t> local_dual, unpack_dual;
+    int dual_rule[2][2] = {{0, 0}, {0, 0}};
     struct xround {  // one exchange round: its pack ops (by their first element) and unpack
                      // ops (by their last element)
         phase_lists pack, unpack;
@@ -2085,7 +2094,8 @@ struct host_lists {
     std::vector<costa_tile_op_t> tiles;
     std::vector<costa_tri_op_t> tri;
     std::vector<costa_scaled_op_t> scaled;
-    std::vector<uint64_t> tiles_work, tri_work, scaled_work, block_work;
+    std::vector<costa_dual_op_t> dual;
+    std::vector<uint64_t> tiles_work, tri_work, scaled_work, block_work, dual_work;
     // the destination-block groups of long lists are built on the GPU and stay there
     device_section sec;
     host_lists(phase_lists& ph, int device, hipStream_t s) : into(&ph) {
@@ -2098,7 +2108,7 @@ struct host_lists {
 // buffers): the counts and flags into *h.into, the lists into h.
 void build_phase(const plan& p, list_kind kind, bool masked, const std::vector<costa_tile_op_t>& tiles,
                  const std::vector<costa_tri_op_t>& tri, const std::vector<costa_scaled_op_t>& scaled,
-                 host_lists& h) {
+                 host_lists& h, const std::vector<costa_dual_op_t>* dual = nullptr) {
     phase_lists& ph = *h.into;
     const dtype_pair t = phase_dtypes(p, kind);
     // (a pack list is launched as one that neither transposes nor reads C)
@@ -2128,6 +2138,10 @@ void build_phase(const plan& p, list_kind kind, bool masked, const std::vector<c
         return !e || std::atoi(e) != 0;
     }();
     const bool by_dst = kind == list_local && local_by_dst;
+    if (dual) {  // a dual-output MX plan: the same ops with their twins, on mx_dual_kernel alone
+        ph.dual_items = build_dual_work(t.dst, *dual, 0, 0, 0, h.dual, h.dual_work, by_dst);
+        return;
+    }
     ph.scaled_items = build_scaled_work(t.src, t.dst, scaled, 0, 0, h.scaled, h.scaled_work, by_dst);
     // (a scaled plan into FP8 also serves block-scaled calls: the regions of its quantising kernel)
     if (block_pair(p.src_dtype, p.dtype) && dtype_is_fp8(p.dtype)) {
@@ -2149,6 +2163,10 @@ void upload_phase(const host_lists& h, hipStream_t s) {
         ph.scaled.work.upload(h.scaled_work, s);
     }
     if (ph.block_items.n_items) ph.block_work.upload(h.block_work, s);
+    if (ph.dual_items.n_items) {
+        ph.dual.ops.upload(h.dual, s);
+        ph.dual.work.upload(h.dual_work, s);
+    }
 }
 
 // the ops of each of R exchange rounds, in list order
@@ -2162,8 +2180,15 @@ std::vector<std::vector<Op>> by_round(const std::vector<Op>& ops, const std::vec
 // Every phase of cp's plan: LOCAL, and PACK and UNPACK of each exchange round.  Pack ops go to the
 // round of their first element (every element a round sends is packed by then), unpack ops to the
 // round of their last (every element they read has arrived).
-std::vector<host_lists> build_lists(cached_plan& cp, comm* c, hipStream_t s, bool masked) {
+std::vector<host_lists> build_lists(cached_plan& cp, comm* c, hipStream_t s, bool masked,
+                                    const elayout* Ct = nullptr) {
     const plan& p = *cp.p;
+    if (Ct) {  // a dual-output MX plan: the twin of every scaled op, or the "dual layouts" error
+        cp.local_dual = dual_twins(p.local_scaled, *Ct, p.rank);
+        cp.unpack_dual = dual_twins(p.unpack_scaled, *Ct, p.rank);
+        check_dual_ops(p.dtype, cp.local_dual, -1, -1, 0, 0);  // (the packed rules on Ct's side)
+        check_dual_ops(p.dtype, cp.unpack_dual, -1, -1, 0, 0);
+    }
     if (p.packed() && (!p.local_ops.empty() || !p.unpack_ops.empty()))
         throw error(COSTA_ERR_INTERNAL, "costa: an FP4 / FP6 plan with ordinary LOCAL / UNPACK ops");
     const int R = c->exchanges() ? exchange_rounds() : 1;
@@ -2174,16 +2199,20 @@ std::vector<host_lists> build_lists(cached_plan& cp, comm* c, hipStream_t s, boo
     const auto pack = by_round(p.pack_ops, pr, R), unpack = by_round(p.unpack_ops, ur, R);
     const auto unpack_tri = by_round(p.unpack_tri, tr, R);
     const auto unpack_scaled = by_round(p.unpack_scaled, sr, R);
+    std::vector<std::vector<costa_dual_op_t>> unpack_dual;
+    if (Ct) unpack_dual = by_round(cp.unpack_dual, sr, R);
     std::vector<host_lists> h;
     h.reserve(1 + 2 * size_t(R));
     h.emplace_back(cp.local, cp.device, s);
-    build_phase(p, list_local, masked, p.local_ops, p.local_tri, p.local_scaled, h.back());
+    build_phase(p, list_local, masked, p.local_ops, p.local_tri, p.local_scaled, h.back(),
+                Ct ? &cp.local_dual : nullptr);
     for (size_t r = 0; r < size_t(R); ++r) {
         cp.rounds.push_back(std::make_unique<cached_plan::xround>());
         h.emplace_back(cp.rounds.back()->pack, cp.device, s);
         build_phase(p, list_pack, false, pack[r], {}, {}, h.back());
         h.emplace_back(cp.rounds.back()->unpack, cp.device, s);
-        build_phase(p, list_unpack, false, unpack[r], unpack_tri[r], unpack_scaled[r], h.back());
+        build_phase(p, list_unpack, false, unpack[r], unpack_tri[r], unpack_scaled[r], h.back(),
+                    Ct ? &unpack_dual[r] : nullptr);
     }
     return h;
 }
@@ -2206,7 +2235,9 @@ std::vector<uint64_t> plan_key(const std::vector<job>& jobs, const comm* c) {
         // ... and whether the ops carry target coordinates (a scaled transform; its vectors are
         // arguments of the call, not of the plan)
         key.push_back(uint64_t(uint8_t(std::toupper(static_cast<unsigned char>(j.uplo)))) << 32 |
-                      uint64_t(j.scaled) << 40 | uint64_t(uint32_t(j.k)));
+                      uint64_t(j.scaled) << 40 | uint64_t(j.Ct != nullptr) << 41 | uint64_t(uint32_t(j.k)));
+        // a dual-output MX call: its lists hold Ct's addresses
+        if (j.Ct) key_layout(key, *j.Ct);
     }
     return key;
 }
@@ -2400,7 +2431,7 @@ std::unique_ptr<cached_plan> build_cached_plan(const std::vector<job>& jobs, com
     const double t_plan = now_ms() - t0 - t_resid;
     g_stats.plan_ms += t_plan;
     if (cp->staged) staged_copies(*cp, st, masked);
-    const std::vector<host_lists> lists = build_lists(*cp, c, dc.main, masked);
+    const std::vector<host_lists> lists = build_lists(*cp, c, dc.main, masked, st.jobs[0].Ct);
     const double t_work = now_ms() - t0 - t_resid - t_plan;
     for (const host_lists& h : lists) upload_phase(h, dc.main);
     HIP_CHECK(hipStreamSynchronize(dc.main));  // the host lists are temporaries
@@ -2470,6 +2501,7 @@ int64_t g_scaled_items = 0;  // sub-tiles run by scaled_kernel (kept beside cost
 int64_t g_amax_items = 0;    // ... by its AMAX instantiations and by amax_kernel (likewise)
 int64_t g_mx_items = 0;      // ... by mx_kernel (likewise; not counted as scaled items)
 int64_t g_blk_items = 0;     // sub-tiles and regions run by block_kernel (likewise)
+int64_t g_mx_dual_items = 0; // sub-tiles run by mx_dual_kernel (likewise; not counted as MX items)
 
 struct phase_timer {
     device_ctx& dc;
@@ -2585,7 +2617,7 @@ void issue_exchange(comm* c, const plan& p, char* sb, char* rb, hipStream_t s, i
 // kernel family the plan's scaled LOCAL / UNPACK lists run on (launch_phase) and the item counter they
 // add to (count_phase) follow from the tag: a new scheme is a tag with its payload here and a case in
 // each of those two.
-enum class scale_scheme { none, vectors, mx, block };
+enum class scale_scheme { none, vectors, mx, block, mx_dual };
 struct scaled_args {
     scale_scheme scheme = scale_scheme::none;
     struct {  // vectors (costa_hip_transform_scaled, _amax): scaled_kernel reads the scales, updates the amax outputs
@@ -2594,6 +2626,8 @@ struct scaled_args {
     } vec;
     struct {  // mx (costa_hip_transform_mx): mx_kernel, its tensors in target coordinates
         mx_side a_scales, c_scales;
+        mx_side ct_scales;  // costa_hip_transform_mx_dual: output 2's tensor, in Ct's coordinates; the
+                            // plan's dual lists run on mx_dual_kernel
         bool ceil = false;
         bool sr = false;  // costa_hip_transform_mx_sr: the SR instances, with the keys of the call's seed
         mx_sr keys;
@@ -2739,6 +2773,59 @@ scaled_args mx_args(const job& j, cached_plan& cp) {
     return sv;
 }
 
+// The argument checks of costa_hip_transform_mx_dual that need no plan and no device (costa_hip.h,
+// "Dual-output MX quantise", "Other checks")
+void check_dual_job(const job& j) {
+    const std::string who = "costa_hip_transform_mx_dual: ";
+    const costa_dtype_t a = j.A->dtype, c = j.C->dtype, ct = j.Ct->dtype;
+    if (a != COSTA_FLOAT)
+        throw error(COSTA_ERR_ARG, who + "A must be COSTA_FLOAT, not " + dtype_name(a) +
+                                       " (no dual MX transform from a quantised or half source)");
+    if (c != ct || c == COSTA_FLOAT || !mx_pair(COSTA_FLOAT, c))
+        throw error(COSTA_ERR_ARG, who + "no dual MX transform for FLOAT -> " + dtype_name(c) + " / " + dtype_name(ct) +
+                                       " (C and Ct of one type: FP8_E4M3, FP8_E5M2, FP4_E2M1, FP6_E2M3 or FP6_E3M2)");
+    if (j.uplo != 'A') throw error(COSTA_ERR_ARG, who + "no triangular mask");
+    if (j.A == j.C) throw error(COSTA_ERR_ARG, who + "in-place calls are not supported");
+    if (j.Ct == j.A || j.Ct == j.C)
+        throw error(COSTA_ERR_ARG, who + "Ct must be a layout of its own, not the same object as " +
+                                       (j.Ct == j.A ? "A" : "C"));
+    int64_t m, n, r, k;
+    layout_extent(*j.C, m, n);
+    layout_extent(*j.Ct, r, k);
+    if (r != n || k != m)
+        throw error(COSTA_ERR_ARG, who + "dual layouts: Ct describes a " + std::to_string(r) + " x " + std::to_string(k) +
+                                       " matrix, the transpose of C's " + std::to_string(m) + " x " + std::to_string(n) +
+                                       " is " + std::to_string(n) + " x " + std::to_string(m));
+    if (!j.c_scales.data) throw error(COSTA_ERR_ARG, who + "c_scales is required");
+    if (!j.ct_scales.data) throw error(COSTA_ERR_ARG, who + "ct_scales is required");
+    if (j.mx_rounding != COSTA_MX_FLOOR && j.mx_rounding != COSTA_MX_CEIL)
+        throw error(COSTA_ERR_ARG, who + "rounding must be COSTA_MX_FLOOR or COSTA_MX_CEIL");
+    check_mx_scales(j.c_scales, m, n, who + "c_scales");
+    check_mx_scales(j.ct_scales, n, m, who + "ct_scales");
+}
+
+// ... and those that need the plan and the device; -> the call's arguments
+scaled_args dual_args(const job& j, cached_plan& cp) {
+    scale_tensors_on_device("costa_hip_transform_mx_dual", j.c_scales.data, j.ct_scales.data);
+    int& rule = cp.dual_rule[j.c_scales.axis == COSTA_MX_ROWS ? 0 : 1][j.ct_scales.axis == COSTA_MX_ROWS ? 0 : 1];
+    if (rule <= 0) {  // (a failing plan is checked again: the error carries the op)
+        int64_t m, n;
+        layout_extent(*j.C, m, n);
+        rule = -1;
+        check_dual_ops(cp.p->dtype, cp.local_dual, j.c_scales.axis, j.ct_scales.axis, m, n);
+        check_dual_ops(cp.p->dtype, cp.unpack_dual, j.c_scales.axis, j.ct_scales.axis, m, n);
+        rule = 1;
+    }
+    scaled_args sv;
+    sv.scheme = scale_scheme::mx_dual;
+    sv.mx.c_scales = mx_side_of(j.c_scales, false);
+    sv.mx.ct_scales = mx_side_of(j.ct_scales, false);
+    sv.mx.ceil = j.mx_rounding == COSTA_MX_CEIL;
+    sv.mx.sr = j.mx_sr;
+    if (j.mx_sr) sv.mx.keys = mx_sr_keys(j.mx_seed);
+    return sv;
+}
+
 scaled_args block_args(const job& j, cached_plan& cp) {
     scale_tensors_on_device("costa_hip_transform_block_scaled", j.a_blocks.data, j.c_blocks.data);
     if (j.c_blocks.data)
@@ -2807,6 +2894,14 @@ void launch_phase(const cached_plan& cp, const phase_lists& ph, list_kind kind, 
                               sv.vec.row_scale, sv.vec.col_scale, sv.vec.row_amax, sv.vec.col_amax, s);
             }
         });
+    if (ph.dual_items.n_items)  // the list of a dual-output MX plan: both outputs in one launch
+        launch(id, [&] {
+            if (sv.scheme != scale_scheme::mx_dual)
+                throw error(COSTA_ERR_INTERNAL, "costa: a dual-output plan outside costa_hip_transform_mx_dual");
+            launch_mx_dual(t.dst, ph.dual.list<costa_dual_op_t>(), ph.dual.items(), ph.dual_items, src_base, dst_base,
+                           nullptr, scal, sv.mx.c_scales, sv.mx.ct_scales, sv.mx.ceil, s,
+                           sv.mx.sr ? &sv.mx.keys : nullptr);
+        });
 }
 
 // the statistics of those launches
@@ -2837,6 +2932,7 @@ void count_phase(const plan& p, const phase_lists& ph, list_kind kind, const sca
     default: g_scaled_items += n;
     }
     if (sv.amax()) g_amax_items += n;
+    g_mx_dual_items += ph.dual_items.n_items;
 }
 
 
@@ -2906,12 +3002,19 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
             if (!layout_on_device(*j.A) || !layout_on_device(*j.C))
                 throw error(COSTA_ERR_ARG, "costa: an emulated communicator needs device-resident layouts");
     }
-    const bool mx = jobs.size() == 1 && jobs[0].mx;
-    if (!mx && any_packed(jobs)) {  // (before any residency or staging question)
+    const bool dual = jobs.size() == 1 && jobs[0].Ct;
+    const bool mx = jobs.size() == 1 && jobs[0].mx && !dual;
+    if (!mx && !dual && any_packed(jobs)) {  // (before any residency or staging question)
         costa_dtype_t a, b;
         check_jobs(jobs, c->size, a, b);
     }
     if (mx) check_mx_job(jobs[0]);  // pair, descriptors, beta, strides: before the plan
+    if (dual) {
+        check_dual_job(jobs[0]);
+        for (const elayout* L : {jobs[0].A, jobs[0].C, jobs[0].Ct})
+            if (!layout_on_device(*L))
+                throw error(COSTA_ERR_ARG, "costa_hip_transform_mx_dual: A, C and Ct must be device-resident layouts");
+    }
     const bool blk = !jobs.empty() && jobs[0].blk;
     if (blk) check_block_job(jobs[0]);
     cached_plan& cp = *get_plan(jobs, c, dc);
@@ -2920,6 +3023,8 @@ void transform(const std::vector<job>& jobs, comm* c, void* user_stream, bool as
     scaled_args sv;
     if (blk) {
         sv = block_args(jobs[0], cp);
+    } else if (dual) {
+        sv = dual_args(jobs[0], cp);
     } else if (mx) {
         sv = mx_args(jobs[0], cp);
     } else if (p.scaled) {
@@ -3451,6 +3556,158 @@ int64_t mx_items(bool reset) {
     std::lock_guard<std::recursive_mutex> lk(g_mutex);
     const int64_t v = g_mx_items;
     if (reset) g_mx_items = 0;
+    return v;
+}
+
+// ---------------------------------------------------------------- dual-output MX quantise
+costa_scaled_op_t dual_twin_op(const costa_dual_op_t& t) {
+    costa_scaled_op_t o = t.s;
+    o.op.dst = t.dst2;
+    o.op.ldd = t.ldd2;
+    o.op.flags = ((t.s.op.flags & ~uint32_t(COSTA_TILE_TRANSPOSE | COSTA_TILE_VEC_DST)) ^ COSTA_SCALED_F_ROWS) |
+                 (t.flags2 & (COSTA_TILE_TRANSPOSE | COSTA_TILE_VEC_DST));
+    o.row0 = t.s.col0;
+    o.col0 = t.s.row0;
+    return o;
+}
+
+std::vector<costa_dual_op_t> dual_twins(const std::vector<costa_scaled_op_t>& ops, const elayout& Ct, int rank) {
+    std::vector<costa_dual_op_t> out;
+    out.reserve(ops.size());
+    if (ops.empty()) return out;
+    const esize E = elem_size(Ct.dtype);
+    const int g = std::max(1, packed_group(Ct.dtype));
+    const bool ct_cm = Ct.ordering == 'C' || Ct.ordering == 'c';
+    const int nbc = Ct.nbc();
+    // Ct's local blocks by the grid cell of their first element
+    std::unordered_map<int64_t, std::vector<const eblock*>> by_cell;
+    auto cell_of = [](const std::vector<int>& split, int at) {
+        return int(std::upper_bound(split.begin(), split.end(), at) - split.begin()) - 1;
+    };
+    for (const eblock& b : Ct.blocks) {
+        if (!b.rows.non_empty() || !b.cols.non_empty()) continue;
+        by_cell[int64_t(cell_of(Ct.rows_split, b.rows.start)) * nbc + cell_of(Ct.cols_split, b.cols.start)].push_back(&b);
+    }
+    const int rb = Ct.rows_split.empty() ? 0 : Ct.rows_split.front(), cb = Ct.cols_split.empty() ? 0 : Ct.cols_split.front();
+    for (const costa_scaled_op_t& t : ops) {
+        costa_dual_op_t d{};
+        d.s = t;
+        if (t.op.nf <= 0 || t.op.ns <= 0) {
+            out.push_back(d);
+            continue;
+        }
+        const bool frow = t.op.flags & COSTA_SCALED_F_ROWS;
+        const int nr = frow ? t.op.nf : t.op.ns, nc = frow ? t.op.ns : t.op.nf;  // the op's rows x columns of C
+        // rows [col0, col0 + nc) x columns [row0, row0 + nr) of Ct, in Ct's own coordinates
+        const interval rows(rb + t.col0, rb + t.col0 + nc), cols(cb + t.row0, cb + t.row0 + nr);
+        auto refuse = [&](const std::string& why) {
+            return error(COSTA_ERR_ARG,
+                         "costa_hip_transform_mx_dual: dual layouts: the tile of C's rows " + std::to_string(t.row0) +
+                             " .. " + std::to_string(t.row0 + nr) + ", columns " + std::to_string(t.col0) + " .. " +
+                             std::to_string(t.col0 + nc) + " needs rows " + std::to_string(t.col0) + " .. " +
+                             std::to_string(t.col0 + nc) + " x columns " + std::to_string(t.row0) + " .. " +
+                             std::to_string(t.row0 + nr) + " of Ct " + why +
+                             " (Ct: C's split points and owners transposed, or coarser blocks)");
+        };
+        const int bi = cell_of(Ct.rows_split, rows.start), bj = cell_of(Ct.cols_split, cols.start);
+        if (bi < 0 || bj < 0 || bi >= Ct.nbr() || bj >= nbc || rows.end > Ct.rows_split[size_t(bi) + 1] ||
+            cols.end > Ct.cols_split[size_t(bj) + 1])
+            throw refuse("inside one block, and Ct's split points cut it");
+        if (Ct.owners[size_t(bi) * size_t(nbc) + size_t(bj)] != rank)
+            throw refuse("on rank " + std::to_string(rank) + ", and rank " +
+                         std::to_string(Ct.owners[size_t(bi) * size_t(nbc) + size_t(bj)]) + " owns that block");
+        const eblock* blk = nullptr;
+        const auto it = by_cell.find(int64_t(bi) * nbc + bj);
+        if (it != by_cell.end())
+            for (const eblock* b : it->second)
+                if (b->rows.contains(rows) && b->cols.contains(cols)) blk = b;
+        if (!blk) throw refuse("inside one local block, and this rank holds no such block");
+        const int64_t dr = rows.start - blk->rows.start, dc = cols.start - blk->cols.start;
+        const int64_t off = ct_cm ? dc * blk->ld + dr : dr * blk->ld + dc;
+        if (off % g != 0)  // (a packed Ct: the op would start inside a byte / a 3-byte group)
+            throw error(COSTA_ERR_ARG,
+                        std::string("costa: ") + packed_rule(Ct.dtype) + ": an op starts " + std::to_string(off) +
+                            " elements into its block of Ct (" + dtype_name(Ct.dtype) + "; a multiple of " +
+                            std::to_string(g) + " is needed; rows " + std::to_string(t.col0) + " .., columns " +
+                            std::to_string(t.row0) + " .. of Ct)");
+        d.dst2 = reinterpret_cast<uintptr_t>(blk->data) + E.bytes(uint64_t(off));
+        d.ldd2 = blk->ld;
+        // f walks Ct's columns when it walks C's rows: contiguous in a row-major Ct (copy), strided in
+        // a column-major one (transpose); the other way round when f walks C's columns
+        d.flags2 = frow == ct_cm ? COSTA_TILE_TRANSPOSE : 0u;
+        out.push_back(d);
+    }
+    return out;
+}
+
+void check_dual_ops(costa_dtype_t dst_dtype, const std::vector<costa_dual_op_t>& ops, int c_axis, int ct_axis,
+                    int64_t m, int64_t n) {
+    std::vector<costa_scaled_op_t> first, twin;
+    first.reserve(ops.size());
+    twin.reserve(ops.size());
+    for (const costa_dual_op_t& t : ops) {
+        first.push_back(t.s);
+        twin.push_back(dual_twin_op(t));
+    }
+    if (c_axis >= 0) check_mx_ops(first, c_axis, m, n);
+    if (ct_axis >= 0) {
+        try {
+            check_mx_ops(twin, ct_axis, n, m);
+        } catch (const error& e) {  // (the same rule and text, naming the output it failed on)
+            std::string msg = e.what();
+            const std::string of_c = "MX block of C:";
+            const size_t at = msg.find(of_c);
+            if (at != std::string::npos) msg.replace(at, of_c.size(), "MX block of Ct (the transposed output):");
+            throw error(e.code, msg);
+        }
+    }
+    if (dtype_is_packed(dst_dtype)) {
+        check_packed_ops(COSTA_FLOAT, dst_dtype, first);
+        check_packed_ops(COSTA_FLOAT, dst_dtype, twin);
+    }
+}
+
+void execute_tiles_mx_dual(costa_dtype_t dst_dtype, const costa_dual_op_t* ops, int64_t n_ops, const void* src_base,
+                           void* dst_base, void* dst2_base, const void* scalars, int n_slots,
+                           const costa_mx_scales_t* c_scales, const costa_mx_scales_t* ct_scales, int rounding,
+                           int64_t m, int64_t n, const uint64_t* seed, int device) {
+    std::lock_guard<std::recursive_mutex> lk(g_mutex);
+    const std::string who = "costa_hip_execute_tiles_mx_dual";
+    if (dst_dtype == COSTA_FLOAT || !mx_pair(COSTA_FLOAT, dst_dtype))
+        throw error(COSTA_ERR_ARG, who + ": no dual MX kernel for FLOAT -> " + dtype_name(dst_dtype));
+    if (!c_scales || !c_scales->data) throw error(COSTA_ERR_ARG, who + ": c_scales is required");
+    if (!ct_scales || !ct_scales->data) throw error(COSTA_ERR_ARG, who + ": ct_scales is required");
+    if (rounding != COSTA_MX_FLOOR && rounding != COSTA_MX_CEIL)
+        throw error(COSTA_ERR_ARG, who + ": rounding must be COSTA_MX_FLOOR or COSTA_MX_CEIL");
+    if (m < 0 || n < 0) throw error(COSTA_ERR_ARG, who + ": negative matrix extent");
+    std::vector<costa_dual_op_t> v(ops, ops + n_ops);
+    std::vector<costa_scaled_op_t> first;
+    for (const costa_dual_op_t& t : v) first.push_back(t.s);
+    check_ops_inside(who, first, m, n);
+    check_mx_scales(*c_scales, m, n, who + ": c_scales");
+    check_mx_scales(*ct_scales, n, m, who + ": ct_scales");
+    check_no_axpby(who, first);
+    check_dual_ops(dst_dtype, v, c_scales->axis, ct_scales->axis, m, n);
+    const mx_sr keys = seed ? mx_sr_keys(*seed) : mx_sr{};
+    ctx(device);  // (is_device_ptr needs the device's context)
+    scale_tensors_on_device(who, c_scales->data, ct_scales->data);
+    const mx_side s1 = mx_side_of(*c_scales, false), s2 = mx_side_of(*ct_scales, false);
+    const uintptr_t sb = reinterpret_cast<uintptr_t>(src_base), db = reinterpret_cast<uintptr_t>(dst_base),
+                    db2 = reinterpret_cast<uintptr_t>(dst2_base);
+    g_mx_dual_items += run_strip_tiles(
+        who, v.data(), n_ops, scalars, n_slots, sizeof(float), device,
+        [&](const auto& l, auto& ord, auto& w) { return build_dual_work(dst_dtype, l, sb, db, db2, ord, w, false); },
+        [&](const costa_dual_op_t* d_ops, const uint64_t* d_work, const strip_list& l, const void* d_scal, void* s) {
+            launch_mx_dual(dst_dtype, d_ops, d_work, l, static_cast<const char*>(src_base),
+                           static_cast<char*>(dst_base), static_cast<char*>(dst2_base), d_scal, s1, s2,
+                           rounding == COSTA_MX_CEIL, s, seed ? &keys : nullptr);
+        });
+}
+
+int64_t mx_dual_items(bool reset) {
+    std::lock_guard<std::recursive_mutex> lk(g_mutex);
+    const int64_t v = g_mx_dual_items;
+    if (reset) g_mx_dual_items = 0;
     return v;
 }
 

@@ -126,6 +126,11 @@ struct job {
     // not of the plan: the cache key does not see it)
     bool mx_sr = false;
     uint64_t mx_seed = 0;
+    // ... and, for costa_hip_transform_mx_dual, the second target and its descriptor: the plan is that of
+    // (A, C, trans), every LOCAL / UNPACK op gets a twin in Ct and the lists run on mx_dual_kernel.  Ct is
+    // part of the plan's cache key (the twins hold its addresses)
+    const elayout* Ct = nullptr;
+    costa_mx_scales_t ct_scales{};
     // block-scaled FP8 transforms (costa_hip_transform_block_scaled): likewise a scaled job, its lists
     // on block_kernel
     bool blk = false;
@@ -444,6 +449,36 @@ void execute_tiles_mx(costa_dtype_t src_dtype, costa_dtype_t dst_dtype, const co
                       int64_t m, int64_t n, int a_transposed, int device, const uint64_t* seed = nullptr);
 // sub-tiles run by mx_kernel since the last reset
 int64_t mx_items(bool reset);
+// ---- dual-output MX quantise (mx_dual_kernels.hip; costa_hip.h, "Dual-output MX quantise") ----
+// mx_dual_kernel<Ed, SR> on costa_dual_op_t: FLOAT -> Q into output 1 (the scaled op) and, from the same
+// load, into output 2 (dst2 / ldd2 / flags2), whose element has target coordinates (j, i).
+// The work list: build_scaled_work's rule for output 1's sides, the same alignment rule for output 2's
+// VEC_DST at its own address; any_transpose where either output transposes
+strip_list build_dual_work(costa_dtype_t dst_dtype, const std::vector<costa_dual_op_t>& ops, uint64_t src_base,
+                           uint64_t dst_base, uint64_t dst2_base, std::vector<costa_dual_op_t>& ordered,
+                           std::vector<uint64_t>& work, bool dst_order);
+// c_scales in C's coordinates, ct_scales in Ct's (both required)
+void launch_mx_dual(costa_dtype_t dst_dtype, const costa_dual_op_t* d_ops, const uint64_t* d_work,
+                    const strip_list& l, const char* src_base, char* dst_base, char* dst2_base,
+                    const void* d_scalars, const mx_side& c_scales, const mx_side& ct_scales, bool ceil,
+                    void* stream /* hipStream_t */, const mx_sr* sr = nullptr);
+// output 2's op as a scaled op of its own n x m matrix (row0 / col0 swapped, F_ROWS complemented, its
+// address, leading dimension and store mode): what the per-op rules are checked on
+costa_scaled_op_t dual_twin_op(const costa_dual_op_t& t);
+// the twin of every op: rows [c0, c1) x columns [r0, r1) of Ct lie inside one block of Ct that is
+// local to `rank` (throws COSTA_ERR_ARG, "dual layouts", with the rectangle)
+std::vector<costa_dual_op_t> dual_twins(const std::vector<costa_scaled_op_t>& ops, const elayout& Ct, int rank);
+// the per-op rules of both outputs on dual ops: "MX block" along each output's axis (axis < 0: not
+// checked; the message names the output), the packed rules on both destinations
+void check_dual_ops(costa_dtype_t dst_dtype, const std::vector<costa_dual_op_t>& ops, int c_axis, int ct_axis,
+                    int64_t m, int64_t n);
+// costa_hip_execute_tiles_mx_dual: m x n is output 1's matrix
+void execute_tiles_mx_dual(costa_dtype_t dst_dtype, const costa_dual_op_t* ops, int64_t n_ops, const void* src_base,
+                           void* dst_base, void* dst2_base, const void* scalars, int n_slots,
+                           const costa_mx_scales_t* c_scales, const costa_mx_scales_t* ct_scales, int rounding,
+                           int64_t m, int64_t n, const uint64_t* seed, int device);
+// sub-tiles run by mx_dual_kernel since the last reset (mx_items does not count them)
+int64_t mx_dual_items(bool reset);
 // ---- block-scaled FP8 transforms (block_kernels.hip; costa_hip.h, "Block-scaled FP8 transforms") ----
 // block_kernel<Es, Ed, QUANT> on the scaled ops of a scaled plan: dequantising lists run the plan's
 // 64 x 64 work items (build_scaled_work), quantising ones 128 x 128 regions (build_block_work, whose

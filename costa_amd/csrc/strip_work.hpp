@@ -1,6 +1,7 @@
 // Work lists of the strip kernel families (convert_kernels.hip, half_kernels.hip, fp8_kernels.hip,
-// tri_kernels.hip, scaled_kernels.hip, mx_kernels.hip; launched by strip_launch.hpp): the alignment rule of the VEC
-// flags and the one builder behind build_convert_work, build_tri_work and build_scaled_work.
+// tri_kernels.hip, scaled_kernels.hip, mx_kernels.hip, mx_dual_kernels.hip; launched by strip_launch.hpp): the
+// alignment rule of the VEC flags and the one builder behind build_convert_work, build_tri_work,
+// build_scaled_work and build_dual_work.
 // Integer arithmetic on op descriptors only: no HIP in it.
 #pragma once
 

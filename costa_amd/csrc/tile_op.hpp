@@ -129,6 +129,8 @@ COSTA_HD inline const costa_tile_op_t& tile_of(const costa_scaled_op_t& o) { ret
 COSTA_HD inline costa_tile_op_t& tile_of(costa_tile_op_t& o) { return o; }
 COSTA_HD inline costa_tile_op_t& tile_of(costa_tri_op_t& o) { return o.op; }
 COSTA_HD inline costa_tile_op_t& tile_of(costa_scaled_op_t& o) { return o.op; }
+COSTA_HD inline const costa_tile_op_t& tile_of(const costa_dual_op_t& o) { return o.s.op; }
+COSTA_HD inline costa_tile_op_t& tile_of(costa_dual_op_t& o) { return o.s.op; }
 
 // kept elements of an edge op
 COSTA_HD inline int64_t tri_kept(const costa_tri_op_t& t) {

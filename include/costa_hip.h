@@ -701,6 +701,80 @@ int costa_hip_execute_tiles_mx_sr(costa_dtype_t src_dtype, costa_dtype_t dst_dty
 /* U(seed, i, j) above (host only, no GPU) */
 int costa_hip_sr_bits(uint64_t seed, int64_t i, int64_t j, uint32_t* u24);
 
+/* ---- Dual-output MX quantise (MI355X-native): C and its transpose from one pass over A ----
+ * The two quantised copies an MX GEMM training step consumes -- op(A) with its blocks along one
+ * reduction dimension and op(A)^T with its blocks cut anew along the other -- from ONE read of the
+ * fp32 source: one launch per phase, the fp32 package exchanged once.
+ *
+ * Arguments.  A is COSTA_FLOAT.  C and Ct hold the same Q, one of COSTA_FP8_E4M3, COSTA_FP8_E5M2,
+ * COSTA_FP4_E2M1, COSTA_FP6_E2M3, COSTA_FP6_E3M2.  With op(A) an m x n matrix C describes an m x n
+ * matrix and Ct an n x m one.  alpha is fp32; there is no beta (both outputs are quantised).
+ * `rounding` is the floor / ceil rule, shared by both outputs.  sr_seed == NULL rounds to nearest;
+ * otherwise both outputs are those of the _sr calls with *sr_seed, each element's random bits keyed
+ * on its row and column in its OWN output's matrix: (i, j) in C, (j, i) in Ct.
+ *
+ * Result.  The bytes of C and c_scales are those of costa_hip_transform_mx(A, C, trans, alpha,
+ * beta = 0, NULL, c_scales, rounding, comm); the bytes of Ct and ct_scales those of the same call on
+ * (A, Ct) with the opposite trans ('T' where trans is 'N', 'N' where it is 'T' or 'C').
+ *
+ * Scale tensors.  c_scales is indexed by C's matrix and ct_scales by Ct's; each has its own axis and
+ * strides and all four axis combinations are valid.  The two tensors must not overlap (not checked).
+ *
+ * Twin rule ("dual layouts").  The plan is the scaled plan of (A, C, trans).  For an op of its LOCAL
+ * and UNPACK lists that covers rows [r0, r1) x columns [c0, c1) of C, rows [c0, c1) x columns
+ * [r0, r1) of Ct must lie inside one block of Ct that is local to this rank (after any rank
+ * relabelling).  Transposed split points with transposed owners always satisfy it, coarser blocks
+ * of Ct too.  A violation is COSTA_ERR_ARG with "dual layouts" and the offending rectangle, raised
+ * before anything is written.  Since the ops of all ranks tile C exactly once, every element of Ct is
+ * then written exactly once.
+ *
+ * Block rule.  "MX block" holds for each output along its own axis: on C's ops as for
+ * costa_hip_transform_mx, and on the transposed ops for Ct; the message says which output failed.
+ * The "FP4 pair" / "FP6 quad" rules hold on Ct's side for the transposed ops.
+ *
+ * Other checks (COSTA_ERR_ARG naming what was wrong; C, Ct and both tensors untouched): A not
+ * COSTA_FLOAT, or C and Ct of different types or not an MX type ("no dual MX transform"); Ct's shape
+ * not n x m ("dual layouts"); a missing descriptor ("c_scales is required" / "ct_scales is
+ * required"); the stride / aliasing rule per tensor against its own matrix; an unknown rounding value;
+ * Ct the same layout object as A or C; a host-resident layout or tensor ("device-resident").
+ *
+ * Several ranks.  The exchange is that of (A, C, trans): fp32 packages, sent once.  Only LOCAL and
+ * UNPACK write; a rank writes the scale bytes of the blocks it owns in C and in Ct and no other byte.
+ * Emulated communicators and _async work as for costa_hip_transform_mx.  The cached plan is keyed on
+ * Ct's layout content too; a plain costa_hip_transform_mx(A, C) keeps its own plan.
+ *
+ * Not covered: Q or half sources, different Q types for C and Ct, beta, batches, masks, host staging,
+ * costa_hip_transform_block_scaled. */
+int costa_hip_transform_mx_dual(costa_layout_t A, costa_layout_t C, costa_layout_t Ct, char trans,
+                                const void* alpha, const costa_mx_scales_t* c_scales,
+                                const costa_mx_scales_t* ct_scales, int rounding, const uint64_t* sr_seed,
+                                costa_comm_t comm);
+int costa_hip_transform_mx_dual_async(costa_layout_t A, costa_layout_t C, costa_layout_t Ct, char trans,
+                                      const void* alpha, const costa_mx_scales_t* c_scales,
+                                      const costa_mx_scales_t* ct_scales, int rounding,
+                                      const uint64_t* sr_seed, costa_comm_t comm, void* stream);
+/* the op of mx_dual_kernel: output 1 exactly as costa_hip_execute_tiles_mx takes it, and where source
+ * element (f, s) goes in output 2, whose element has target coordinates (j, i) and whose F_ROWS is the
+ * complement of the op's */
+typedef struct {
+    costa_scaled_op_t s; /* output 1 */
+    uint64_t dst2;       /* output 2: byte offset added to dst2_base (absolute when the base is NULL) */
+    int32_t ldd2;        /* elements */
+    uint32_t flags2;     /* COSTA_TILE_TRANSPOSE: dst2(f*ldd2 + s), else dst2(s*ldd2 + f); the library
+                            sets COSTA_TILE_VEC_DST */
+} costa_dual_op_t; /* 64 bytes */
+/* dual ops of COSTA_FLOAT -> dst_dtype in ONE launch of mx_dual_kernel; fp32 scalars.  m x n is output
+ * 1's matrix (c_scales is indexed by it, ct_scales by the n x m one).  The per-op checks run on the
+ * ops: the block rule and the packed rules on both outputs, kind not AXPBY.  sr_seed as above. */
+int costa_hip_execute_tiles_mx_dual(costa_dtype_t dst_dtype, const costa_dual_op_t* ops, int64_t n_ops,
+                                    const void* src_base, void* dst_base, void* dst2_base,
+                                    const void* scalars, int n_slots, const costa_mx_scales_t* c_scales,
+                                    const costa_mx_scales_t* ct_scales, int rounding, int64_t m, int64_t n,
+                                    const uint64_t* sr_seed, int device);
+/* sub-tiles run by mx_dual_kernel since the last reset (costa_hip_mx_items does not count them) */
+int costa_hip_mx_dual_items(int64_t* items, int reset);
+/* (costa_hip_plan_export_dual, host only: below, with the other plan exports) */
+
 /* ---- Block-scaled FP8 transforms (fp32 scales) (MI355X-native): 1 x 128 / 128 x 128 blocks, fused ----
  * FP8 data with one fp32 scale per 1 x 128 group of a row, 128 x 1 group of a column or 128 x 128
  * tile ("blockwise" / DeepSeek-style scaling), produced or consumed in the pass that redistributes
@@ -929,6 +1003,15 @@ int costa_hip_plan_export_scaled(costa_layout_t A, costa_layout_t C, char trans,
                                  costa_scaled_op_t* local_scaled, costa_scaled_op_t* unpack_scaled,
                                  int64_t* send_counts, int64_t* send_displs, int64_t* recv_counts,
                                  int64_t* recv_displs, void* scalars);
+/* ... and of a dual-output MX quantise ("Dual-output MX quantise"): the LOCAL and UNPACK dual ops of
+ * `rank`, in the order of costa_hip_plan_export_scaled(A, C, trans), whose pack ops, counts and
+ * scalars are the call's.  A first call with NULL arrays returns the counts in
+ * info->n_local_scaled / n_unpack_scaled; the twin rule, both block rules (with c_axis / ct_axis,
+ * COSTA_MX_ROWS or COSTA_MX_COLS; -1: not checked) and the packed rules raise their errors. */
+int costa_hip_plan_export_dual(costa_layout_t A, costa_layout_t C, costa_layout_t Ct, char trans,
+                               const void* alpha, int c_axis, int ct_axis, int rank, int nranks,
+                               costa_scaled_plan_info_t* info, costa_dual_op_t* local_dual,
+                               costa_dual_op_t* unpack_dual);
 
 /* ---- measurement ----
  * With profiling on, every kernel launch and exchange is bracketed by HIP events on
